@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- denoising steps/sec of the Seva 1.3B hot path on MI355X (driver contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one Euler-EDM sampler step over one 21-view window at 576x576 (latent 72x72): noise
@@ -264,7 +264,13 @@ def main():
     ap.add_argument("--other-steps", type=int, default=5, help="timed steps of each `other_configs` steps/s leg")
     ap.add_argument("--leg-traj-steps", type=int, default=4,
                     help="sampler steps per window of the 168-view trajectory legs on the default line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the sampler state the last timed step returned (what a caller of "
+                         "sampler_step receives: T x 4 x latent x latent) as DIR/latents.npy, float32, rank 0; inputs and the "
+                         "per-step noise are seeded, so two runs with the same arguments see the same inputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -296,7 +302,9 @@ def main():
     if args.trajectory:
         return trajectory_mode(args, net, device, rank, world)
     total_steps = K + Wm
-    sampler, denoise, noise, cond, uc, gk = make_sampler(net, device, T, hw, max(total_steps, 2), 23 + rank)
+    # the DDPM schedule holds at most 1000 sigmas: longer runs cycle through it, so --steps is always the number of timed steps
+    n_sched = min(max(total_steps, 2), 1000)
+    sampler, denoise, noise, cond, uc, gk = make_sampler(net, device, T, hw, n_sched, 23 + rank)
     cond_assembly_ms = getattr(make_sampler, "cond_assembly_ms", None)  # (of the headline window; later legs overwrite the attribute)
 
     # anchors shared by adjacent windows (first-pass output; here: this rank's input-view latent)
@@ -304,9 +312,11 @@ def main():
     x, s_in, sigmas, num_sigmas, cond, uc = sampler.prepare_sampling_loop(noise, cond, uc, None)
 
     def step(i, xx):
+        i %= num_sigmas - 1
         return sampler.sampler_step(s_in * sigmas[i], s_in * sigmas[i + 1], denoise, xx, 2.0, cond, uc,
                                     0.0, **gk)
 
+    torch.cuda.manual_seed(23 + rank)  # the per-step noise draws (sampler_step's eps) are the same from run to run
     with torch.no_grad():
         # set-up (like a compile step, outside warm-up and timing): the first call of a trajectory runs eagerly and fills
         # every cache, the second captures the whole sampler step into one hipGraph; W warm-up and K timed steps replay it
@@ -332,6 +342,11 @@ def main():
         elapsed = time.perf_counter() - t0
     if not torch.isfinite(x).all():
         raise SystemExit("non-finite sampler state")
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), x.detach().float().cpu().numpy())
     tmax = torch.tensor([elapsed], device=device, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

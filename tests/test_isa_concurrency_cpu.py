@@ -10,6 +10,7 @@ import os
 import re
 import subprocess
 import sys
+import tarfile
 
 import pytest
 
@@ -105,21 +106,18 @@ def test_lint_scanner_on_synthetic_streams():
 def test_lint_is_red_on_the_sources_before_the_two_fixes(tmp_path):
     """Round 3's two non-repeatable kernels, as they were BEFORE commit 031eb80 (`git show 251746c:...`): the scanner flags exactly the
     instructions that were at fault -- `v_pk_fma_f32` reading the modulation loads' registers in the modulated GroupNorm apply, and
-    `v_pk_add_f32` reading `ds_bpermute_b32` results in the fused feed-forward's LayerNorm prologue."""
-    rel = "stable-virtual-camera_amd/csrc/"
-    old = {}
-    for name, rev in (("norm.hip", "251746c"), ("ff_fused.hip", "12312b2"), ("seva_common.h", "251746c"), ("gemm_common.h", "251746c")):
-        r = subprocess.run(["git", "-C", ROOT, "show", f"{rev}:{rel}{name}"], capture_output=True, text=True)
-        if r.returncode != 0:
-            pytest.skip("no git history here")
-        old[name] = r.stdout
+    `v_pk_add_f32` reading `ds_bpermute_b32` results in the fused feed-forward's LayerNorm prologue.
+
+    The old sources are stored byte for byte in tests/golden/isa_lint_pre_fix.tar.gz (csrc/norm.hip, seva_common.h, gemm_common.h and
+    include/seva_hip.h at 251746c; csrc/ff_fused.hip at 12312b2), so the test needs no git history."""
+    with tarfile.open(os.path.join(ROOT, "tests", "golden", "isa_lint_pre_fix.tar.gz")) as tf:
+        old = {m.name: tf.extractfile(m).read().decode() for m in tf.getmembers() if m.isfile()}
     d = tmp_path / "csrc"
     d.mkdir()
     (tmp_path / "include").mkdir()
-    hdr = subprocess.run(["git", "-C", ROOT, "show", "251746c:include/seva_hip.h"], capture_output=True, text=True).stdout
-    (tmp_path / "include" / "seva_hip.h").write_text(hdr)
+    (tmp_path / "include" / "seva_hip.h").write_text(old.pop("include/seva_hip.h"))
     for name, text in old.items():
-        (d / name).write_text(text.replace('"../../include/seva_hip.h"', '"../include/seva_hip.h"'))
+        (tmp_path / name).write_text(text.replace('"../../include/seva_hip.h"', '"../include/seva_hip.h"'))
     gn = isa_lint.kernels(isa_lint.compile_to_asm(str(d / "norm.hip")))
     hits = [h for k, b in gn.items() if "gn_apply_kernelILb1E" in k for h in isa_lint.lint_body(b)]
     assert any(rd.startswith("v_pk_fma_f32") and ld.startswith("global_load") for _, ld, rd in hits), hits[:4]

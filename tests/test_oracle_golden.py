@@ -1,5 +1,6 @@
 """Pins the CPU oracle (oracle/*.py) against golden vectors produced by the reference itself
 (oracle/make_goldens.py).  CPU-only; these run under `-m "not gpu"`."""
+import math
 import os
 import sys
 
@@ -125,8 +126,18 @@ def test_g2_conv_blocks():
     assert rel_l2(O.upsample(up, "m", g["x"]), g["up"]) < TOL
     assert rel_l2(O.downsample(dn, "m", g["x"]), g["down"]) < TOL
     g = load_golden("g2_temb")
-    assert torch.allclose(O.timestep_embedding(g["t"], 320), g["y320"], atol=1e-6)
-    assert torch.allclose(O.timestep_embedding(g["t"], 64), g["y64"], atol=1e-6)
+    for dim in (320, 64):
+        err = (O.timestep_embedding(g["t"], dim) - g[f"y{dim}"]).abs()
+        assert (err <= _temb_tol(g["t"], dim)).all(), (dim, float(err.max()))
+
+
+def _temb_tol(t, dim, max_period=10000):
+    """1e-6 plus two ulps of the fp32 argument t * freq of each cos / sin.  For t near 1000 the argument's own rounding moves the
+    result by up to ~1e-4, and the last-ulp choices of exp / cos / sin differ between CPUs' math paths: 1e-6 flat held only
+    where they matched the library that produced the golden bit for bit."""
+    half = dim // 2
+    a = (t[:, None].double() * torch.exp(-math.log(max_period) * torch.arange(half, dtype=torch.float64) / half)).abs()
+    return 1e-6 + torch.cat([a, a], dim=-1) * 2.0**-22
 
 
 def _golden_shapes(tag):
