@@ -187,6 +187,18 @@ typedef struct seva_attn_desc {
 } seva_attn_desc;
 int seva_attention_f16(const seva_attn_desc* d, seva_stream_t stream);
 
+/* fp8 P.V attention (ABI 9; the opt-in `attention="fp8"` sub-option of the fp8 precision mode): the same operator for the long
+ * sequences (lq >= 2048) with P and V in OCP e4m3 on the block-scaled MFMA; Q K^T stays f16.  V is first quantised into a private
+ * workspace -- e4m3 values in the kernel's key order plus one E8M0 (power-of-two) scale byte per 32 keys and channel, per sample,
+ * keys >= lk zero-padded -- by seva_attn_quant_v_fp8, which reads d->v through the k strides (nb0 / nb1 / token); then
+ * seva_attention_pv8 reads q, k (f16, the desc's strides), the quantised V and writes out.  q must be pre-scaled (q_prescaled);
+ * split_ws as for seva_attention_f16 (the split is a function of lk alone).  The row sum is taken from the quantised P, the
+ * probabilities stay below 2^8 (rescale whenever a score passes the running reference by 8).  Accuracy class of the fp8 mode.
+ * seva_attn_v_fp8_size: bytes of the two workspace parts for `batch` = nb0 * nb1 samples. */
+int seva_attn_v_fp8_size(int32_t batch, int32_t heads, int32_t lk, int64_t* v8_bytes, int64_t* scale_bytes);
+int seva_attn_quant_v_fp8(const seva_attn_desc* d, void* v8, uint8_t* v8_scale, seva_stream_t stream);
+int seva_attention_pv8(const seva_attn_desc* d, const void* v8, const uint8_t* v8_scale, seva_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * GroupNorm (fp32 statistics) over a channels-last tensor that may be the channel
  * concatenation of two sources (the UNet skip concat, seva/model.py:206-207, is never

@@ -16,6 +16,7 @@
 // regime (L = num_frames <= 32, batch = pixels) uses one wave per (pixel, head) with a 32-key
 // tile and reads its tokens through the token stride, so no (b t) s c <-> (b s) t c transpose exists.
 #include "seva_common.h"
+#include "attn_pv8.h"
 
 #include <stdlib.h>
 
@@ -1130,6 +1131,18 @@ int launch(const AttnArgs& a, int64_t batch, hipStream_t s, bool use_tr, bool pr
 }
 
 }  // namespace
+
+// attn_combine_kernel for the K/V-split fp8 P.V kernel (attention_fp8.hip: same partial layout as attn16_kernel<64, true>)
+int seva_attn_combine_launch(const float* part_o, const float* part_ml, int nsplit, void* out, int64_t o_sb0, int64_t o_sb1,
+                             int64_t o_sl, int nb1, int heads, int lq, int64_t rows_all, hipStream_t s) {
+  AttnArgs a{};
+  a.out = (half_t*)out;
+  a.o_sb0 = o_sb0; a.o_sb1 = o_sb1; a.o_sl = o_sl;
+  a.nb1 = nb1; a.heads = heads; a.lq = lq;
+  a.part_o = (float*)part_o; a.part_ml = (float*)part_ml; a.nsplit = nsplit;
+  hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((rows_all * 8 + 255) / 256)), dim3(256), 0, s, a, rows_all);
+  return seva_check_launch("attn_combine_kernel");
+}
 
 extern "C" int seva_attention_f16(const seva_attn_desc* d, seva_stream_t stream) {
   SEVA_REQUIRE(d != nullptr, "attention: null desc");

@@ -93,7 +93,7 @@ class SevaEngine:
         _native.load()
         return params[0].device
 
-    def __init__(self, model, precision: str | None = None):
+    def __init__(self, model, precision: str | None = None, attention: str | None = None):
         """precision "f16" (default; the parity mode, fp16 operands / fp32 accumulation) or "fp8" (BASELINE config 5:
         e4m3 weights AND activations on the block-scaled fp8 MFMA for the QKV / GEGLU / FF2 projections and the ResBlock 3x3
         convs whose reduction length is a multiple of 128 -- the C = 640 / 1280 levels; the C = 320 level (opt-in through
@@ -105,6 +105,16 @@ class SevaEngine:
         if self.precision not in ("f16", "fp8"):
             raise ValueError(f"unknown precision {self.precision!r} (f16 | fp8)")
         self.fp8 = self.precision == "fp8"
+        # fp8 mode's attention sub-option: "fp8" runs the long self-attention launches (lq >= ops.PV8_MIN_LQ, the ones
+        # seva_attention_f16 gives attn16_kernel) with P and V in e4m3 (seva_attention_pv8).  Not given: SEVA_FP8_ATTENTION=0|1.
+        if attention is None:
+            attention = "fp8" if self.fp8 and _os.environ.get("SEVA_FP8_ATTENTION", "0") == "1" else "f16"
+        if attention not in ("f16", "fp8"):
+            raise ValueError(f"unknown attention {attention!r} (f16 | fp8)")
+        if attention == "fp8" and not self.fp8:
+            raise ValueError('attention="fp8" needs precision "fp8" (the f16 parity mode stays pure)')
+        self.attention = attention
+        self.pv8 = attention == "fp8"
         # fp8 mode only: also take reductions that need zero-padding to a multiple of 128 (C = 320 -> 384, 960 -> 1024).  Off by
         # default -- measured (profiles/r02_bench_T21_fp8_pad320.json): the C = 320 level then leaves the fused f16 feed-forward
         # for the two-kernel fp8 path, the step stays at 86.1 ms and the error doubles (rel-L2 2.9e-2 -> 5.2e-2).
@@ -477,23 +487,33 @@ class SevaEngine:
         att = self._buf("att", (rows, c), F16)
         q, k, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
         if regime == "frame":  # batch = frame, tokens = pixels
-            ops.attention(q, k, v, att, nb0=n, nb1=1, heads=heads, lq=hw, lk=hw,
-                          q_strides=(hw * c3, 0, c3), k_strides=(hw * c3, 0, c3), o_strides=(hw * c, 0, c),
-                          q_prescaled=True)
+            self._attention_long(q, k, v, att, nb0=n, heads=heads, L=hw, q_strides=(hw * c3, 0, c3),
+                                 k_strides=(hw * c3, 0, c3), o_strides=(hw * c, 0, c), split_ws=None)
         elif regime == "joint":  # batch = scene, tokens = (frame, pixel)
             # long key sequences (L = T hw >= 6144) run K/V-split: the workspace for the two partial results
             sws = None
             if self.attn_split and T * hw >= ops.ATTN_SPLIT_MIN_LK:
                 sws = self._buf("attn_split", (ops.attention_split_workspace_numel(n // T, heads, T * hw, self.attn_split_max),), F32)
-            ops.attention(q, k, v, att, nb0=n // T, nb1=1, heads=heads, lq=T * hw, lk=T * hw,
-                          q_strides=(T * hw * c3, 0, c3), k_strides=(T * hw * c3, 0, c3),
-                          o_strides=(T * hw * c, 0, c), q_prescaled=True, split_ws=sws)
+            self._attention_long(q, k, v, att, nb0=n // T, heads=heads, L=T * hw, q_strides=(T * hw * c3, 0, c3),
+                                 k_strides=(T * hw * c3, 0, c3), o_strides=(T * hw * c, 0, c), split_ws=sws)
         else:  # temporal: batch = (scene, pixel), tokens = frames, read through strides
             ops.attention(q, k, v, att, nb0=n // T, nb1=hw, heads=heads, lq=T, lk=T,
                           q_strides=(T * hw * c3, c3, hw * c3), k_strides=(T * hw * c3, c3, hw * c3),
                           o_strides=(T * hw * c, c, hw * c), q_prescaled=True)
         ops.gemm(att, W[at_pfx + ".out.w"], bias=W[at_pfx + ".out.b"], residual=residual,
                  row_add=row_add, rows_per_group=rpg, ld_row_add=ldra, out_f32=out_f32)
+
+    def _attention_long(self, q, k, v, att, *, nb0, heads, L, q_strides, k_strides, o_strides, split_ws):
+        """Per-frame / joint self-attention (q pre-scaled).  fp8 attention sub-option: the launches of L >= ops.PV8_MIN_LQ (those
+        seva_attention_f16 runs on attn16_kernel) quantise V into an arena workspace and take seva_attention_pv8."""
+        if self.pv8 and L >= ops.PV8_MIN_LQ:
+            ws = self._buf("v_fp8", (ops.v_fp8_workspace_numel(nb0, heads, L),), U8)
+            ops.quantize_v_fp8(v, ws, nb0=nb0, nb1=1, heads=heads, lk=L, k_strides=k_strides)
+            ops.attention_pv8(q, k, ws, att, nb0=nb0, nb1=1, heads=heads, lq=L, lk=L, q_strides=q_strides,
+                              k_strides=k_strides, o_strides=o_strides, split_ws=split_ws)
+            return
+        ops.attention(q, k, v, att, nb0=nb0, nb1=1, heads=heads, lq=L, lk=L, q_strides=q_strides, k_strides=k_strides,
+                      o_strides=o_strides, q_prescaled=True, split_ws=split_ws)
 
     def _cross_attention_general(self, x32, ln_pfx, at_pfx, rows, c, heads, ctx16, lc, *, nb0, nb1,
                                  lq, q_strides, o_strides, ctx_batch_stride, out_f32):

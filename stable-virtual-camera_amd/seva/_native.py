@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SEVA_HIP_LIB: A/B benchmarking of two builds of the same library (tools/); default = the in-tree build
 LIB_PATH = os.environ.get("SEVA_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libseva_hip.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 PROF_CLASSES = 5
 PROF_NAMES = ("gemm", "conv", "attention", "norm", "elementwise")
 
@@ -87,6 +87,9 @@ SYMBOLS = {
     "seva_gemm_fp8": (c_int, [POINTER(GemmDesc), c_void_p]),
     "seva_ff_fused_f16": (c_int, [POINTER(FfDesc), c_void_p]),
     "seva_attention_f16": (c_int, [POINTER(AttnDesc), c_void_p]),
+    "seva_attn_v_fp8_size": (c_int, [c_int32, c_int32, c_int32, POINTER(c_int64), POINTER(c_int64)]),
+    "seva_attn_quant_v_fp8": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p]),
+    "seva_attention_pv8": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p]),
     "seva_groupnorm_f16": (c_int, [POINTER(GroupNormDesc), c_void_p]),
     "seva_layernorm_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
     "seva_layernorm_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_int64, c_void_p]),

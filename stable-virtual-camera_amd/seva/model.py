@@ -158,13 +158,20 @@ class Seva(nn.Module):
         if self._engine is None:
             from ._engine import SevaEngine
 
-            self._engine = SevaEngine(self, getattr(self, "_precision", None))
+            self._engine = SevaEngine(self, getattr(self, "_precision", None), getattr(self, "_attention", None))
         return self._engine
 
-    def set_precision(self, precision: str) -> "Seva":
+    def set_precision(self, precision: str, attention: str | None = None) -> "Seva":
         """"f16" (default, the parity mode) or "fp8" (BASELINE config 5: e4m3 operands on the fp8 MFMA where the reduction
-        length allows; separate accuracy class).  Re-packs the weights on the next forward."""
+        length allows; separate accuracy class).  Re-packs the weights on the next forward.
+        attention (fp8 mode only): "f16" (default) or "fp8" -- the long self-attention launches (L >= 2048) with P and V in e4m3
+        (seva_attention_pv8), an accuracy class of its own; None leaves the choice to SEVA_FP8_ATTENTION (0 / 1, default 0)."""
+        if attention not in (None, "f16", "fp8"):
+            raise ValueError(f"unknown attention {attention!r} (f16 | fp8)")
+        if attention == "fp8" and precision != "fp8":
+            raise ValueError('attention="fp8" needs precision "fp8" (the f16 parity mode stays pure)')
         self._precision = precision
+        self._attention = attention
         self._engine = None
         return self
 

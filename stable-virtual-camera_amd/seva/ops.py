@@ -282,6 +282,62 @@ def attention_split_workspace_numel(batch: int, heads: int, lq: int, nsplit: int
     return nsplit * batch * heads * lq * 66
 
 
+PV8_MIN_LQ = 2048  # query length from which seva_attention_f16 runs attn16_kernel: the launches the fp8 P.V kernel replaces
+
+
+def _v_fp8_parts(batch: int, heads: int, lk: int) -> tuple[int, int]:
+    v8, sc = C.c_int64(), C.c_int64()
+    check(_lib().seva_attn_v_fp8_size(batch, heads, lk, C.byref(v8), C.byref(sc)), "seva_attn_v_fp8_size")
+    return v8.value, sc.value
+
+
+def v_fp8_workspace_numel(batch: int, heads: int, lk: int) -> int:
+    """uint8 elements of the quantised-V workspace of `quantize_v_fp8` / `attention_pv8` (e4m3 values, then E8M0 scales)."""
+    v8, sc = _v_fp8_parts(batch, heads, lk)
+    return v8 + sc
+
+
+def _v_fp8_ptrs(ws: torch.Tensor, batch: int, heads: int, lk: int) -> tuple[int, int]:
+    v8, sc = _v_fp8_parts(batch, heads, lk)
+    assert ws.dtype == U8 and ws.is_contiguous() and ws.numel() >= v8 + sc, "v_fp8 workspace too small"
+    return ws.data_ptr(), ws.data_ptr() + v8
+
+
+def _attn_desc(q, k, v, out, nb0, nb1, heads, lq, lk, q_strides, k_strides, o_strides, split_ws) -> AttnDesc:
+    d = AttnDesc()
+    d.q, d.k, d.v, d.out = ptr(q), ptr(k), ptr(v), ptr(out)
+    d.q_sb0, d.q_sb1, d.q_sl = q_strides
+    d.k_sb0, d.k_sb1, d.k_sl = k_strides
+    d.o_sb0, d.o_sb1, d.o_sl = o_strides
+    d.nb0, d.nb1, d.heads, d.lq, d.lk = nb0, nb1, heads, lq, lk
+    d.q_prescaled = 1
+    if split_ws is not None:
+        assert split_ws.dtype == F32 and split_ws.is_contiguous()
+        d.split_ws, d.split_ws_bytes = split_ws.data_ptr(), split_ws.numel() * 4
+    return d
+
+
+def quantize_v_fp8(v: torch.Tensor, ws: torch.Tensor, *, nb0: int, nb1: int, heads: int, lk: int,
+                   k_strides: tuple[int, int, int]) -> None:
+    """V (f16, the attention strides) -> the e4m3 + E8M0 workspace `attention_pv8` reads (seva_attn_quant_v_fp8).
+    ws: uint8, at least v_fp8_workspace_numel(nb0 * nb1, heads, lk) elements."""
+    require_cuda(v, ws)
+    v8, sc = _v_fp8_ptrs(ws, nb0 * nb1, heads, lk)
+    d = _attn_desc(None, None, v, None, nb0, nb1, heads, lk, lk, (0, 0, 0), k_strides, (0, 0, 0), None)
+    check(_lib().seva_attn_quant_v_fp8(C.byref(d), v8, sc, stream_ptr(v.device)), "seva_attn_quant_v_fp8")
+
+
+def attention_pv8(q: torch.Tensor, k: torch.Tensor, ws: torch.Tensor, out: torch.Tensor, *, nb0: int, nb1: int, heads: int,
+                  lq: int, lk: int, q_strides: tuple[int, int, int], k_strides: tuple[int, int, int],
+                  o_strides: tuple[int, int, int], split_ws: torch.Tensor | None = None) -> None:
+    """`attention` (q pre-scaled by scale * log2(e)) with P and V in e4m3 on the block-scaled MFMA (seva_attention_pv8); V comes
+    from `ws`, filled by `quantize_v_fp8` with the same nb0 / nb1 / heads / lk.  The fp8 mode's opt-in attention sub-option."""
+    require_cuda(q, k, ws, out)
+    v8, sc = _v_fp8_ptrs(ws, nb0 * nb1, heads, lk)
+    d = _attn_desc(q, k, None, out, nb0, nb1, heads, lq, lk, q_strides, k_strides, o_strides, split_ws)
+    check(_lib().seva_attention_pv8(C.byref(d), v8, sc, stream_ptr(q.device)), "seva_attention_pv8")
+
+
 GN_WORKSPACE_SLABS = 1024  # include/seva_hip.h SEVA_GN_WORKSPACE_SLABS
 
 
