@@ -71,8 +71,9 @@ typedef struct seva_gemm_desc {
   int32_t epilogue;
   int32_t n, ih, iw, cin, oh, ow, stride, upsample;
   /* out[:, f] = (a @ w^T + bias)[:, f] * col_scale for f < col_scale_n (fp32, before the f16
-   * rounding); 0 columns = off.  Plain epilogue without residual / row_add only.  Used to fold the
-   * softmax scale * log2(e) into the q third of a fused QKV projection. */
+   * rounding); 0 columns = off.  Mode 0 only, plain epilogue without residual / row_add.  Used to fold the
+   * softmax scale * log2(e) into the q third of a fused QKV projection.  A convolution (mode 1) with
+   * col_scale_n > 0 is an ERROR: it used to be applied by the per-tap kernel and ignored by the window kernel. */
   float col_scale;
   int32_t col_scale_n;
   /* conv mode: 1 = zero padding only at the bottom / right edge (taps start AT pixel (stride*oy, stride*ox)); the

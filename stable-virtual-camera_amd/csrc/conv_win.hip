@@ -14,8 +14,8 @@
 // P(m) = img * S + (y + 1) Wp + (x + 1) and its tap (ky, kx) at P(m) + (ky - 1) Wp + (kx - 1), for every pixel of every image --
 // border taps land on frame cells, which the fill routes to the zero page.  A tile of BM consecutive output pixels needs
 // BM + (row crossings) + (W + 2 per image crossing) + 2 (W + 2) + 1 window pixels whatever its alignment, and the tap shift is
-// one workgroup-uniform scalar.  Tiles are consecutive pixels of the whole batch where that fits the window capacity (36x36
-// and smaller at 160 rows), consecutive pixels of ONE image otherwise (72x72).  Per slab and 160 x 160 tile the LDS-DMA traffic drops from
+// one workgroup-uniform scalar.  Tiles are consecutive pixels of the whole launch where that fits the window capacity (36x36
+// and smaller at 160 rows), consecutive pixels of ONE image otherwise (72x72); an output row gets the same bits either way.  Per slab and 160 x 160 tile the LDS-DMA traffic drops from
 // 9 * (160 + 160) * 128 B = 360 KiB to 316 * 128 B + 9 * 160 * 128 B = 220 KiB; the weight tile is now the main stream.
 //
 // Everything else is gemm.hip's core: K-tile 64, 128-byte LDS rows, lane-linear LDS-DMA with the chunk swizzle
@@ -35,6 +35,7 @@
 #include "gemm_common.h"
 
 #include <atomic>
+#include <numeric>
 #include <type_traits>
 
 namespace {
@@ -46,8 +47,8 @@ struct ConvWinGeom {
   int32_t Wp, Sp, hw;                       // hw = OUTPUT pixels per image; mul_iw divides by the OUTPUT width ow
   int32_t ow;
   int32_t tiles_m, tiles_n;
-  int32_t tpi;  // 0: M-tiles are consecutive BM-pixel ranges of the whole batch; > 0: tiles per image (a tile never leaves its image)
-  int32_t lin_ok;  // host only: the multiply-high divisions of the linear tiles are exact for this launch
+  int32_t tpi;  // 0: M-tiles are consecutive BM-pixel ranges of the whole launch; > 0: tiles per image (a tile never leaves its image)
+  int32_t n_lin;  // host only: images per launch of the linear tiles (31-bit offsets, exact multiply-high divisions); 0 = not even one
 };
 
 // UP: the conv input is the nearest-2x upsampled image (reference layers.py:35-46: F.interpolate(scale_factor=2) then conv): the window
@@ -448,16 +449,27 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
   }
   ConvWinGeom g = g0;
   g.tiles_n = (int)((a.N + BN - 1) / BN);
+  const auto go = [&](const GemmArgs& c, const ConvWinGeom& gc) {
+    const int64_t nb = (int64_t)gc.tiles_m * gc.tiles_n;
+    if (nb <= 0 || nb > 0x7fffffff) {
+      seva_set_error("conv_win: bad grid %lld", (long long)nb);
+      return SEVA_ERR_ARG;
+    }
+    hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8>), dim3((unsigned)nb), dim3(64 * NW), lds, s, c, gc);
+    return seva_check_launch("conv_win_kernel");
+  };
   if constexpr (TW > 0) {
     // 2-D tiles: whole tiles only, and (statistics) whole 64-pixel blocks per image
     constexpr int TH = BM / 16;
     if (a.ow % 16 != 0 || a.oh % TH != 0 || g.hw % 64 != 0) return 1;
     g.tpi = (a.oh / TH) * (a.ow / 16);
     g.tiles_m = a.n * g.tpi;
+    return go(a, g);
   } else {
-  if (!g.lin_ok) return 1;
-  // the widest window any tile needs must fit the instantiation's capacity: consecutive pixels of the whole batch if that fits
-  // (a tile may then straddle images), else consecutive pixels of one image, else the launch is not for this kernel
+  // Whether the linear tiles apply is decided from ONE image: the widest window of a tile of consecutive pixels of one image must fit
+  // the instantiation's capacity.  (Tiles over consecutive pixels of several images, which may straddle an image border, are never
+  // narrower than those of image 0 alone, so they cannot widen what applies.)  The output rows are the same bits however they are tiled.
+  if (g.n_lin <= 0 || g.Wp + 1 > WCAP) return 1;
   const auto window_len = [&](int64_t ma, int64_t mb) {  // the kernel's WL for output rows [ma, mb]
     const auto idx = [&](int64_t m, int64_t& x) {
       const int64_t img = m / g.hw, rem = m % g.hw, y = rem / g.ow;
@@ -469,36 +481,47 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
     const int64_t q0 = (UP ? pa - (xa >> 1) : pa) - (g.Wp + 1);
     return (UP ? pb - (xb >> 1) + a.iw - 1 : pb) - q0 + g.Wp + 2;
   };
-  const auto widest = [&](int tpi) {
-    const int64_t tiles = tpi > 0 ? (int64_t)tpi : (a.M + BM - 1) / BM;  // per-image tiling: every image has the same windows
-    int64_t wl_max = 0;
+  const auto fits = [&](int64_t rows, int tpi) {  // every tile's window <= WCAP; tpi > 0: tiles per image, else over `rows` consecutive rows
+    const int64_t tiles = tpi > 0 ? (int64_t)tpi : (rows + BM - 1) / BM;  // per-image tiling: every image has the same windows
+    const int64_t lim = tpi > 0 ? g.hw : rows;
     for (int64_t t = 0; t < tiles; ++t) {
-      const int64_t lim = tpi > 0 ? g.hw : a.M;
       const int64_t ma = t * BM, mb = ma + BM < lim ? ma + BM : lim;
-      const int64_t wl = window_len(ma, mb - 1);
-      if (wl > wl_max) wl_max = wl;
+      if (window_len(ma, mb - 1) > WCAP) return false;
     }
-    return wl_max;
+    return true;
   };
   const int tpi = (g.hw + BM - 1) / BM;
-  // (the scan over the tiles of the whole batch is bounded: a window of BM pixels + two rows cannot fit once a row exceeds the capacity)
-  if (g.Wp + 1 <= WCAP && (int64_t)a.M / BM <= 65536 && widest(0) <= WCAP) {
-    g.tpi = 0;
-    g.tiles_m = (int)((a.M + BM - 1) / BM);
-  } else if (g.Wp + 1 <= WCAP && widest(tpi) <= WCAP && !(a.ch_stats != nullptr && g.hw % 64 != 0)) {  // (statistics: 64-row blocks of the WHOLE tensor)
-    g.tpi = tpi;
-    g.tiles_m = a.n * tpi;
-  } else {
-    return 1;  // not applicable: the caller tries 2-D tiles, then falls back to the per-tap gather
+  if (!fits(g.hw, tpi)) return 1;  // not applicable: the caller tries 2-D tiles, then falls back to the per-tap gather
+  // Launches of at most n_lin images (the 31-bit offsets and multiply-high divisions of the linear tiles hold over that range; n_lin
+  // comes from per-image dimensions): outputs, residual, row_add and statistics move by whole images.  n_lin keeps a range's first row
+  // on a row_add group boundary, and the statistics need hw % 64 == 0, so a range starts on a 64-row block.
+  for (int64_t i0 = 0; i0 < a.n; i0 += g.n_lin) {
+    const int nc = (int)(a.n - i0 < g.n_lin ? a.n - i0 : g.n_lin);
+    const int64_t r0 = i0 * g.hw;
+    GemmArgs c = a;
+    c.n = nc;
+    c.M = (int64_t)nc * g.hw;
+    c.a = a.a + i0 * a.ih * a.iw * a.cin;
+    if (c.residual) c.residual += r0 * a.ldr;
+    if (c.out_f32) c.out_f32 += r0 * a.ldo32;
+    if (c.out_f16) c.out_f16 += r0 * a.ldo16;
+    if (c.row_add) c.row_add += (r0 / a.rows_per_group) * a.ldra;
+    if (c.ch_stats) c.ch_stats += (r0 / 64) * 2 * a.N;
+    ConvWinGeom gc = g;
+    // consecutive pixels of the whole range where that fits (a tile may then straddle images: fewer, fuller tiles), else one image's
+    // (the scan is bounded: a window of BM pixels + two rows cannot fit once a row exceeds the capacity)
+    if (c.M / BM <= 65536 && fits(c.M, 0)) {
+      gc.tpi = 0;
+      gc.tiles_m = (int)((c.M + BM - 1) / BM);
+    } else {
+      gc.tpi = tpi;
+      gc.tiles_m = nc * tpi;
+    }
+    const int rc = go(c, gc);
+    if (rc != 0) return rc;
   }
+  return 0;
   }
-  const int64_t nb = (int64_t)g.tiles_m * g.tiles_n;
-  if (nb <= 0 || nb > 0x7fffffff) {
-    seva_set_error("conv_win: bad grid %lld", (long long)nb);
-    return SEVA_ERR_ARG;
-  }
-  hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8>), dim3((unsigned)nb), dim3(64 * NW), lds, s, a, g);
-  return seva_check_launch("conv_win_kernel");
 }
 
 }  // namespace
@@ -517,6 +540,9 @@ int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
   g.Sp = (a.ih + 1) * g.Wp;
   g.hw = a.oh * a.ow;
   g.ow = a.ow;
+  // GroupNorm statistics are 64-row blocks of the whole tensor: only where a block cannot straddle two images (the consumer refuses other
+  // statistics anyway), for every batch size
+  if (a.ch_stats != nullptr && g.hw % 64 != 0) return 1;
   // 31-bit byte offsets into the image; exactness of the multiply-high divisions of the LINEAR tiles (2-D tiles divide by constants
   // only): mulhi(x, floor(2^32 / d) + 1) == x / d for every x with x * e < 2^32, e = (floor(2^32 / d) + 1) * d - 2^32 in (0, d]
   if ((uint64_t)a.ih * a.iw * a.cin * 2 >= (1ull << 31)) return 1;  // one image
@@ -524,9 +550,23 @@ int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
     const uint64_t e = (uint64_t)magic_u32(d) * d - (1ull << 32);
     return x_max < (1ull << 32) && x_max * e < (1ull << 32);
   };
-  const uint64_t q_max = (uint64_t)a.n * g.Sp + 1024;
-  g.lin_ok = (uint64_t)a.n * a.ih * a.iw * a.cin * 2 < (1ull << 31) && div_exact((uint64_t)a.M, (uint32_t)g.hw) &&
-             div_exact((uint64_t)g.hw, (uint32_t)g.ow) && div_exact(q_max, (uint32_t)g.Sp) && div_exact((uint64_t)g.Sp, (uint32_t)g.Wp);
+  // the terms that grow with the number of images hold up to some count n_lin: larger batches are launched as ranges of n_lin images
+  // (launch_win), so that whether the window kernel computes an image depends on per-image dimensions only
+  const auto lin_exact = [&](uint64_t nn) {
+    return nn * a.ih * a.iw * a.cin * 2 < (1ull << 31) && div_exact(nn * g.hw, (uint32_t)g.hw) && div_exact(nn * g.Sp + 1024, (uint32_t)g.Sp);
+  };
+  g.n_lin = 0;
+  if (div_exact((uint64_t)g.hw, (uint32_t)g.ow) && div_exact((uint64_t)g.Sp, (uint32_t)g.Wp) && lin_exact(1)) {
+    // largest count for which lin_exact holds -- NOT capped at n: n_lin must not depend on the batch
+    uint64_t lo = 1, hi = (1ull << 31) / ((uint64_t)a.ih * a.iw * a.cin * 2);
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi + 1) / 2;
+      if (lin_exact(mid)) lo = mid; else hi = mid - 1;
+    }
+    // row_add: a range of n_lin images must end on a group boundary (groups of rows_per_group rows count from row 0 of the tensor)
+    const uint64_t rpg = a.row_add ? (uint64_t)a.rows_per_group : 1, step = rpg / std::gcd(rpg, (uint64_t)g.hw);
+    g.n_lin = (int32_t)(lo / step * step);  // (< 2^31: lo is)
+  }
   g.mul_hw = magic_u32((uint32_t)g.hw);
   g.mul_iw = magic_u32((uint32_t)g.ow);
   g.mul_sp = magic_u32((uint32_t)g.Sp);
@@ -578,7 +618,9 @@ int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
   // (128 with statistics) or one 8-wave workgroup on a 256-row tile with the window double-buffered.  The 8-wave tile moves a third
   // fewer LDS-DMA bytes per FLOP and is ~5 % faster where its tile count fills whole rounds of the 256 CUs; the choice is made from
   // how the launch quantises (measured: 72x72 and 18x18 at batch 42 prefer 8 waves, 36x36 prefers 4: tools/kconvwin.py).  Which of
-  // the two RUNS may depend on the batch; whether the window kernel runs at all depends on per-sample dimensions only.
+  // the two RUNS may depend on the batch.  Whether the window kernel runs at all depends on per-sample dimensions only: a family applies
+  // when one image's tiles fit its window (launch_win), statistics need hw % 64 == 0 at every batch size, and a batch too large for the
+  // 32-bit index arithmetic of the linear tiles is launched as ranges of whole images (n_lin) instead of falling back to the gather.
   const auto launch4 = [&]() { return stats ? launch_win<128, 160, 4, 288, false, true>(a, g, s) : launch_win<160, 160, 4, 320, false, false>(a, g, s); };
   const auto launch8 = [&]() { return launch_win<256, 160, 8, 416, true, true>(a, g, s); };
   bool eight;

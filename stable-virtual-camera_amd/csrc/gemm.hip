@@ -955,8 +955,8 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
   a.col_scale_n = d->col_scale_n;
   SEVA_REQUIRE(d->col_scale_n >= 0 && d->col_scale_n % 4 == 0 && d->col_scale_n <= d->N,
                "gemm: col_scale_n=%d invalid", d->col_scale_n);
-  SEVA_REQUIRE(d->col_scale_n == 0 || (!d->residual && !d->row_add && d->epilogue == 0 && d->N > 32),
-               "gemm: col_scale needs the plain epilogue without residual / row_add");
+  SEVA_REQUIRE(d->col_scale_n == 0 || (d->mode == 0 && !d->residual && !d->row_add && d->epilogue == 0 && d->N > 32),
+               "gemm: col_scale needs mode 0 (no convolution) and the plain epilogue without residual / row_add");
   a.ldra = d->ld_row_add > 0 ? d->ld_row_add : d->N;
   SEVA_REQUIRE(a.ldra % 4 == 0, "gemm: ld_row_add must be a multiple of 4");
   if (d->mode == 1) {

@@ -323,8 +323,8 @@ class SevaEngine:
         if not self.conv_splitk:
             return None
         # sized from the launch (never below 512 slots), so that whether a small-image conv is split depends on the per-sample
-        # image size only and not on how many samples are batched (the library falls back to unsplit tiles when a workspace
-        # cannot hold the launch)
+        # image size only and not on how many samples are batched (a workspace that cannot hold a launch that qualifies for the
+        # split is an error in the library, not a fall-back to unsplit tiles: seva_gemm_desc.splitk_ws)
         tiles = max(512, ((rows + 127) // 128) * ((c + 127) // 128)) if hw and hw <= 128 else 512
         tiles = min(tiles, 16382)
         return self._buf("sk_ws", (16384 + tiles * 128 * 160,), F32, zero=True)
