@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- denoising steps/sec of the Seva 1.3B hot path on MI355X (driver contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one Euler-EDM sampler step over one 21-view window at 576x576 (latent 72x72): noise
@@ -13,15 +13,18 @@ N > 1: the windows of a long trajectory are independent work units (SURVEY.md §
 denoises its own window with replicated weights ("weak" scaling), after one RCCL all-gather of the
 anchor latents that adjacent windows share.  value = (steps of all ranks) / max-over-ranks time.
 
-Extra objects on the JSON line: `roofline` (dominant kernel class, algorithmic FLOP / HIP-event
-time measured live in one instrumented step) and `cpu_baseline` (the CPU oracle timed on the
-host cores on BASELINE config 1, rank 0, N=1 only).
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, --dump-outputs, the JSON
+line.  Everything else it can measure runs only with --full, after the headline figure, and is reported next to it (the
+line's `roofline`, `cpu_baseline`, `vae_decode`, `other_configs`, `trajectory` and `cond_assembly` are null without it):
 
-Outside `value`, so that the driver-run record also carries BASELINE.json's other configurations:
-`other_configs` (N = 1: config 2 = T=8, config 3 = T=24 as one window, config 5 = fp8 at T=21, config 4 = the 168-view
-two-pass trajectory on this one GPU with a few sampler steps per window) and, for N > 1, `trajectory`: the SAME 168-view
-trajectory run across the N ranks with CFG-split (STRONG scaling: total work fixed; seva/pipeline.py) -- the number that
-says something about config 4, which one-window-per-rank weak scaling does not.
+`roofline` (dominant kernel class, algorithmic FLOP / HIP-event time measured live in one instrumented step),
+`cpu_baseline` (the CPU oracle timed on the host cores on BASELINE config 1, rank 0, N=1 only), `vae_decode` (VAE decode /
+encode and the CLIP conditioner), `cond_assembly` (the once-per-window conditioning assembly, median of 3) and, so that
+the driver-run record also carries BASELINE.json's other configurations, `other_configs` (N = 1: config 2 = T=8, config
+3 = T=24 as one window, config 5 = fp8 at T=21, config 4 = the 168-view two-pass trajectory on this one GPU with a few
+sampler steps per window) and, for N > 1, `trajectory`: the SAME 168-view trajectory run across the N ranks with
+CFG-split (STRONG scaling: total work fixed; seva/pipeline.py) -- the number that says something about config 4, which
+one-window-per-rank weak scaling does not.
 """
 
 from __future__ import annotations
@@ -32,6 +35,7 @@ import os
 import sys
 import threading
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "stable-virtual-camera_amd"))
@@ -59,32 +63,44 @@ def build_model(device, shapes_only=False):
         net = Seva(SevaParams())
     shapes = {k: tuple(v.shape) for k, v in net.state_dict().items()}
     t0 = time.time()
-    sd = synth.synth_state_dict(shapes, 0)
-    log(f"[bench] synthetic 1.3B weights generated on CPU in {time.time() - t0:.1f}s")
+    # synth.synth_state_dict(shapes, 0), drawn tensor by tensor on a thread pool: every tensor has a generator seeded by its
+    # own name, so the values do not depend on the order or the thread that draws them.  The CPU draw is single-threaded
+    # per tensor and dominates the set-up; each worker runs its ops on one thread (no nested intra-op pools).
+    intra = torch.get_num_threads()
+    workers = max(1, min(intra, 16))
+    torch.set_num_threads(1)
+    try:
+        with ThreadPoolExecutor(workers) as ex:
+            sd = dict(zip(shapes, ex.map(lambda kv: synth.synth_tensor(kv[0], kv[1], 0), shapes.items())))
+    finally:
+        torch.set_num_threads(intra)
+    log(f"[bench] synthetic 1.3B weights generated on CPU in {time.time() - t0:.1f}s ({workers} threads)")
     net.load_state_dict(sd, strict=True, assign=True)
     return net, sd
 
 
-def make_sampler(net, device, T, hw, steps, seed):
+def make_sampler(net, device, T, hw, steps, seed, time_cond=True):
     from seva import sampling as S
     from seva import synthetic as synth
     from seva.model import SGMWrapper
 
     sc = synth.synth_scene(T, (hw, hw), (0,), seed=seed)
     # step-invariant inputs assembled on the GPU: camera normalisation on the host, Pluecker maps
-    # and the cond / uc channel assembly by HIP kernels; replaces the CPU-built dictionaries of synth_scene
+    # and the cond / uc channel assembly by HIP kernels; replaces the CPU-built dictionaries of synth_scene.
+    # time_cond: time the assembly (cond_assembly_ms); otherwise it runs once (it is deterministic: same inputs either way)
     from seva import conditioning as Cn
-    Cn.get_value_dict((hw * 8, hw * 8), [0], sc["c2w"][:, :3], sc["K"], sc["c2w"], 2.0, device=device)  # warm-up
-    torch.cuda.synchronize()
+    if time_cond:
+        Cn.get_value_dict((hw * 8, hw * 8), [0], sc["c2w"][:, :3], sc["K"], sc["c2w"], 2.0, device=device)  # warm-up
+        torch.cuda.synchronize()
     times = []
-    for _ in range(3):  # median of three: the host part (camera normalisation, V + 1 tiny inverses) is noisy on a fresh box
+    for _ in range(3 if time_cond else 1):  # median of three: the host part (camera normalisation, V + 1 tiny inverses) is noisy on a fresh box
         t0 = time.perf_counter()
         vd = Cn.get_value_dict((hw * 8, hw * 8), [0], sc["c2w"][:, :3], sc["K"], sc["c2w"], 2.0, device=device)
         lat = sc["cond"]["replace"][sc["input_frame_mask"], :4]
         cond_d, uc_d = Cn.assemble_cond(lat, sc["cond"]["crossattn"][0, 0], sc["input_frame_mask"], vd["plucker_coordinate"])
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1e3)
-    make_sampler.cond_assembly_ms = sorted(times)[1]
+    make_sampler.cond_assembly_ms = sorted(times)[1] if time_cond else None
     sc["cond"], sc["uc"], sc["c2w"] = cond_d, uc_d, vd["c2w"]
     disc = S.DDPMDiscretization()
     den = S.DiscreteDenoiser(disc, num_idx=1000, device=device)
@@ -256,14 +272,17 @@ def main():
     ap.add_argument("--precision", choices=["f16", "fp8"], default="f16",
                     help="f16 = parity mode (default, the headline line); fp8 = BASELINE config 5: e4m3 weights + activations "
                          "on the block-scaled fp8 MFMA for the C >= 640 levels (separate accuracy class)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-vae", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure what a plain run leaves out: `roofline`, `vae_decode`, "
+                         "`cond_assembly`, `other_configs` / `trajectory` and `cpu_baseline` (each can be skipped below)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the `cpu_baseline` leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the `roofline` step")
+    ap.add_argument("--no-vae", action="store_true", help="--full without the `vae_decode` leg")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the `other_configs` legs (N = 1) / the strong-scaling `trajectory` leg (N > 1)")
+                    help="--full without the `other_configs` legs (N = 1) / the strong-scaling `trajectory` leg (N > 1)")
     ap.add_argument("--other-steps", type=int, default=5, help="timed steps of each `other_configs` steps/s leg")
     ap.add_argument("--leg-traj-steps", type=int, default=4,
-                    help="sampler steps per window of the 168-view trajectory legs on the default line")
+                    help="sampler steps per window of the 168-view trajectory legs of --full")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the sampler state the last timed step returned (what a caller of "
                          "sampler_step receives: T x 4 x latent x latent) as DIR/latents.npy, float32, rank 0; inputs and the "
@@ -304,7 +323,7 @@ def main():
     total_steps = K + Wm
     # the DDPM schedule holds at most 1000 sigmas: longer runs cycle through it, so --steps is always the number of timed steps
     n_sched = min(max(total_steps, 2), 1000)
-    sampler, denoise, noise, cond, uc, gk = make_sampler(net, device, T, hw, n_sched, 23 + rank)
+    sampler, denoise, noise, cond, uc, gk = make_sampler(net, device, T, hw, n_sched, 23 + rank, args.full)
     cond_assembly_ms = getattr(make_sampler, "cond_assembly_ms", None)  # (of the headline window; later legs overwrite the attribute)
 
     # anchors shared by adjacent windows (first-pass output; here: this rank's input-view latent)
@@ -353,7 +372,7 @@ def main():
     elapsed = float(tmax.item())
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         eng = net.engine()
         # events bracket individual launches: this one instrumented step runs eagerly (no step graph, no network graph)
         was_graph, eng.use_graph = eng.use_graph, False
@@ -396,7 +415,7 @@ def main():
         }
 
     vae = None
-    if rank == 0 and not args.no_vae:
+    if args.full and rank == 0 and not args.no_vae:
         try:
             # VAE decode of finished latents (reference autoencoder.py:40-48, chunk_size=1), outside `value`
             from seva.modules.autoencoder import AutoEncoder
@@ -466,8 +485,9 @@ def main():
                    "model_tflops": (flop * value / 1e12) if flop else None},
         "roofline": roofline, "cpu_baseline": None, "vae_decode": vae,
         "other_configs": None, "trajectory": None,
-        "cond_assembly": {"ms": cond_assembly_ms,
-                          "what": "camera normalisation (host) + Pluecker maps + cond/uc assembly (HIP), once per window, outside `value`; median of 3"},
+        "cond_assembly": None if cond_assembly_ms is None else {
+            "ms": cond_assembly_ms,
+            "what": "camera normalisation (host) + Pluecker maps + cond/uc assembly (HIP), once per window, outside `value`; median of 3"},
     }
     print_lock = threading.Lock()
     state = {"printed": False, "leg": "none"}
@@ -511,7 +531,7 @@ def main():
 
     # whatever happens below -- an exception outside a leg included -- the headline line is printed
     try:
-        if not args.no_other_configs and (T, hw) == (21, 72) and args.precision == "f16":
+        if args.full and not args.no_other_configs and (T, hw) == (21, 72) and args.precision == "f16":
             if world == 1:
                 # BASELINE configs 2, 3, 5 and (on this one GPU) 4 -- outside `value`
                 other = {"config2_T8": leg("config2_T8", steps_leg, net, device, 8, hw, args.other_steps),
@@ -523,7 +543,7 @@ def main():
             else:
                 out["trajectory"] = leg("trajectory", trajectory_leg, net, device, rank, world, 168, hw, T, args.leg_traj_steps, True)
 
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = leg("cpu_baseline", cpu_baseline, sd)
         state["leg"] = "none"
     except BaseException as e:  # noqa: BLE001
