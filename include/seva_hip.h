@@ -81,15 +81,18 @@ typedef struct seva_gemm_desc {
   int32_t pad_br_only;
   /* seva_gemm_fp8 only (NULL / 0 for seva_gemm_f16): */
   const void* w_exp;     /* uint8 [N]: E8M0 scale byte 127 + e[n]; weight row n holds e4m3(w[n] * 2^-e[n]) */
-  void* out_f8;          /* GEGLU epilogue: e4m3 [M][ldo8] (saturating), the next fp8 GEMM's A operand; or NULL */
+  void* out_f8;          /* GEGLU epilogue: e4m3 [M][ldo8] (saturating), the next fp8 GEMM's A operand; or NULL.  ABI 10: also the
+                          * plain epilogue of a 3x3 convolution of seva_gemm_fp8 (window kernel only): the fp32 result (bias, residual,
+                          * row_add) as saturating RNE e4m3, alone or beside out_f32 / out_f16, e.g. the A operand of the next fp8 conv.
+                          * ldo8 and the pointer must be multiples of 8.  Not together with `upsample` (an ERROR). */
   int64_t ldo8;
   /* optional (NULL = off): GroupNorm statistics of out_f32, emitted by the epilogue while the values are in registers,
    * so that the GroupNorm consuming this tensor (seva_groupnorm_desc.stats1 / stats2) needs no statistics pass over it.
    * float [ceil(M / 64)][2][N]: for every block of 64 output rows and every output channel, the sum ([..][0][n]) and the
    * sum of squares ([..][1][n]) of the fp32 values stored (after bias / row_add / residual); rows >= M contribute
    * nothing.  A block is 64 consecutive rows aligned to multiples of 64 rows of the whole tensor, EXCEPT for 3x3
-   * convolutions over images at least 144 pixels wide with N % 160 != 0 (the 2-D tiles of the window-staged kernel, round
-   * 4), where the blocks [i * hw / 64, (i + 1) * hw / 64) partition the pixels of image i in tile order: consumers must
+   * convolutions over images at least 144 pixels wide with N % 160 != 0, or any such e4m3 convolution (ABI 10) (the 2-D tiles of
+   * the window-staged kernel, round 4), where the blocks [i * hw / 64, (i + 1) * hw / 64) partition the pixels of image i in tile order: consumers must
    * only rely on the blocks of an image adding up to that image (seva_groupnorm does).  Per channel, so any grouping or
    * channel concatenation can be formed by the consumer.  Plain epilogue with out_f32 and N >= 128 only; forces 128-row tiles. */
   float* ch_stats;
@@ -121,7 +124,10 @@ int seva_gemm_f16(const seva_gemm_desc* d, seva_stream_t stream);
  * bytes or an NHWC e4m3 image, w: [N][K] bytes) on v_mfma_scale_f32_16x16x128_f8f6f4 with fp32 accumulation; the
  * per-output-channel power-of-two weight scale enters as the MFMA's E8M0 block scale, so the accumulator holds the
  * de-quantised product and bias / row_add / residual / GEGLU / col_scale behave exactly as in seva_gemm_f16.
- * K % 128 == 0 (conv: cin % 128 == 0), N % 16 == 0, no fused upsample.  The reference keeps bf16 weights
+ * K % 128 == 0 (conv: cin % 128 == 0), N % 16 == 0.  A 3x3 conv with the fused nearest-2x upsample or with out_f8 (ABI 10; the
+ * VAE decoder's fp8 mode) runs on the window-staged kernel only: stride 1, pad 1, N % 128 == 0, linear tiles where the image's
+ * window fits, 2-D tiles of 16 output columns (ow % 16 == 0, oh % 8 == 0) otherwise; where that kernel declines (or the conv_win
+ * knob is 0) the call is an ERROR, not a fall-back to the per-tap gather, which has neither.  The reference keeps bf16 weights
  * (seva/utils.py:50-53): this is a separate precision mode, reported separately from the f16 parity mode. */
 int seva_gemm_fp8(const seva_gemm_desc* d, seva_stream_t stream);
 

@@ -58,10 +58,12 @@ struct ConvWinGeom {
 // FP8 (BASELINE config 5; gemm.hip's e4m3 scheme): a 128-byte window / weight row is 128 e4m3 channels instead of 64 f16 ones (cin, K and the
 // pointers count 2-byte units, so every address here is unchanged); the two 16-byte fragment reads of a (tap, slab) form ONE 32-byte operand of
 // v_mfma_scale_f32_16x16x128_f8f6f4, the per-output-channel power-of-two weight scale rides as the E8M0 block scale of the weight operand.
-template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false>
+// The VAE decoder's fp8 mode adds e4m3 instantiations with 2-D tiles and with UP (both byte-agnostic above), and O8: the e4m3 output epilogue.
+template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false>
 __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWinGeom g) {
   constexpr bool T2D = TW > 0;
   static_assert(TW == 0 || TW == 16, "2-D tiles are 16 output columns wide: an MFMA block is a tile row");
+  static_assert(!O8 || FP8, "the e4m3 output epilogue belongs to the e4m3 instantiations");
   constexpr int TH = BM / 16;                                  // output rows of a 2-D tile
   constexpr int SW2 = UP ? 8 : 16, SH2 = UP ? TH / 2 : TH;     // its source extent; window = (SH2 + 2) x (SW2 + 2) pixels
   constexpr int PITCH2 = SW2 + 2, WL2 = (SH2 + 2) * PITCH2;
@@ -402,6 +404,24 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
         *(half4_t*)(p.out_f16 + m * p.ldo16 + f) = h;
       }
     }
+    if constexpr (O8) {
+      // e4m3 output (saturating, RNE; gemm.hip's GEGLU out_f8): a lane holds 4 features of block j, its partner lane ^ 16 the next 4.  One
+      // swizzle per pair of blocks hands each lane the partner's quad, so that every lane stores 8 consecutive features in one 8-byte store:
+      // even fg lanes of block j, odd fg lanes of block j + 1
+      static_assert(NJ % 2 == 0, "out_f8: blocks in pairs");
+      if (p.out_f8) {
+        typedef int v2i_t __attribute__((ext_vector_type(2)));
+        const bool odd = (fg & 1) != 0;
+#pragma unroll
+        for (int j = 0; j < NJ; j += 2) {
+          const int q0 = pack_fp8x4(v[j][0], v[j][1], v[j][2], v[j][3]);
+          const int q1 = pack_fp8x4(v[j + 1][0], v[j + 1][1], v[j + 1][2], v[j + 1][3]);
+          const int got = __builtin_amdgcn_ds_swizzle(odd ? q0 : q1, 0x401F);  // bit-mask mode: and 0x1f, xor 0x10 -> lane ^ 16
+          const int64_t f = n0 + wn * WN + 16 * (odd ? j + 1 : j) + 4 * (fg & 2);
+          if (row_ok && f + 8 <= p.N) *(v2i_t*)(p.out_f8 + m * p.ldo8 + f) = odd ? v2i_t{got, q1} : v2i_t{q0, got};
+        }
+      }
+    }
   }
   if constexpr (STATS) {
     if (p.ch_stats != nullptr) {  // per 64-row block and channel: sum and sum of squares (gemm.hip, same association)
@@ -435,7 +455,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
 
 uint32_t magic_u32(uint32_t d) { return (uint32_t)(0x100000000ull / d) + 1u; }
 
-template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false>
+template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false>
 int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
   constexpr int lds = (DBW ? 2 : 1) * WCAP * 128 + 2 * BN * 128;
   static_assert(lds <= 160 * 1024, "LDS per workgroup");
@@ -444,7 +464,7 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
   (void)hipGetDevice(&dev);
   const uint64_t dev_bit = 1ull << (dev & 63);
   if (!(attr_devs.load(std::memory_order_relaxed) & dev_bit)) {
-    (void)hipFuncSetAttribute((const void*)conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_devs.fetch_or(dev_bit, std::memory_order_relaxed);
   }
   ConvWinGeom g = g0;
@@ -455,7 +475,7 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
       seva_set_error("conv_win: bad grid %lld", (long long)nb);
       return SEVA_ERR_ARG;
     }
-    hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8>), dim3((unsigned)nb), dim3(64 * NW), lds, s, c, gc);
+    hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8>), dim3((unsigned)nb), dim3(64 * NW), lds, s, c, gc);
     return seva_check_launch("conv_win_kernel");
   };
   if constexpr (TW > 0) {
@@ -505,6 +525,7 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
     if (c.residual) c.residual += r0 * a.ldr;
     if (c.out_f32) c.out_f32 += r0 * a.ldo32;
     if (c.out_f16) c.out_f16 += r0 * a.ldo16;
+    if (c.out_f8) c.out_f8 += r0 * a.ldo8;
     if (c.row_add) c.row_add += (r0 / a.rows_per_group) * a.ldra;
     if (c.ch_stats) c.ch_stats += (r0 / 64) * 2 * a.N;
     ConvWinGeom gc = g;
@@ -577,9 +598,23 @@ int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
     // MFMA no longer fit beside 100 accumulators: 2 KB of scratch; gemm.hip's e4m3 kernels found the same); cin counts 2-byte units
     if (a.N % 128 != 0 || a.w_exp == nullptr) return 1;
     const bool eight = knob == 2;  // two 4-wave workgroups per CU are faster on every e4m3 shape of a step (profiles/r04_kconvwin_fp8.log)
-    if (a.upsample) return 1;  // (the engine keeps the three upsample convs in f16)
-    int rc = eight ? launch_win<256, 128, 8, 416, true, true, false, 0, true>(a, g, s) : launch_win<128, 128, 4, 288, false, true, false, 0, true>(a, g, s);
+    // The VAE decoder's fp8 mode (128 / 256 / 512 channels, 72 .. 576 px rows) follows the f16 128-column family: linear tiles where the
+    // window fits, else 2-D tiles of 16 output columns.  Fused nearest-2x upsample and the e4m3 output epilogue (out_f8: the resnet that
+    // feeds an upsample conv writes its A operand) are instantiations of their own; the plain family keeps its linear chain unchanged.
+    int rc;
+    if (a.upsample) {
+      rc = eight ? launch_win<256, 128, 8, 416, true, true, true, 0, true>(a, g, s) : launch_win<128, 128, 4, 288, false, true, true, 0, true>(a, g, s);
+      if (rc == 1) rc = eight ? launch_win<256, 128, 8, 104, true, true, true, 16, true>(a, g, s) : launch_win<128, 128, 4, 64, false, true, true, 16, true>(a, g, s);
+      return rc;
+    }
+    if (a.out_f8) {
+      rc = eight ? launch_win<256, 128, 8, 416, true, true, false, 0, true, true>(a, g, s) : launch_win<128, 128, 4, 288, false, true, false, 0, true, true>(a, g, s);
+      if (rc == 1) rc = eight ? launch_win<256, 128, 8, 328, true, true, false, 16, true, true>(a, g, s) : launch_win<128, 128, 4, 184, false, true, false, 16, true, true>(a, g, s);
+      return rc;
+    }
+    rc = eight ? launch_win<256, 128, 8, 416, true, true, false, 0, true>(a, g, s) : launch_win<128, 128, 4, 288, false, true, false, 0, true>(a, g, s);
     if (rc == 1) rc = eight ? launch_win<128, 128, 4, 288, false, true, false, 0, true>(a, g, s) : launch_win<256, 128, 8, 416, true, true, false, 0, true>(a, g, s);
+    if (rc == 1) rc = eight ? launch_win<256, 128, 8, 328, true, true, false, 16, true>(a, g, s) : launch_win<128, 128, 4, 184, false, true, false, 16, true>(a, g, s);
     return rc;
   }
   if (narrow) {

@@ -918,9 +918,9 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
   if (FP8) {
     SEVA_REQUIRE(d->w_exp != nullptr, "gemm fp8: w_exp (per-channel E8M0 scale bytes) is required");
     SEVA_REQUIRE(d->N % 16 == 0 && d->N > 32, "gemm fp8: N=%lld must be a multiple of 16 and > 32", (long long)d->N);
-    SEVA_REQUIRE(!d->upsample, "gemm fp8: the fused-upsample conv stays on the f16 kernel");
-    SEVA_REQUIRE(!d->out_f8 || (d->epilogue == 1 && d->ldo8 % 8 == 0 && (uintptr_t)d->out_f8 % 8 == 0),
-                 "gemm fp8: out_f8 is the GEGLU epilogue's output (row pitch and pointer multiples of 8)");
+    SEVA_REQUIRE(!d->out_f8 || ((d->epilogue == 1 || d->mode == 1) && d->ldo8 % 8 == 0 && (uintptr_t)d->out_f8 % 8 == 0),
+                 "gemm fp8: out_f8 is the output of the GEGLU epilogue or of a 3x3 convolution (row pitch and pointer multiples of 8)");
+    SEVA_REQUIRE(!(d->upsample && d->out_f8), "gemm fp8: out_f8 and the fused upsample are not available together (no such instantiation)");
   } else {
     SEVA_REQUIRE(!d->out_f8 && !d->w_exp, "gemm f16: out_f8 / w_exp belong to seva_gemm_fp8");
   }
@@ -1022,6 +1022,10 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
       const int rc = seva_conv_win_launch(a, s, true);
       if (rc <= 0) return rc;
     }
+    // the per-tap gather below has neither the fused upsample nor the e4m3 output in conv mode: only the window kernel runs those
+    SEVA_REQUIRE(!(d->mode == 1 && (d->upsample || d->out_f8)),
+                 "gemm fp8: a conv with %s runs on the window kernel only, which declined it (3x3 / stride 1 / pad 1, N %% 128 == 0, "
+                 "image tiles must fit its window; conv_win knob not 0)", d->upsample ? "the fused upsample" : "out_f8");
     if (half_m8) return wide8 ? launch<64, 160, 1, 0, true>(a, s) : launch<64, 128, 1, 0, true>(a, s);
     return launch<128, 128, 1, 0, true>(a, s);
   } else {

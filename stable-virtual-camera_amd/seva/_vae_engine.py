@@ -4,9 +4,14 @@ fp32 stream, fp16 GEMM operands, 3x3 convs as implicit GEMM with the nearest-2x 
 into the gather.  The single-head d=512 mid-block attention runs as GEMM(QK^T) -> row softmax ->
 GEMM(P V^T) with V produced already transposed by swapping the GEMM operand roles; the value
 bias is added after P*V (rows of P sum to 1, exact).
+
+The decoder has an opt-in fp8 precision (`AutoEncoder.set_precision("fp8")`, or SEVA_VAE_PRECISION=fp8 when that was not
+called): see `fp8_decoder_convs`.  Encode is always f16.
 """
 
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -15,6 +20,72 @@ from ._engine import CIN_PAD, _Arena, pack_conv3x3
 from ._native import SevaNativeError, require_cuda
 
 F16, F32 = torch.float16, torch.float32
+U8 = torch.uint8  # e4m3 bytes (ops.py)
+VAE_PRECISIONS = ("f16", "fp8")
+
+
+def check_vae_precision(precision: str) -> str:
+    if precision not in VAE_PRECISIONS:
+        raise ValueError(f"unknown VAE precision {precision!r} (f16 | fp8)")
+    return precision
+
+
+def vae_precision_from_env() -> str:
+    """SEVA_VAE_PRECISION=f16|fp8 (unset: f16); used only where `AutoEncoder.set_precision` was not called."""
+    return check_vae_precision(os.environ.get("SEVA_VAE_PRECISION") or "f16")
+
+
+def fp8_upsample_from_env() -> bool:
+    """SEVA_VAE_FP8_UPSAMPLE=1: the fp8 decode also runs the three upsample convs in e4m3 (off by default, see fp8_decoder_convs)."""
+    return os.environ.get("SEVA_VAE_FP8_UPSAMPLE", "0") == "1"
+
+
+def fp8_decoder_convs(block_out, upsample: bool = False) -> list[str]:
+    """Decoder convs that the fp8 decode runs on e4m3 operands (e4m3 weights with a per-output-channel power-of-two E8M0
+    scale, e4m3 activations, fp32 accumulation): every 3x3 conv inside a resnet with cin % 128 == 0 and cout % 128 == 0, i.e.
+    both convs of the mid-block resnets and conv1 / conv2 of the up-block resnets.  These stay f16:
+      * post_quant_conv (1x1, 4 channels) and decoder.conv_in (4 input channels), decoder.conv_out (3 output channels);
+      * the mid-block attention GEMMs;
+      * conv2 of the channel-changing resnets (512 -> 256, 256 -> 128): the 1x1 shortcut folded into it (seva_gemm_desc.a2)
+        is f16-only;
+      * the three upsample convs, unless `upsample` (SEVA_VAE_FP8_UPSAMPLE=1).  Their A operand is the residual stream itself,
+        not a normalised resnet branch: in e4m3 its rounding goes straight into every later layer, and the decode's rel-L2 to
+        f16 grows about threefold.  With `upsample`, the last resnet of an up
+        block writes `conv + residual` as e4m3 straight into the upsample conv's A operand (the e4m3 twin of `f16_out`);
+        without, its e4m3 conv2 writes that f16 operand.
+    The GroupNorm + SiLU in front of an e4m3 conv writes e4m3."""
+    def ok(ci, co):
+        return ci % 128 == 0 and co % 128 == 0
+
+    top = block_out[-1]
+    names = []
+    for r in range(2):
+        if ok(top, top):
+            names += [f"decoder.mid_block.resnets.{r}.conv1", f"decoder.mid_block.resnets.{r}.conv2"]
+    rev = list(reversed(block_out))
+    cin = rev[0]
+    for i, cout in enumerate(rev):
+        for j in range(3):
+            ci = cin if j == 0 else cout
+            p = f"decoder.up_blocks.{i}.resnets.{j}"
+            if ok(ci, cout):
+                names.append(p + ".conv1")
+            if ci == cout and ok(cout, cout):
+                names.append(p + ".conv2")
+        cin = cout
+        if upsample and i != len(rev) - 1 and ok(cout, cout):
+            names.append(f"decoder.up_blocks.{i}.upsamplers.0.conv")
+    return names
+
+
+def pack_fp8_convs(sd: dict, block_out, upsample: bool = False) -> dict:
+    """{prefix + ".w8": e4m3 bytes [cout, 9 * cin] (K ordered (ky, kx, ci), the UNet's fp8 conv layout), prefix + ".w8e":
+    E8M0 scale bytes [cout]} for `fp8_decoder_convs`, quantised from the fp32 weights by `ops.quantize_weight_fp8`."""
+    W8 = {}
+    for p in fp8_decoder_convs(block_out, upsample):
+        w = sd[p + ".weight"].float()
+        W8[p + ".w8"], W8[p + ".w8e"] = ops.quantize_weight_fp8(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1))
+    return W8
 
 
 class _VaeEngineBase:
@@ -30,6 +101,8 @@ class _VaeEngineBase:
 
         _native.load()
         return params[0].device
+
+    _w8: dict = {}  # e4m3 conv weights of the running decode (fp8 precision), else empty
 
     def __init__(self, weights):
         self.device = self._resolve_device(weights)
@@ -108,22 +181,47 @@ class _VaeEngineBase:
         else:
             self._stats[out.data_ptr()] = st
 
-    def _resnet(self, p, x, n, h, w, cin, cout, f16_out=None):
+    def _resnet(self, p, x, n, h, w, cin, cout, f16_out=None, f8_out=None):
         """diffusers ResnetBlock2D (no time embedding): GN-SiLU-conv-GN-SiLU-conv + shortcut.
         f16_out: the block's only consumer is a resampling conv (A operand = f16): the second conv's epilogue rounds
         `conv + shortcut` straight into that buffer -- the same rounding the separate cast pass made -- and the fp32 tensor
         (4 B written, 4 B read back per element at up to 576 x 576 x 256) is never formed.  The shortcut conv's f16 input comes
-        out of the first GroupNorm's pass over x (`raw_f16`) instead of a cast pass of its own."""
-        W, hw = self.W, h * w
-        a16 = self._buf("gn16", (n, hw, cin), F16)
+        out of the first GroupNorm's pass over x (`raw_f16`) instead of a cast pass of its own.
+        fp8 decode: a conv with e4m3 weights in `self._w8` reads the e4m3 output of its GroupNorm; f8_out is f16_out's e4m3
+        twin (the upsample conv's A operand, written by the e4m3 conv2's epilogue, saturating)."""
+        W, W8, hw = self.W, self._w8, h * w
+        f8_1, f8_2 = p + ".conv1.w8" in W8, p + ".conv2.w8" in W8
+        assert f8_out is None or f8_2
+        a16 = None if f8_1 else self._buf("gn16", (n, hw, cin), F16)
+        a8 = self._buf("gn8", (n, hw, cin), U8) if f8_1 else None
         xs16 = self._buf("v_sk16", (n * hw, cin), F16) if cin != cout else None
         ops.groupnorm(x, None, W[p + ".norm1.g"], W[p + ".norm1.b"], a16, self.gn_ws, eps=1e-6, silu=True,
-                      stats1=self._stats.get(x.data_ptr()), raw_f16=None if xs16 is None else xs16.view(n, hw, cin))
+                      stats1=self._stats.get(x.data_ptr()), raw_f16=None if xs16 is None else xs16.view(n, hw, cin), out_f8=a8)
         mid = self._buf("v_mid", (n, hw, cout), F32)
         st_mid = self._stats_buf("v_mid", n * hw, hw, cout)
-        ops.conv3x3(a16.view(n, h, w, cin), W[p + ".conv1.w"], bias=W[p + ".conv1.b"], out_f32=mid, ch_stats=st_mid)
-        b16 = self._buf("gn16", (n, hw, cout), F16)
-        ops.groupnorm(mid, None, W[p + ".norm2.g"], W[p + ".norm2.b"], b16, self.gn_ws, eps=1e-6, silu=True, stats1=st_mid)
+        if f8_1:
+            ops.conv3x3(a8.view(n, h, w, cin), W8[p + ".conv1.w8"], w_exp=W8[p + ".conv1.w8e"], bias=W[p + ".conv1.b"], out_f32=mid,
+                        ch_stats=st_mid)
+        else:
+            ops.conv3x3(a16.view(n, h, w, cin), W[p + ".conv1.w"], bias=W[p + ".conv1.b"], out_f32=mid, ch_stats=st_mid)
+        b16 = None if f8_2 else self._buf("gn16", (n, hw, cout), F16)
+        b8 = self._buf("gn8", (n, hw, cout), U8) if f8_2 else None
+        ops.groupnorm(mid, None, W[p + ".norm2.g"], W[p + ".norm2.b"], b16, self.gn_ws, eps=1e-6, silu=True, stats1=st_mid,
+                      out_f8=b8)
+        if f8_2:  # (never a channel-changing resnet: its folded shortcut is f16-only)
+            assert cin == cout
+            w8, e8 = W8[p + ".conv2.w8"], W8[p + ".conv2.w8e"]
+            if f8_out is not None:
+                ops.conv3x3(b8.view(n, h, w, cout), w8, w_exp=e8, bias=W[p + ".conv2.b"], residual=x, out_f8=f8_out.view(n, hw, cout))
+                return f8_out
+            if f16_out is not None:
+                ops.conv3x3(b8.view(n, h, w, cout), w8, w_exp=e8, bias=W[p + ".conv2.b"], residual=x, out_f16=f16_out.view(n, hw, cout))
+                return f16_out
+            out = self._buf("out:" + p, (n, hw, cout), F32)
+            st_out = self._stats_buf("out:" + p, n * hw, hw, cout)
+            ops.conv3x3(b8.view(n, h, w, cout), w8, w_exp=e8, bias=W[p + ".conv2.b"], residual=x, out_f32=out, ch_stats=st_out)
+            self._produced(out, st_out)
+            return out
         w2, b2, res, a2 = W[p + ".conv2.w"], W[p + ".conv2.b"], x, None
         if cin != cout:
             if self.fold_shortcut and (p + ".conv2.wf") in W:
@@ -176,6 +274,20 @@ class VaeDecoderEngine(_VaeEngineBase):
     PREFIXES = ("decoder.", "post_quant_conv.")
     CONV_IN, CONV_OUT = "decoder.conv_in", "decoder.conv_out"
 
+    def __init__(self, weights, precision: str = "f16"):
+        super().__init__(weights)
+        self.precision = check_vae_precision(precision)  # decode precision; may be changed between decodes (AutoEncoder.set_precision)
+        self._src = weights
+        self.fp8_upsample = fp8_upsample_from_env()
+        self.W8 = None  # e4m3 conv weights, packed the first time an fp8 decode runs
+
+    def fp8_weights(self) -> dict:
+        if self.W8 is None:
+            sd = self._src.state_dict()
+            self.W8 = pack_fp8_convs({k: v.detach().to(self.device) for k, v in sd.items() if k.startswith("decoder.")},
+                                     self.block_out, self.fp8_upsample)
+        return self.W8
+
     def _pack_ends(self, sd, conv3):
         conv3("decoder.conv_out", cout_pad=4)
         # post_quant_conv (1x1, 4->4) as a GEMM over the 64-channel padded latent image
@@ -193,6 +305,7 @@ class VaeDecoderEngine(_VaeEngineBase):
             raise ValueError(f"expected {self.latent} latent channels, got {cz}")
         self.gn_ws = self._buf("gn_ws", (n * ops.GN_WORKSPACE_SLABS * 32 * 2,), F32)
         self._stats = {}
+        self._w8 = W8 = self.fp8_weights() if check_vae_precision(self.precision) == "fp8" else {}
         inv = torch.full((n,), 1.0 / scale_factor, dtype=F32, device=self.device)
         z16 = self._buf("v_z16", (n, h * w, CIN_PAD), F16)
         ops.nchw_to_nhwc_f16(z, None, z16, scale=inv)                      # z / 0.18215, channels-last, padded
@@ -210,17 +323,23 @@ class VaeDecoderEngine(_VaeEngineBase):
         cin = rev[0]
         for i, cout in enumerate(rev):
             up = i != len(rev) - 1
-            x16 = self._buf("v_up16", (n, h, w, cout), F16) if up else None
+            p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
+            # e4m3 upsample conv (SEVA_VAE_FP8_UPSAMPLE=1): its A operand is written by the e4m3 epilogue of the last resnet's conv2
+            up8 = up and p + ".w8" in W8 and f"decoder.up_blocks.{i}.resnets.2.conv2.w8" in W8
+            x16 = self._buf("v_up16", (n, h, w, cout), F16) if up and not up8 else None
+            x8 = self._buf("v_up8", (n, h, w, cout), U8) if up8 else None
             for j in range(3):
                 x = self._resnet(f"decoder.up_blocks.{i}.resnets.{j}", x, n, h, w, cin if j == 0 else cout, cout,
-                                 f16_out=x16 if j == 2 else None)
+                                 f16_out=x16 if j == 2 else None, f8_out=x8 if j == 2 else None)
             cin = cout
             if up:
-                p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
                 h, w = 2 * h, 2 * w
                 x = self._buf("out:" + p, (n, h * w, cout), F32)
                 st = self._stats_buf("out:" + p, n * h * w, h * w, cout)
-                ops.conv3x3(x16, W[p + ".w"], upsample=True, bias=W[p + ".b"], out_f32=x, ch_stats=st)
+                if up8:
+                    ops.conv3x3(x8, W8[p + ".w8"], w_exp=W8[p + ".w8e"], upsample=True, bias=W[p + ".b"], out_f32=x, ch_stats=st)
+                else:
+                    ops.conv3x3(x16, W[p + ".w"], upsample=True, bias=W[p + ".b"], out_f32=x, ch_stats=st)
                 self._produced(x, st)
         c = rev[-1]
         g16 = self._buf("gn16", (n, h * w, c), F16)

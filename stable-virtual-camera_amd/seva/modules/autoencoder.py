@@ -179,6 +179,31 @@ class AutoEncoder(nn.Module):
         self.chunk_size = chunk_size
         self._engine = None
         self._enc_engine = None
+        self._precision = None  # decode precision set by set_precision; None: SEVA_VAE_PRECISION, else "f16"
+
+    def set_precision(self, precision: str) -> "AutoEncoder":
+        """Decode precision: "f16" (the default) or "fp8" (the decoder's 3x3 convs with 128k channels on e4m3 weights and
+        activations, seva/_vae_engine.py:fp8_decoder_convs).  Decode only: encoded latents feed the denoiser's replace
+        channels, so encode stays f16.  Independent of `Seva.set_precision`.  Switching back to "f16" gives exactly the
+        default results; the e4m3 weights are packed the first time an fp8 decode runs."""
+        from .._vae_engine import check_vae_precision
+
+        self._precision = check_vae_precision(precision)
+        if self._engine is not None:
+            self._engine.precision = self._precision
+        return self
+
+    @property
+    def precision(self) -> str:
+        """The decode precision in effect: set_precision's value, else SEVA_VAE_PRECISION (read when the decoder engine is
+        built), else "f16"."""
+        if self._precision is not None:
+            return self._precision
+        if self._engine is not None:
+            return self._engine.precision
+        from .._vae_engine import vae_precision_from_env
+
+        return vae_precision_from_env()
 
     def _apply(self, fn, *a, **k):
         self._engine = self._enc_engine = None
@@ -199,7 +224,7 @@ class AutoEncoder(nn.Module):
         if self._engine is None:
             from .._vae_engine import VaeDecoderEngine
 
-            self._engine = VaeDecoderEngine(self.module)
+            self._engine = VaeDecoderEngine(self.module, precision=self.precision)
         return self._engine
 
     def _encode(self, x: torch.Tensor) -> torch.Tensor:

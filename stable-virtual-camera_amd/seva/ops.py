@@ -191,12 +191,15 @@ def conv3x3(
     splitk_ws: torch.Tensor | None = None,
     a2: torch.Tensor | None = None,
     alg_k: int = 0,
+    out_f8: torch.Tensor | None = None,
 ) -> None:
     """3x3 pad-1 conv as implicit GEMM; x: [n, ih, iw, cin] f16 NHWC, w: [cout, 9*cin] f16.
     a2 ([M, K2] f16, K2 % 64 == 0): a second operand folded into the reduction behind the nine taps, w: [cout, 9*cin + K2]
     (seva_gemm_desc.a2: the ResBlock's 1x1 skip conv inside its second 3x3 conv).
     pad_br_only: zero padding at the bottom / right edge only (diffusers Downsample2D, pad (0,1,0,1)).
-    fp8 mode (w_exp given): x and w are uint8 tensors of e4m3 bytes, cin % 128 == 0, no fused upsample."""
+    fp8 mode (w_exp given): x and w are uint8 tensors of e4m3 bytes, cin % 128 == 0.  The fused upsample and out_f8 (uint8
+    [.., cout] e4m3 bytes, saturating RNE of the fp32 result, alone or beside out_f32; pixel pitch and pointer multiples of 8; not
+    together with upsample) run on the window kernel only (stride 1, cout % 128 == 0): where it declines, the call raises instead of falling back."""
     require_cuda(x, w)
     fp8 = w_exp is not None
     assert x.dtype == w.dtype == (U8 if fp8 else F16) and x.dim() == 4 and x.is_contiguous()
@@ -232,8 +235,13 @@ def conv3x3(
     if fp8:
         assert w_exp.dtype == U8 and w_exp.numel() == w.shape[0]
         d.w_exp = w_exp.data_ptr()
+        if out_f8 is not None:
+            assert out_f8.dtype == U8 and out_f8.stride(-1) == 1 and out_f8.shape[-1] >= w.shape[0]
+            assert not upsample, "out_f8 and the fused upsample are not available together"
+            d.out_f8, d.ldo8 = out_f8.data_ptr(), out_f8.stride(-2)
         check(_lib().seva_gemm_fp8(C.byref(d), stream_ptr(x.device)), "seva_gemm_fp8(conv)")
     else:
+        assert out_f8 is None, "out_f8 belongs to the fp8 conv (w_exp)"
         check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), "seva_gemm_f16(conv)")
 
 
