@@ -91,8 +91,8 @@ typedef struct seva_gemm_desc {
    * float [ceil(M / 64)][2][N]: for every block of 64 output rows and every output channel, the sum ([..][0][n]) and the
    * sum of squares ([..][1][n]) of the fp32 values stored (after bias / row_add / residual); rows >= M contribute
    * nothing.  A block is 64 consecutive rows aligned to multiples of 64 rows of the whole tensor, EXCEPT for 3x3
-   * convolutions over images at least 144 pixels wide with N % 160 != 0, or any such e4m3 convolution (ABI 10) (the 2-D tiles of
-   * the window-staged kernel, round 4), where the blocks [i * hw / 64, (i + 1) * hw / 64) partition the pixels of image i in tile order: consumers must
+   * convolutions over images at least 144 pixels wide with N % 160 != 0, or any such e4m3 convolution (ABI 10), or an e4m3 stride-2
+   * pad_br_only convolution whose image is too wide for its linear tiles (ABI 11) (the 2-D tiles of the window-staged kernel), where the blocks [i * hw / 64, (i + 1) * hw / 64) partition the pixels of image i in tile order: consumers must
    * only rely on the blocks of an image adding up to that image (seva_groupnorm does).  Per channel, so any grouping or
    * channel concatenation can be formed by the consumer.  Plain epilogue with out_f32 and N >= 128 only; forces 128-row tiles. */
   float* ch_stats;
@@ -127,7 +127,11 @@ int seva_gemm_f16(const seva_gemm_desc* d, seva_stream_t stream);
  * K % 128 == 0 (conv: cin % 128 == 0), N % 16 == 0.  A 3x3 conv with the fused nearest-2x upsample or with out_f8 (ABI 10; the
  * VAE decoder's fp8 mode) runs on the window-staged kernel only: stride 1, pad 1, N % 128 == 0, linear tiles where the image's
  * window fits, 2-D tiles of 16 output columns (ow % 16 == 0, oh % 8 == 0) otherwise; where that kernel declines (or the conv_win
- * knob is 0) the call is an ERROR, not a fall-back to the per-tap gather, which has neither.  The reference keeps bf16 weights
+ * knob is 0) the call is an ERROR, not a fall-back to the per-tap gather, which has neither.  ABI 11 (the VAE encoder's fp8 mode): the
+ * window-staged kernel has a 3x3 / stride 2 / pad_br_only family (N % 128 == 0; linear tiles where one image's window fits, 2-D tiles of
+ * 16 x 8 output pixels otherwise; no out_f8).  It measured slower than the per-tap gather on the encoder's shapes, so such a conv takes the
+ * gather by default; with the conv_win knob at 1 or 2 it runs on that family, and where the family declines the call is an ERROR.
+ * Stride-2 convs with symmetric padding (the UNet's) keep the gather.  The reference keeps bf16 weights
  * (seva/utils.py:50-53): this is a separate precision mode, reported separately from the f16 parity mode. */
 int seva_gemm_fp8(const seva_gemm_desc* d, seva_stream_t stream);
 

@@ -59,14 +59,26 @@ struct ConvWinGeom {
 // pointers count 2-byte units, so every address here is unchanged); the two 16-byte fragment reads of a (tap, slab) form ONE 32-byte operand of
 // v_mfma_scale_f32_16x16x128_f8f6f4, the per-output-channel power-of-two weight scale rides as the E8M0 block scale of the weight operand.
 // The VAE decoder's fp8 mode adds e4m3 instantiations with 2-D tiles and with UP (both byte-agnostic above), and O8: the e4m3 output epilogue.
-template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false>
+//
+// S2 (the VAE encoder's fp8 mode: diffusers Downsample2D, 3x3 / stride 2 / padding on the bottom and right only): output pixel (y, x) reads
+// source pixel (2y + ky, 2x + kx), never a negative one.  Stride-2 fragment rows would all sit on one parity of window pixels, i.e. on one
+// 128-byte half of the 256-byte bank row: 2-way bank conflicts on every read whatever the chunk key.  So the window is stored COLUMN-PARITY
+// SPLIT: even source columns first, odd ones behind them.  Fragment row i then reads slot base + i (consecutive slots, the stride-1 pattern and
+// its chunk key), and tap (ky, kx) is still one uniform slot shift, ky * RP + (kx & 1) * HALF + (kx >> 1).
+//   2-D tiles: a window of (2 TH + 1) source rows x 33 columns per 16 x TH output tile, each row stored as 17 even + 16 odd columns
+//              (RP = 33, HALF = 17);
+//   linear tiles: the padded index space with bottom / right frame cells only (P(m) = img * Sp + 2y Wp + 2x, Wp = iw + 1 rounded up to even so
+//              that parity of P is parity of the column), split over the tile's window: even indices in slots [0, HALF), odd ones behind
+//              (RP = Wp / 2, HALF = half the tile's window, a workgroup-uniform scalar).
+template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false, bool S2 = false>
 __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWinGeom g) {
   constexpr bool T2D = TW > 0;
   static_assert(TW == 0 || TW == 16, "2-D tiles are 16 output columns wide: an MFMA block is a tile row");
   static_assert(!O8 || FP8, "the e4m3 output epilogue belongs to the e4m3 instantiations");
+  static_assert(!S2 || (FP8 && !UP && !O8), "stride 2: e4m3, no upsample, no e4m3 output (the encoder's downsample convs)");
   constexpr int TH = BM / 16;                                  // output rows of a 2-D tile
   constexpr int SW2 = UP ? 8 : 16, SH2 = UP ? TH / 2 : TH;     // its source extent; window = (SH2 + 2) x (SW2 + 2) pixels
-  constexpr int PITCH2 = SW2 + 2, WL2 = (SH2 + 2) * PITCH2;
+  constexpr int PITCH2 = S2 ? 33 : SW2 + 2, WL2 = S2 ? (2 * TH + 1) * 33 : (SH2 + 2) * PITCH2;
   static_assert(!T2D || (WL2 <= WCAP && TH % 2 == 0), "2-D window capacity");
   constexpr int WMW = NW / 2, WNW = 2;
   constexpr int WM = BM / WMW, WN = BN / WNW;  // per-wave tile
@@ -126,20 +138,29 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
     const uint32_t rem = m - img * (uint32_t)g.hw;
     yo = __umulhi(rem, g.mul_iw);
     xo = rem - yo * (uint32_t)g.ow;
+    if constexpr (S2) return img * (uint32_t)g.Sp + 2u * yo * (uint32_t)g.Wp + 2u * xo;  // (S2: the source pixel under tap (0, 0))
     const uint32_t y = UP ? yo >> 1 : yo, x = UP ? xo >> 1 : xo;
     return img * (uint32_t)g.Sp + (y + 1) * (uint32_t)g.Wp + x + 1;
   };
   uint32_t q0 = 0;
-  int WL = WL2;
+  int WL = WL2, WS = WL2;  // window pixels; window slots (S2 linear: two halves of HALF slots)
+  int s2_half = 17;        // S2: slot of the first odd column (2-D) / odd padded index (linear)
   if constexpr (!T2D) {
     uint32_t y_a, x_a, y_b, x_b;
     const uint32_t P0 = pad_index(m0, y_a, x_a), P1 = pad_index(m_end - 1, y_b, x_b);
+    if constexpr (S2) {  // taps (ky, kx) of the tile's first .. last output pixel: [P0, P1 + 2 Wp + 2]; P0 and Wp are even
+      q0 = P0;
+      WL = (int)(P1 - P0) + 2 * g.Wp + 3;
+      s2_half = __builtin_amdgcn_readfirstlane((WL + 1) >> 1);
+      WS = 2 * s2_half;
+    } else {
     // window = [first source pixel any tap reads, last one]: plain conv: consecutive pixels, one halo of Wp + 1 on either side;
     // UP: output rows 2r and 2r + 1 read the same source row, so the window holds whole source rows (first row's start .. last row's end)
     q0 = (UP ? P0 - (x_a >> 1) : P0) - (uint32_t)(g.Wp + 1);   // padded index of window pixel 0
-    WL = (int)((UP ? P1 - (x_b >> 1) + (uint32_t)p.iw - 1 : P1) - q0) + g.Wp + 2;  // window pixels this tile reads (<= WCAP)
+    WL = WS = (int)((UP ? P1 - (x_b >> 1) + (uint32_t)p.iw - 1 : P1) - q0) + g.Wp + 2;  // window pixels this tile reads (<= WCAP)
+    }
   }
-  const int npc = __builtin_amdgcn_readfirstlane((WL + 7) >> 3);
+  const int npc = __builtin_amdgcn_readfirstlane((WS + 7) >> 3);
 
   // ---- window fill: lane (pixel 8 pc + sr, physical chunk sp) of piece pc fetches logical chunk sp ^ key(pixel) ----
   int woff[PPW];  // byte offset of the lane's 16 bytes in slab 0, or -1: frame pixel / past the batch -> zero page
@@ -150,11 +171,25 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
     const int chunk = sp ^ ((j >> 1) & 7);
     bool ok;
     uint32_t pix;
-    if constexpr (T2D) {  // window pixel j = (wy, wx) of the (SH2 + 2) x PITCH2 block around the tile's source pixels
+    if constexpr (T2D && S2) {  // slot j = (wy, r): source row 2 t_y0 + wy, column 2 t_x0 + (r < 17 ? 2 r : 2 (r - 17) + 1)
+      const int wy = j / 33, r = j - wy * 33;
+      const int sy = 2 * (int)t_y0 + wy, sx = 2 * (int)t_x0 + (r < 17 ? 2 * r : 2 * (r - 17) + 1);
+      ok = (j < WL2) & (sy < p.ih) & (sx < p.iw);  // the bottom row / right column past the image are the zero padding
+      pix = (uint32_t)sy * (uint32_t)p.iw + (uint32_t)sx;
+    } else if constexpr (T2D) {  // window pixel j = (wy, wx) of the (SH2 + 2) x PITCH2 block around the tile's source pixels
       const int wy = j / PITCH2, wx = j - wy * PITCH2;
       const int sy = (int)(UP ? t_y0 >> 1 : t_y0) - 1 + wy, sx = (int)(UP ? t_x0 >> 1 : t_x0) - 1 + wx;
       ok = (j < WL2) & (sy >= 0) & (sy < p.ih) & (sx >= 0) & (sx < p.iw);
       pix = (uint32_t)sy * (uint32_t)p.iw + (uint32_t)sx;  // inside the tile's image: its base is added as a 64-bit scalar (a_img)
+    } else if constexpr (S2) {  // slot j: padded index q0 + 2 j (j < HALF) or q0 + 2 (j - HALF) + 1; the frame is row ih / columns >= iw
+      const int jj = j < s2_half ? 2 * j : 2 * (j - s2_half) + 1;
+      const uint32_t q = q0 + (uint32_t)jj;
+      const uint32_t img = __umulhi(q, g.mul_sp);
+      const uint32_t rem = q - img * (uint32_t)g.Sp;
+      const uint32_t py = __umulhi(rem, g.mul_wp);
+      const uint32_t px = rem - py * (uint32_t)g.Wp;
+      ok = (img < (uint32_t)p.n) & (py < (uint32_t)p.ih) & (px < (uint32_t)p.iw) & (jj < WL);
+      pix = (img * (uint32_t)p.ih + py) * (uint32_t)p.iw + px;
     } else {
       const uint32_t q = q0 + (uint32_t)j;
       const uint32_t img = __umulhi(q, g.mul_sp);
@@ -212,7 +247,10 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
     int ctr, yp, xp;  // window pixel under the centre tap; (UP) row / column parity of the output pixel
-    if constexpr (T2D) {
+    if constexpr (T2D && S2) {
+      ctr = 2 * (wm * (WM / 16) + i) * 33 + fr;  // slot of tap (0, 0): source row 2 x tile row, even column 2 fr
+      yp = xp = 0;
+    } else if constexpr (T2D) {
       const int row = wm * (WM / 16) + i;  // tile row = MFMA block
       ctr = UP ? ((row >> 1) + 1) * PITCH2 + (fr >> 1) + 1 : (row + 1) * PITCH2 + fr + 1;
       yp = row & 1;  // the tile's origin is even in both directions
@@ -221,6 +259,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
       uint32_t m = row_m(i), yo, xo;
       if (m >= m_end) m = m_end - 1;
       ctr = (int)(pad_index(m, yo, xo) - q0);
+      if constexpr (S2) ctr >>= 1;  // even padded index -> its slot
       yp = (int)(yo & 1);
       xp = (int)(xo & 1);
     }
@@ -230,7 +269,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
       a_rp[i] = ctr + yp * pitch;
       a_xp[i] = xp;
     } else {
-      a_base[i] = ctr - pitch - 1;
+      a_base[i] = S2 ? ctr : ctr - pitch - 1;
     }
   }
 
@@ -297,7 +336,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
         if (more && t < PPW) fill_piece(t, s + 1, (s + 1) & 1);
       }
       const char* const tb = lds_b + cur * B_BYTES;
-      int toff = UP ? 0 : (t / 3) * pitch + (t % 3);
+      int toff = S2 ? (t / 3) * (T2D ? 33 : g.Wp >> 1) + ((t % 3) & 1) * s2_half + ((t % 3) >> 1) : UP ? 0 : (t / 3) * pitch + (t % 3);
       asm volatile("" : "+s"(toff));  // opaque: the nine taps' fragment addresses are formed here, not hoisted out of the slab loop (45 registers)
       // fragment reads + MFMAs of the tap.  FIRST: every fragment read is ISSUED before the first MFMA (hipcc otherwise re-uses one
       // register quad for the second k-step's window fragments and waits for each read right in front of the five MFMAs that need it:
@@ -455,7 +494,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
 
 uint32_t magic_u32(uint32_t d) { return (uint32_t)(0x100000000ull / d) + 1u; }
 
-template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false>
+template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false, bool S2 = false>
 int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
   constexpr int lds = (DBW ? 2 : 1) * WCAP * 128 + 2 * BN * 128;
   static_assert(lds <= 160 * 1024, "LDS per workgroup");
@@ -464,7 +503,7 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
   (void)hipGetDevice(&dev);
   const uint64_t dev_bit = 1ull << (dev & 63);
   if (!(attr_devs.load(std::memory_order_relaxed) & dev_bit)) {
-    (void)hipFuncSetAttribute((const void*)conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_devs.fetch_or(dev_bit, std::memory_order_relaxed);
   }
   ConvWinGeom g = g0;
@@ -475,7 +514,7 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
       seva_set_error("conv_win: bad grid %lld", (long long)nb);
       return SEVA_ERR_ARG;
     }
-    hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8>), dim3((unsigned)nb), dim3(64 * NW), lds, s, c, gc);
+    hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2>), dim3((unsigned)nb), dim3(64 * NW), lds, s, c, gc);
     return seva_check_launch("conv_win_kernel");
   };
   if constexpr (TW > 0) {
@@ -490,14 +529,16 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
   // the instantiation's capacity.  (Tiles over consecutive pixels of several images, which may straddle an image border, are never
   // narrower than those of image 0 alone, so they cannot widen what applies.)  The output rows are the same bits however they are tiled.
   if (g.n_lin <= 0 || g.Wp + 1 > WCAP) return 1;
-  const auto window_len = [&](int64_t ma, int64_t mb) {  // the kernel's WL for output rows [ma, mb]
+  const auto window_len = [&](int64_t ma, int64_t mb) {  // the kernel's WL (S2: window slots) for output rows [ma, mb]
     const auto idx = [&](int64_t m, int64_t& x) {
       const int64_t img = m / g.hw, rem = m % g.hw, y = rem / g.ow;
       x = rem % g.ow;
+      if (S2) return img * g.Sp + 2 * y * g.Wp + 2 * x;
       return img * g.Sp + ((UP ? y >> 1 : y) + 1) * g.Wp + (UP ? x >> 1 : x) + 1;
     };
     int64_t xa, xb;
     const int64_t pa = idx(ma, xa), pb = idx(mb, xb);
+    if (S2) return ((pb - pa + 2 * g.Wp + 3 + 1) >> 1) * 2;
     const int64_t q0 = (UP ? pa - (xa >> 1) : pa) - (g.Wp + 1);
     return (UP ? pb - (xb >> 1) + a.iw - 1 : pb) - q0 + g.Wp + 2;
   };
@@ -551,13 +592,19 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
 int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
   const int knob = g_seva_knobs.conv_win;
   if (knob == 0) return 1;
-  if (a.stride != 1 || a.pad_lo != 1 || a.a2 != nullptr || a.sk_ws != nullptr) return 1;
+  // e4m3 stride 2 with bottom / right padding only (the VAE encoder's Downsample2D convs in its fp8 mode); the UNet's stride-2 convs (pad 1)
+  // and every f16 stride-2 conv keep the per-tap gather
+  const bool s2 = fp8 && a.stride == 2 && a.pad_lo == 0 && !a.upsample;
+  if (!s2 && (a.stride != 1 || a.pad_lo != 1)) return 1;
+  if (a.a2 != nullptr || a.sk_ws != nullptr) return 1;
   const int up = a.upsample ? 2 : 1;
-  if (a.oh != up * a.ih || a.ow != up * a.iw || a.iw < 2 || a.ih < 2) return 1;
+  if (!s2 && (a.oh != up * a.ih || a.ow != up * a.iw)) return 1;  // (S2: oh = (ih - 2) / 2 + 1, checked by gemm.hip)
+  if (a.iw < 2 || a.ih < 2) return 1;
   const bool narrow = a.N <= 32 && a.N % 4 == 0;  // the UNet's head (4 channels), the VAE's conv_out
   if (a.cin % 64 != 0 || (a.N % 160 != 0 && a.N % 128 != 0 && !narrow) || a.K != 9LL * a.cin) return 1;
   ConvWinGeom g{};
   g.Wp = a.iw + 1;             // padded SOURCE space (UP: the image before the nearest-2x upsample)
+  if (s2) g.Wp += g.Wp & 1;    // S2: frame columns on the right only, as many as make the row pitch even (parity of P = parity of x)
   g.Sp = (a.ih + 1) * g.Wp;
   g.hw = a.oh * a.ow;
   g.ow = a.ow;
@@ -598,6 +645,21 @@ int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
     // MFMA no longer fit beside 100 accumulators: 2 KB of scratch; gemm.hip's e4m3 kernels found the same); cin counts 2-byte units
     if (a.N % 128 != 0 || a.w_exp == nullptr) return 1;
     const bool eight = knob == 2;  // two 4-wave workgroups per CU are faster on every e4m3 shape of a step (profiles/r04_kconvwin_fp8.log)
+    if (s2) {
+      // The VAE encoder's three Downsample2D convs (576 -> 288, 288 -> 144, 144 -> 72 px): the window of a stride-2 tile has about four times
+      // its output pixels, so one 4-wave workgroup per CU on 128-row tiles (no 8-wave variant).  Linear tiles where one image's windows fit
+      // 864 slots (output rows up to 72 px: a 128-pixel tile spans at most three of them, 846 slots at 72 px), else 2-D tiles of 16 x 8 output
+      // pixels (a 17 x 33 source window: 561 slots; 144 and 288 px output rows).
+      // Both are decided from one image's dimensions.  No e4m3 output epilogue here (the encoder's downsample output is the fp32 stream).
+      // Measured at 7 frames per pass, the family is SLOWER than the e4m3 per-tap gather on all three shapes (255 / 181 / 157 us against
+      // 184 / 133 / 110 us: one 4-wave workgroup per CU does not hide the barriers; profiles/r05_kvae_fp8_encode.log), so it runs only when
+      // the conv_win knob asks for it (1 or 2); by default these convs keep the gather, as the decoder's families follow the faster kernel.
+      if (knob != 1 && knob != 2) return 1;
+      if (a.out_f8) return 1;
+      int rc = launch_win<128, 128, 4, 864, false, true, false, 0, true, false, true>(a, g, s);
+      if (rc == 1) rc = launch_win<128, 128, 4, 568, false, true, false, 16, true, false, true>(a, g, s);
+      return rc;
+    }
     // The VAE decoder's fp8 mode (128 / 256 / 512 channels, 72 .. 576 px rows) follows the f16 128-column family: linear tiles where the
     // window fits, else 2-D tiles of 16 output columns.  Fused nearest-2x upsample and the e4m3 output epilogue (out_f8: the resnet that
     // feeds an upsample conv writes its A operand) are instantiations of their own; the plain family keeps its linear chain unchanged.

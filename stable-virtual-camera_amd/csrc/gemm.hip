@@ -1017,11 +1017,20 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
       if (half_m8) return wide8 ? launch<64, 160, 0, 0, true>(a, s) : launch<64, 128, 0, 0, true>(a, s);
       return launch<128, 128, 0, 0, true>(a, s);
     }
-    // 3x3 / stride 1 / pad 1 convs: the window-staged kernel (conv_win.hip, e4m3 instantiations of its 128-column family)
-    if (d->mode == 1 && d->a2 == nullptr && g_seva_knobs.gemm_dbg < 0 && g_seva_knobs.gemm_bm <= 0 && g_seva_knobs.gemm_bn <= 0 && g_seva_knobs.gemm_chunks <= 0) {
+    // 3x3 / stride 1 / pad 1 convs and the stride-2 bottom / right-padded ones: the window-staged kernel (conv_win.hip, e4m3 instantiations)
+    const bool win_on = g_seva_knobs.conv_win != 0 && g_seva_knobs.gemm_dbg < 0 && g_seva_knobs.gemm_bm <= 0 && g_seva_knobs.gemm_bn <= 0 &&
+                        g_seva_knobs.gemm_chunks <= 0;
+    if (d->mode == 1 && d->a2 == nullptr && win_on) {
       const int rc = seva_conv_win_launch(a, s, true);
       if (rc <= 0) return rc;
     }
+    // e4m3 stride 2 + pad_br_only (the VAE encoder's fp8 downsample convs): the per-tap gather by default (measured faster, conv_win.hip);
+    // where the conv_win knob asks for the stride-2 window family (1 or 2) and it declines, an error, not a silent fall-back to the gather
+    SEVA_REQUIRE(!(d->mode == 1 && win_on && (g_seva_knobs.conv_win == 1 || g_seva_knobs.conv_win == 2) && d->stride == 2 && d->pad_br_only &&
+                   d->N % 128 == 0),
+                 "gemm fp8: the stride-2 bottom/right-padded conv runs on the window kernel only, which declined it (image %dx%d -> %dx%d, "
+                 "cin %d: no e4m3 output, statistics need oh*ow %% 64 == 0, 2-D tiles need ow %% 16 == 0 and oh %% 8 == 0, linear tiles a "
+                 "window of at most 864 slots)", d->ih, d->iw, d->oh, d->ow, d->cin);
     // the per-tap gather below has neither the fused upsample nor the e4m3 output in conv mode: only the window kernel runs those
     SEVA_REQUIRE(!(d->mode == 1 && (d->upsample || d->out_f8)),
                  "gemm fp8: a conv with %s runs on the window kernel only, which declined it (3x3 / stride 1 / pad 1, N %% 128 == 0, "

@@ -6,7 +6,8 @@ GEMM(P V^T) with V produced already transposed by swapping the GEMM operand role
 bias is added after P*V (rows of P sum to 1, exact).
 
 The decoder has an opt-in fp8 precision (`AutoEncoder.set_precision("fp8")`, or SEVA_VAE_PRECISION=fp8 when that was not
-called): see `fp8_decoder_convs`.  Encode is always f16.
+called): see `fp8_decoder_convs`.  The encoder has one of its own (`AutoEncoder.set_precision(..., encode="fp8")`, or
+SEVA_VAE_ENCODE_PRECISION=fp8 when no `encode=` was given): see `fp8_encoder_convs`.
 """
 
 from __future__ import annotations
@@ -33,6 +34,16 @@ def check_vae_precision(precision: str) -> str:
 def vae_precision_from_env() -> str:
     """SEVA_VAE_PRECISION=f16|fp8 (unset: f16); used only where `AutoEncoder.set_precision` was not called."""
     return check_vae_precision(os.environ.get("SEVA_VAE_PRECISION") or "f16")
+
+
+def vae_encode_precision_from_env() -> str:
+    """SEVA_VAE_ENCODE_PRECISION=f16|fp8 (unset: f16); used only where `AutoEncoder.set_precision` was not given `encode=`."""
+    return check_vae_precision(os.environ.get("SEVA_VAE_ENCODE_PRECISION") or "f16")
+
+
+def fp8_downsample_from_env() -> bool:
+    """SEVA_VAE_FP8_DOWNSAMPLE=1: the fp8 encode also runs the three downsample convs in e4m3 (off by default, see fp8_encoder_convs)."""
+    return os.environ.get("SEVA_VAE_FP8_DOWNSAMPLE", "0") == "1"
 
 
 def fp8_upsample_from_env() -> bool:
@@ -78,11 +89,46 @@ def fp8_decoder_convs(block_out, upsample: bool = False) -> list[str]:
     return names
 
 
-def pack_fp8_convs(sd: dict, block_out, upsample: bool = False) -> dict:
+def fp8_encoder_convs(block_out, downsample: bool = False) -> list[str]:
+    """Encoder convs that the fp8 encode runs on e4m3 operands (the counterpart of `fp8_decoder_convs`): every 3x3 conv inside a
+    resnet with cin % 128 == 0 and cout % 128 == 0, i.e. both convs of the down-block resnets and of the mid-block resnets.  These
+    stay f16:
+      * encoder.conv_in (3 input channels) and the folded encoder.conv_out + quant_conv (4 output channels);
+      * the mid-block attention GEMMs;
+      * conv2 of the channel-changing resnets (128 -> 256, 256 -> 512): the folded 1x1 shortcut (seva_gemm_desc.a2) is f16-only;
+      * the three downsample convs (3x3, stride 2, bottom / right padding), unless `downsample` (SEVA_VAE_FP8_DOWNSAMPLE=1).  Like
+        the decoder's upsample convs, their A operand is the residual stream itself.  With `downsample`, the second resnet of a down
+        block writes `conv + residual` as e4m3 straight into the downsample conv's A operand; without, its e4m3 conv2 writes that
+        f16 operand.
+    The GroupNorm + SiLU in front of an e4m3 conv writes e4m3."""
+    def ok(ci, co):
+        return ci % 128 == 0 and co % 128 == 0
+
+    names = []
+    cin = block_out[0]
+    for i, cout in enumerate(block_out):
+        for j in range(2):
+            ci = cin if j == 0 else cout
+            p = f"encoder.down_blocks.{i}.resnets.{j}"
+            if ok(ci, cout):
+                names.append(p + ".conv1")
+            if ci == cout and ok(cout, cout):
+                names.append(p + ".conv2")
+        cin = cout
+        if downsample and i != len(block_out) - 1 and ok(cout, cout):
+            names.append(f"encoder.down_blocks.{i}.downsamplers.0.conv")
+    top = block_out[-1]
+    for r in range(2):
+        if ok(top, top):
+            names += [f"encoder.mid_block.resnets.{r}.conv1", f"encoder.mid_block.resnets.{r}.conv2"]
+    return names
+
+
+def pack_fp8_convs(sd: dict, block_out, upsample: bool = False, names=None) -> dict:
     """{prefix + ".w8": e4m3 bytes [cout, 9 * cin] (K ordered (ky, kx, ci), the UNet's fp8 conv layout), prefix + ".w8e":
-    E8M0 scale bytes [cout]} for `fp8_decoder_convs`, quantised from the fp32 weights by `ops.quantize_weight_fp8`."""
+    E8M0 scale bytes [cout]} for `names` (default: `fp8_decoder_convs`), quantised from the fp32 weights by `ops.quantize_weight_fp8`."""
     W8 = {}
-    for p in fp8_decoder_convs(block_out, upsample):
+    for p in fp8_decoder_convs(block_out, upsample) if names is None else names:
         w = sd[p + ".weight"].float()
         W8[p + ".w8"], W8[p + ".w8e"] = ops.quantize_weight_fp8(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1))
     return W8
@@ -102,7 +148,7 @@ class _VaeEngineBase:
         _native.load()
         return params[0].device
 
-    _w8: dict = {}  # e4m3 conv weights of the running decode (fp8 precision), else empty
+    _w8: dict = {}  # e4m3 conv weights of the running decode / encode (fp8 precision), else empty
 
     def __init__(self, weights):
         self.device = self._resolve_device(weights)
@@ -187,8 +233,8 @@ class _VaeEngineBase:
         `conv + shortcut` straight into that buffer -- the same rounding the separate cast pass made -- and the fp32 tensor
         (4 B written, 4 B read back per element at up to 576 x 576 x 256) is never formed.  The shortcut conv's f16 input comes
         out of the first GroupNorm's pass over x (`raw_f16`) instead of a cast pass of its own.
-        fp8 decode: a conv with e4m3 weights in `self._w8` reads the e4m3 output of its GroupNorm; f8_out is f16_out's e4m3
-        twin (the upsample conv's A operand, written by the e4m3 conv2's epilogue, saturating)."""
+        fp8 decode / encode: a conv with e4m3 weights in `self._w8` reads the e4m3 output of its GroupNorm; f8_out is f16_out's
+        e4m3 twin (the upsample / downsample conv's A operand, written by the e4m3 conv2's epilogue, saturating)."""
         W, W8, hw = self.W, self._w8, h * w
         f8_1, f8_2 = p + ".conv1.w8" in W8, p + ".conv2.w8" in W8
         assert f8_out is None or f8_2
@@ -359,6 +405,20 @@ class VaeEncoderEngine(_VaeEngineBase):
     PREFIXES = ("encoder.", "quant_conv.")
     CONV_IN, CONV_OUT = "encoder.conv_in", "encoder.conv_out"
 
+    def __init__(self, weights, precision: str = "f16"):
+        super().__init__(weights)
+        self.precision = check_vae_precision(precision)  # encode precision; may be changed between encodes (AutoEncoder.set_precision)
+        self._src = weights
+        self.fp8_downsample = fp8_downsample_from_env()
+        self.W8 = None  # e4m3 conv weights, packed the first time an fp8 encode runs
+
+    def fp8_weights(self) -> dict:
+        if self.W8 is None:
+            sd = self._src.state_dict()
+            self.W8 = pack_fp8_convs({k: v.detach().to(self.device) for k, v in sd.items() if k.startswith("encoder.")},
+                                     self.block_out, names=fp8_encoder_convs(self.block_out, self.fp8_downsample))
+        return self.W8
+
     def _pack_ends(self, sd, conv3):
         L = self.latent
         wo, bo = sd["encoder.conv_out.weight"].double(), sd["encoder.conv_out.bias"].double()
@@ -378,6 +438,7 @@ class VaeEncoderEngine(_VaeEngineBase):
             raise ValueError(f"VAE encode needs H and W divisible by {1 << nd} (got {h}x{w})")
         self.gn_ws = self._buf("gn_ws", (n * ops.GN_WORKSPACE_SLABS * 32 * 2,), F32)
         self._stats = {}
+        self._w8 = W8 = self.fp8_weights() if check_vae_precision(self.precision) == "fp8" else {}
         one = torch.ones((n,), dtype=F32, device=self.device)
         x16 = self._buf("v_x16", (n, h * w, CIN_PAD), F16)
         ops.nchw_to_nhwc_f16(x, None, x16, scale=one)  # channels-last, 3 -> 64 zero-padded channels
@@ -388,17 +449,24 @@ class VaeEncoderEngine(_VaeEngineBase):
         self._produced(cur, st)
         cin = c0
         for i, cout in enumerate(self.block_out):
-            d16 = self._buf("v_dn16", (n, h, w, cout), F16) if i != nd else None
+            p = f"encoder.down_blocks.{i}.downsamplers.0.conv"
+            # e4m3 downsample conv (SEVA_VAE_FP8_DOWNSAMPLE=1): its A operand is written by the e4m3 epilogue of the second resnet's conv2
+            dn8 = i != nd and p + ".w8" in W8 and f"encoder.down_blocks.{i}.resnets.1.conv2.w8" in W8
+            d16 = self._buf("v_dn16", (n, h, w, cout), F16) if i != nd and not dn8 else None
+            d8 = self._buf("v_dn8", (n, h, w, cout), U8) if dn8 else None
             for j in range(2):
                 cur = self._resnet(f"encoder.down_blocks.{i}.resnets.{j}", cur, n, h, w, cin if j == 0 else cout, cout,
-                                   f16_out=d16 if j == 1 else None)
+                                   f16_out=d16 if j == 1 else None, f8_out=d8 if j == 1 else None)
             cin = cout
             if i != nd:
-                p = f"encoder.down_blocks.{i}.downsamplers.0.conv"
                 h, w = h // 2, w // 2
                 cur = self._buf("out:" + p, (n, h * w, cout), F32)
                 st = self._stats_buf("out:" + p, n * h * w, h * w, cout)
-                ops.conv3x3(d16, W[p + ".w"], stride=2, pad_br_only=True, bias=W[p + ".b"], out_f32=cur, ch_stats=st)
+                if dn8:
+                    ops.conv3x3(d8, W8[p + ".w8"], w_exp=W8[p + ".w8e"], stride=2, pad_br_only=True, bias=W[p + ".b"], out_f32=cur,
+                                ch_stats=st)
+                else:
+                    ops.conv3x3(d16, W[p + ".w"], stride=2, pad_br_only=True, bias=W[p + ".b"], out_f32=cur, ch_stats=st)
                 self._produced(cur, st)
         top = self.block_out[-1]
         cur = self._resnet("encoder.mid_block.resnets.0", cur, n, h, w, top, top)

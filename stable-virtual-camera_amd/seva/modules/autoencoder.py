@@ -180,18 +180,40 @@ class AutoEncoder(nn.Module):
         self._engine = None
         self._enc_engine = None
         self._precision = None  # decode precision set by set_precision; None: SEVA_VAE_PRECISION, else "f16"
+        self._encode_precision = None  # encode precision set by set_precision(encode=); None: SEVA_VAE_ENCODE_PRECISION, else "f16"
 
-    def set_precision(self, precision: str) -> "AutoEncoder":
+    def set_precision(self, precision: str, *, encode: str | None = None) -> "AutoEncoder":
         """Decode precision: "f16" (the default) or "fp8" (the decoder's 3x3 convs with 128k channels on e4m3 weights and
-        activations, seva/_vae_engine.py:fp8_decoder_convs).  Decode only: encoded latents feed the denoiser's replace
-        channels, so encode stays f16.  Independent of `Seva.set_precision`.  Switching back to "f16" gives exactly the
-        default results; the e4m3 weights are packed the first time an fp8 decode runs."""
+        activations, seva/_vae_engine.py:fp8_decoder_convs).  `encode` sets the encode precision on its own: "f16" (the
+        default) or "fp8" (the encoder's resnet 3x3 convs with 128k channels, seva/_vae_engine.py:fp8_encoder_convs; the
+        downsample convs too with SEVA_VAE_FP8_DOWNSAMPLE=1); None leaves it as it is.  Encoded latents feed the denoiser's
+        replace channels, so `set_precision("fp8")` alone keeps an f16 encode; what an e4m3 encode costs there is measured in
+        DESIGN.md section 5.  The two precisions do not affect each other, and `Seva.set_precision` touches neither.
+        Switching back to "f16" gives exactly the default results; the e4m3 weights are packed the first time an fp8
+        decode / encode runs.  A refused value changes nothing."""
         from .._vae_engine import check_vae_precision
 
-        self._precision = check_vae_precision(precision)
+        precision = check_vae_precision(precision)
+        if encode is not None:
+            self._encode_precision = check_vae_precision(encode)
+            if self._enc_engine is not None:
+                self._enc_engine.precision = self._encode_precision
+        self._precision = precision
         if self._engine is not None:
             self._engine.precision = self._precision
         return self
+
+    @property
+    def encode_precision(self) -> str:
+        """The encode precision in effect: set_precision's `encode=` value, else SEVA_VAE_ENCODE_PRECISION (read when the
+        encoder engine is built), else "f16"."""
+        if self._encode_precision is not None:
+            return self._encode_precision
+        if self._enc_engine is not None:
+            return self._enc_engine.precision
+        from .._vae_engine import vae_encode_precision_from_env
+
+        return vae_encode_precision_from_env()
 
     @property
     def precision(self) -> str:
@@ -217,7 +239,7 @@ class AutoEncoder(nn.Module):
         if self._enc_engine is None:
             from .._vae_engine import VaeEncoderEngine
 
-            self._enc_engine = VaeEncoderEngine(self.module)
+            self._enc_engine = VaeEncoderEngine(self.module, precision=self.encode_precision)
         return self._enc_engine
 
     def engine(self):

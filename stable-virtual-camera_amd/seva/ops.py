@@ -199,7 +199,9 @@ def conv3x3(
     pad_br_only: zero padding at the bottom / right edge only (diffusers Downsample2D, pad (0,1,0,1)).
     fp8 mode (w_exp given): x and w are uint8 tensors of e4m3 bytes, cin % 128 == 0.  The fused upsample and out_f8 (uint8
     [.., cout] e4m3 bytes, saturating RNE of the fp32 result, alone or beside out_f32; pixel pitch and pointer multiples of 8; not
-    together with upsample) run on the window kernel only (stride 1, cout % 128 == 0): where it declines, the call raises instead of falling back."""
+    together with upsample) run on the window kernel only (stride 1, cout % 128 == 0): where it declines, the call raises instead of falling back.
+    The stride-2 pad_br_only conv in fp8 mode (the VAE encoder's fp8 downsample convs) takes the per-tap gather by default; with the conv_win
+    knob at 1 or 2 it runs on the window kernel's stride-2 family (cout % 128 == 0, no out_f8), and raises where that declines."""
     require_cuda(x, w)
     fp8 = w_exp is not None
     assert x.dtype == w.dtype == (U8 if fp8 else F16) and x.dim() == 4 and x.is_contiguous()
