@@ -160,8 +160,20 @@ typedef struct seva_ff_desc {
   const float* ln_beta;
   int64_t ldx;
   float ln_eps;
+  /* seva_ff_fused_fp8 only (ABI 12; ignored by seva_ff_fused_f16): uint8 E8M0 scale bytes 127 + e, one per weight row:
+   * w1_exp [8C] (interleaved row order), w2_exp [C]; row n of a weight holds e4m3(w[n] * 2^-e[n]). */
+  const void* w1_exp;
+  const void* w2_exp;
 } seva_ff_desc;
 int seva_ff_fused_f16(const seva_ff_desc* d, seva_stream_t stream);
+/* e4m3 sibling (ABI 12; the fp8 mode's `ff="fp8"` option): the same operator on v_mfma_scale_f32_16x16x128_f8f6f4 with fp32
+ * accumulation.  a: e4m3 [M][lda] bytes (lda >= C, a multiple of 16; columns >= C are not read) or the LayerNorm prologue, whose
+ * normalised row is rounded once to e4m3 (saturating, round-to-nearest-even, unit scale); w1: e4m3 [8C][KP] with KP = the multiple
+ * of 128 at or above C and zero columns >= C, interleaved GEGLU rows as above; w2: e4m3 [C][4C] with its columns permuted into the
+ * kernel's order of the hidden features (csrc/ff_fp8.h; seva.ops.pack_ff_fp8 writes both).  The hidden value v * gelu_erf(g) is
+ * rounded once to e4m3 (saturating), the value the two-kernel e4m3 chain stores through seva_gemm_desc.out_f8.  w1_exp and w2_exp
+ * are required.  Every output row depends on its own input row only. */
+int seva_ff_fused_fp8(const seva_ff_desc* d, seva_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Scaled-dot-product attention, head dim 64, no mask, fp16 in/out, fp32 softmax.

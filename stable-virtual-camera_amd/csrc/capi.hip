@@ -88,7 +88,7 @@ SevaProfScope::~SevaProfScope() {
 extern "C" {
 
 const char* seva_last_error(void) { return g_err; }
-int seva_abi_version(void) { return 11; }
+int seva_abi_version(void) { return 12; }
 const char* seva_target_arch(void) { return "gfx950"; }
 
 int seva_set_knob(const char* name, int value) {

@@ -21,6 +21,7 @@
 // Weight layouts are those of seva_gemm_f16: W1 [8C][C] rows interleaved in groups of 64 = [32 value | 32 gate]
 // (b1 likewise), W2 [C][4C].
 #include "gemm_common.h"
+#include "ff_fp8.h"
 
 #include <atomic>
 
@@ -45,9 +46,28 @@ struct FfArgs {
   float ln_eps;
 };
 
+// e4m3 kernel (seva_ff_fused_fp8): the same arguments, `a` / w1 / w2 as e4m3 bytes (lda counts bytes), plus the weights'
+// per-row E8M0 scale bytes
+struct Ff8Args {
+  FfArgs f;
+  const uint8_t* w1_exp;
+  const uint8_t* w2_exp;
+};
+
 template <int N>
 __device__ __forceinline__ void ff_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// glds16_raw with a wave-uniform 64-bit base in SGPRs and a 32-bit per-lane byte offset (saddr form): one VGPR per staging pass
+// instead of a 64-bit address pair (the e4m3 kernel runs at the register limit)
+static __device__ __forceinline__ void glds16_sv(const void* sbase, unsigned voff, unsigned lds_wave_base) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(sbase), "s"(lds_wave_base)
+      : "memory");
 }
 
 
@@ -334,6 +354,332 @@ int ff_launch8(const FfArgs& a, hipStream_t s) {
   return seva_check_launch("ff_fused8_kernel");
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// e4m3 sibling of ff_fused8_kernel (seva_ff_fused_fp8, the fp8 mode's `ff="fp8"` option): the same 128-row tile, 8 waves,
+// 3-deep W1 LDS-DMA ring and double-buffered W2 slice, with both GEMMs on v_mfma_scale_f32_16x16x128_f8f6f4.
+//   * A: the LayerNorm prologue rounds the normalised row once to e4m3 (saturating RNE, unit scale) and zero-pads it to
+//     KP = the multiple of 128 at or above C IN REGISTERS (C = 320: the sixth 64-wide chunk is zero); or e4m3 bytes `a`.
+//     Registers: 2 token blocks x KP/128 K-tiles x 8 dwords (48 at C = 320, against 80 for the f16 panel).
+//   * stage 1: a K-tile is 128 W1 rows x 128 bytes (128 e4m3 elements: the f16 kernel's LDS image, same swizzle); lane group
+//     fg's 32-byte operand is chunks fg and 4 + fg of a row for BOTH operands (the GEMM kernels' convention).  W1 row scales
+//     2^e enter as the E8M0 scale of the weight operand (constant along K); four scale bytes per chunk and lane sit in LDS.
+//   * GEGLU (geglu4) -> hidden value rounded once to e4m3, 8 features (one chunk) per lane and token block.
+//   * stage 2 runs once per PAIR of 64-feature chunks (one 128-deep MFMA k-step): the lane's 16 bytes of the pair plus the
+//     partner wave's 16 (LDS exchange) are its B operand as they sit.  W2's columns are stored in that order (ff_fp8.h).
+template <int C>
+__global__ __launch_bounds__(512, 2) void ff_fused8_fp8_kernel(Ff8Args q) {
+  const FfArgs& p = q.f;
+  constexpr int KP = FF8_KP(C), NK1 = KP / 128, NU = C / 64;  // K-tiles of stage 1; 64-wide input chunks that hold data
+  constexpr int NJ2 = C / 16, NJH = NJ2 / 2, NCH = C / 16, NP = NCH / 2, NSC2 = (NJH + 3) / 4;
+  constexpr int W1_BYTES = 128 * 128, W2_BYTES = C * 128;
+  constexpr int W2_PASSES = C / 64;  // 8-row passes per wave and slice (C/8 rows per wave)
+  constexpr int W2_PER_KT = (W2_PASSES + 2 * NK1 - 1) / (2 * NK1);  // a slice is staged over the 2 NK1 K-tiles of a chunk pair
+  static_assert(NJ2 % 2 == 0 && NCH % 2 == 0, "output blocks split over two waves; chunks taken in pairs");
+  static_assert(2 + W2_PER_KT <= 3, "wait_all_but counts at most 3 loads per K-tile");
+  typedef int v4i_t __attribute__((ext_vector_type(4)));
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // [W1 ring: 3 tiles][W2 buf0][W2 buf1][b1: 8C floats][W1 scale words: NCH x 2 halves x 16 rows][exchange: 16 KiB]
+  constexpr int W1_RING = 3;
+  char* const lds_w1 = smem;
+  char* const lds_w2 = smem + W1_RING * W1_BYTES;
+  float* const lds_b1 = (float*)(smem + W1_RING * W1_BYTES + 2 * W2_BYTES);
+  int* const lds_s1 = (int*)(smem + W1_RING * W1_BYTES + 2 * W2_BYTES + 8 * C * 4);
+  char* const lds_x = smem + W1_RING * W1_BYTES + 2 * W2_BYTES + 8 * C * 4 + NCH * 32 * 4;
+  const unsigned lds_base_u32 = __builtin_amdgcn_readfirstlane(lds_addr_u32(smem));
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int mr = wave & 3, h = wave >> 2;
+  const int fr = lane & 15, fg = lane >> 4;
+  const int sr = lane >> 3, sp = lane & 7;
+
+  const int tm = xcd_remap(blockIdx.x, p.tiles_m);
+  const int64_t m0 = (int64_t)tm * 128 + mr * 32;
+
+  // areg[i][u]: input elements 64 u + 16 fg .. + 15 of token row m0 + 16 i + fr; K-tile kt = lo u = 2 kt, hi u = 2 kt + 1
+  half8_t areg[2][2 * NK1];
+  if (p.ln_x) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int64_t m = m0 + 16 * i + fr;
+      if (m >= p.M) m = p.M - 1;
+      const float* xr = p.ln_x + m * p.ldx + 16 * fg;
+      f32x4 v[NU][4];
+#pragma unroll
+      for (int u = 0; u < NU; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[u][e] = first_read(*(const f32x4*)(xr + 64 * u + 4 * e));
+      float sum = 0.f;
+#pragma unroll
+      for (int u = 0; u < NU; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sum += v[u][e][0] + v[u][e][1] + v[u][e][2] + v[u][e][3];
+      sum += __shfl_xor(sum, 16, 64);
+      asm volatile("" : "+v"(sum));
+      sum += __shfl_xor(sum, 32, 64);
+      asm volatile("" : "+v"(sum));
+      const float mean = sum / (float)C;
+      float ss = 0.f;
+#pragma unroll
+      for (int u = 0; u < NU; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float dlt = v[u][e][r] - mean;
+            ss += dlt * dlt;
+          }
+      ss += __shfl_xor(ss, 16, 64);
+      asm volatile("" : "+v"(ss));
+      ss += __shfl_xor(ss, 32, 64);
+      asm volatile("" : "+v"(ss));
+      const float rstd = rsqrtf(ss / (float)C + p.ln_eps);
+#pragma unroll
+      for (int u = 0; u < 2 * NK1; ++u) {
+        if (u >= NU) {  // zero padding C .. KP - 1 (W1's columns there are zero too)
+          areg[i][u] = half8_t{};
+          continue;
+        }
+        v4i_t w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const f32x4 g4 = first_read(*(const f32x4*)(p.ln_gamma + 64 * u + 16 * fg + 4 * e));
+          const f32x4 b4 = first_read(*(const f32x4*)(p.ln_beta + 64 * u + 16 * fg + 4 * e));
+          float y[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) y[r] = (v[u][e][r] - mean) * rstd * g4[r] + b4[r];
+          w[e] = pack_fp8x4(y[0], y[1], y[2], y[3]);
+        }
+        areg[i][u] = __builtin_bit_cast(half8_t, w);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int64_t m = m0 + 16 * i + fr;
+      if (m >= p.M) m = p.M - 1;
+      const uint8_t* ap = (const uint8_t*)p.a + m * p.lda + 16 * fg;
+#pragma unroll
+      for (int u = 0; u < 2 * NK1; ++u) areg[i][u] = u < NU ? *(const half8_t*)(ap + 64 * u) : half8_t{};
+    }
+  }
+  // stage-2 accumulators start from zero; the residual is added in the epilogue (loaded here, its 80 registers at C = 320 pushed
+  // A fragments into scratch)
+  f32x4 acc2[2][NJH];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int jj = 0; jj < NJH; ++jj) acc2[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < 2 * C; i += 512) *(f32x4*)(lds_b1 + 4 * i) = *(const f32x4*)(p.b1 + 4 * i);
+  // W1 scale word of (chunk hc, half hh, MFMA row f): byte j = 127 + e of the row that block j (value e0, value e1, gate e0,
+  // gate e1) reads in MFMA row f -- the rows of the f16 kernel's fragment reads
+  for (int idx = threadIdx.x; idx < NCH * 32; idx += 512) {
+    const int hc = idx >> 5, hh = (idx >> 4) & 1, f = idx & 15;
+    const int rb = hc * 128 + 64 * hh + 8 * (f >> 2) + (f & 3);
+    lds_s1[idx] = (int)q.w1_exp[rb] | ((int)q.w1_exp[rb + 4] << 8) | ((int)q.w1_exp[rb + 32] << 16) | ((int)q.w1_exp[rb + 36] << 24);
+  }
+  // W2 row scales of this wave's output blocks (constant over the whole kernel): 4 blocks per word
+  int wsc2[NSC2];
+#pragma unroll
+  for (int w = 0; w < NSC2; ++w) wsc2[w] = 0;
+#pragma unroll
+  for (int jj = 0; jj < NJH; ++jj) wsc2[jj >> 2] |= (int)q.w2_exp[16 * (h * NJH + jj) + fr] << (8 * (jj & 3));
+  // retire every compiler-visible global load here: the main loop's waits are the counted ones below
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u) asm volatile("" : "+v"(areg[i][u]));  // (the zero padding stays a constant the allocator can rematerialise)
+#pragma unroll
+    for (int jj = 0; jj < NJH; ++jj) asm volatile("" : "+v"(acc2[i][jj]));
+  }
+#pragma unroll
+  for (int w = 0; w < NSC2; ++w) asm volatile("" : "+v"(wsc2[w]));
+
+  auto w1_key = [](int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); };
+  unsigned w1_voff[2];  // W1 tile: wave w stages rows 16w .. 16w+15 (2 passes); byte offsets (W1 < 4 GiB)
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int row = wave * 16 + 8 * i + sr;
+    w1_voff[i] = (unsigned)(row * KP + (sp ^ w1_key(row)) * 16);
+  }
+  unsigned w2_voff[2];  // W2 slice: wave w stages rows (C/8)w .. ; passes two apart share the swizzle key
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int row = wave * (C / 8) + 8 * i + sr;
+    w2_voff[i] = (unsigned)(row * (4 * C) + (sp ^ ((row >> 1) & 7)) * 16);
+  }
+  auto stage_w1 = [&](int buf, int hc, int kt) {
+    const unsigned dst = lds_base_u32 + buf * W1_BYTES + wave * 16 * 128;
+    const uint8_t* const base = (const uint8_t*)p.w1 + (int64_t)hc * 128 * KP + kt * 128;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) glds16_sv(base, w1_voff[i], dst + i * 1024);
+  };
+  auto stage_w2_part = [&](int buf, int pp, int part) {
+    const unsigned dst = lds_base_u32 + W1_RING * W1_BYTES + buf * W2_BYTES + wave * (C / 8) * 128;
+#pragma unroll
+    for (int u = 0; u < W2_PER_KT; ++u) {
+      const int i = part * W2_PER_KT + u;
+      if (i < W2_PASSES)
+        glds16_sv((const uint8_t*)p.w2 + (int64_t)(i >> 1) * 16 * (4 * C) + pp * 128, w2_voff[i & 1], dst + i * 1024);
+    }
+  };
+  auto barrier_raw = [&]() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+
+  int w1_off[2], w2_off[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const int rb = 64 * h + 8 * (fr >> 2) + (fr & 3);
+    w1_off[s] = rb * 128 + (((4 * s + fg) ^ w1_key(rb)) << 4);
+    const int r2 = 16 * (h * NJH) + fr;
+    w2_off[s] = r2 * 128 + (((4 * s + fg) ^ ((r2 >> 1) & 7)) << 4);
+  }
+  char* const x_mine = lds_x + ((mr * 2 + h) * 2) * 1024 + lane * 16;
+  const char* const x_q0 = lds_x + (mr * 2 * 2) * 1024 + lane * 16;  // half 0's two fragments, then half 1's
+
+  constexpr int NTILES = NCH * NK1;
+  auto stage_w1_seq = [&](int g) { stage_w1(g % W1_RING, g / NK1, g % NK1); };
+  auto wait_all_but = [&](int n) {
+    if (n >= 3) ff_wait_vm<3>();
+    else if (n == 2) ff_wait_vm<2>();
+    else if (n == 1) ff_wait_vm<1>();
+    else ff_wait_vm<0>();
+  };
+  __syncthreads();
+  stage_w1_seq(0);
+#pragma unroll
+  for (int part = 0; part < 2 * NK1; ++part) stage_w2_part(0, 0, part);
+  stage_w1_seq(1);
+  ff_wait_vm<2>();  // tile 0 and the first W2 slice have landed; tile 1 (2 loads) flies on
+  barrier_raw();
+
+  int g = 0;  // W1 tile sequence number
+  for (int pp = 0; pp < NP; ++pp) {
+    v4i_t hx[2];  // [token block]: e4m3 hidden features of chunk 2 pp (bytes 0..7) and 2 pp + 1 (bytes 8..15)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int hc = 2 * pp + c;
+      // stage-1 accumulators start from zero, b1 is added after the chunk's last K-tile: no bias registers live under the MFMAs
+      f32x4 acc1[2][4];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const int sc1 = lds_s1[hc * 32 + h * 16 + fr];
+#pragma unroll
+      for (int kt = 0; kt < NK1; ++kt) {
+        int issued = 0;
+        if (g + 2 < NTILES) {
+          stage_w1_seq(g + 2);
+          issued += 2;
+        }
+        const int kk = c * NK1 + kt;
+        if (pp + 1 < NP && kk * W2_PER_KT < W2_PASSES) {
+          stage_w2_part((pp + 1) & 1, pp + 1, kk);
+          issued += (kk + 1) * W2_PER_KT <= W2_PASSES ? W2_PER_KT : W2_PASSES - kk * W2_PER_KT;
+        }
+        const char* const tb = lds_w1 + (g % W1_RING) * W1_BYTES;
+#pragma unroll
+        for (int jp = 0; jp < 2; ++jp) {  // value blocks, then gate blocks: 16 fragment registers live, not 32
+          half8_t bfr[2][2];
+#pragma unroll
+          for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) bfr[s][e] = *(const half8_t*)(tb + w1_off[s] + (32 * jp + 4 * e) * 128);
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+              acc1[i][2 * jp + e] = mfma_f8(2 * jp + e, bfr[0][e], bfr[1][e], areg[i][2 * kt], areg[i][2 * kt + 1], acc1[i][2 * jp + e], sc1);
+          if (jp == 0) __builtin_amdgcn_sched_barrier(0);
+        }
+        // the K-tile's scaled MFMAs stay in front of its barrier (gemm.hip / conv_win.hip: hipcc otherwise sinks them behind it)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(acc1[i][j]));
+        wait_all_but(issued);  // tile g + 1 (issued a K-tile ago) has landed; this K-tile's loads stay in flight
+        barrier_raw();
+        ++g;
+      }
+      f32x4 bias[4];  // blocks 0, 1 = value e = 0, 1; blocks 2, 3 = gate
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const float* bp = lds_b1 + hc * 128 + 64 * h + 8 * fg + 4 * e;
+        bias[e] = first_read(*(const f32x4*)bp);
+        bias[2 + e] = first_read(*(const f32x4*)(bp + 32));
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const f32x4 o0 = geglu4(acc1[i][0] + bias[0], acc1[i][2] + bias[2]);
+        const f32x4 o1 = geglu4(acc1[i][1] + bias[1], acc1[i][3] + bias[3]);
+        hx[i][2 * c] = pack_fp8x4(o0[0], o0[1], o0[2], o0[3]);
+        hx[i][2 * c + 1] = pack_fp8x4(o1[0], o1[1], o1[2], o1[3]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) *(v4i_t*)(x_mine + i * 1024) = hx[i];
+    barrier_raw();  // both halves of every row group have published the pair's features
+    half8_t hq[2][2];  // [half q that produced the features = lo / hi 16 bytes of the operand][token block i]
+#pragma unroll
+    for (int qq = 0; qq < 2; ++qq)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) hq[qq][i] = *(const half8_t*)(x_q0 + (qq * 2 + i) * 1024);
+    const char* const t2 = lds_w2 + (pp & 1) * W2_BYTES;
+#pragma unroll
+    for (int jj = 0; jj < NJH; ++jj) {
+      const half8_t w0 = *(const half8_t*)(t2 + w2_off[0] + jj * (16 * 128));
+      const half8_t w1f = *(const half8_t*)(t2 + w2_off[1] + jj * (16 * 128));
+#pragma unroll
+      for (int i = 0; i < 2; ++i) acc2[i][jj] = mfma_f8(jj, w0, w1f, hq[0][i], hq[1][i], acc2[i][jj], wsc2[jj >> 2]);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int jj = 0; jj < NJH; ++jj) asm volatile("" : "+v"(acc2[i][jj]));
+    barrier_raw();  // W2 buffer (pp & 1) and the exchange slots are rewritten during the next pair
+  }
+
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int64_t m = m0 + 16 * i + fr;
+    const bool ok = m < p.M;
+#pragma unroll
+    for (int jj = 0; jj < NJH; ++jj) {
+      const int f = 16 * (h * NJH + jj) + 4 * fg;
+      if (!ok) continue;
+      f32x4 v = acc2[i][jj] + first_read(*(const f32x4*)(p.b2 + f));
+      if (p.residual) v += first_read(*(const f32x4*)(p.residual + m * p.ldr + f));
+      if (p.out_f32) *(f32x4*)(p.out_f32 + m * p.ldo32 + f) = v;
+      if (p.out_f16) {
+        const half4_t hh = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+        *(half4_t*)(p.out_f16 + m * p.ldo16 + f) = hh;
+      }
+    }
+  }
+}
+
+template <int C>
+int ff_launch8_fp8(const Ff8Args& a, hipStream_t s) {
+  constexpr int lds = 3 * 128 * 128 + 2 * C * 128 + 8 * C * 4 + (C / 16) * 32 * 4 + 16 * 1024;
+  static_assert(lds <= 160 * 1024, "LDS budget of one workgroup per CU");
+  static std::atomic<uint64_t> attr_devs{0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const uint64_t bit = 1ull << (dev & 63);
+  if (!(attr_devs.load(std::memory_order_relaxed) & bit)) {
+    (void)hipFuncSetAttribute((const void*)ff_fused8_fp8_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    attr_devs.fetch_or(bit, std::memory_order_relaxed);
+  }
+  hipLaunchKernelGGL((ff_fused8_fp8_kernel<C>), dim3((unsigned)a.f.tiles_m), dim3(512), lds, s, a);
+  return seva_check_launch("ff_fused8_fp8_kernel");
+}
+
 }  // namespace
 
 extern "C" int seva_ff_fused_f16(const seva_ff_desc* d, seva_stream_t stream) {
@@ -370,5 +716,48 @@ extern "C" int seva_ff_fused_f16(const seva_ff_desc* d, seva_stream_t stream) {
     case 128: return ff_launch8<128>(a, s);
     case 256: return ff_launch8<256>(a, s);
     default: return ff_launch8<320>(a, s);
+  }
+}
+
+// e4m3 operands (ff_fp8.h): a [M][lda] bytes (columns C .. KP - 1 are not read) or the LayerNorm prologue; w1 [8C][KP], w2 [C][4C]
+// column-permuted, w1_exp [8C] / w2_exp [C] E8M0 row scales.
+extern "C" int seva_ff_fused_fp8(const seva_ff_desc* d, seva_stream_t stream) {
+  SEVA_REQUIRE(d != nullptr, "ff_fused_fp8: null desc");
+  SEVA_REQUIRE(d->C == 64 || d->C == 128 || d->C == 256 || d->C == 320, "ff_fused_fp8: C=%d unsupported (64, 128, 256, 320)", d->C);
+  SEVA_REQUIRE(d->a || d->ln_x, "ff_fused_fp8: neither a nor ln_x given");
+  SEVA_REQUIRE(d->w1 && d->b1 && d->w2 && d->b2, "ff_fused_fp8: null operand");
+  SEVA_REQUIRE(d->w1_exp && d->w2_exp, "ff_fused_fp8: w1_exp and w2_exp (per-row E8M0 scale bytes) are required");
+  SEVA_REQUIRE(!d->ln_x || (d->ln_gamma && d->ln_beta && d->ldx >= d->C && d->ldx % 4 == 0 &&
+                            ((uintptr_t)d->ln_x | (uintptr_t)d->ln_gamma | (uintptr_t)d->ln_beta) % 16 == 0),
+               "ff_fused_fp8: LayerNorm prologue needs gamma, beta, a row pitch >= C (multiple of 4), 16-byte aligned pointers");
+  SEVA_REQUIRE(d->out_f32 || d->out_f16, "ff_fused_fp8: no output");
+  SEVA_REQUIRE(d->M > 0, "ff_fused_fp8: empty problem");
+  SEVA_REQUIRE(d->ln_x || (d->lda >= d->C && d->lda % 16 == 0), "ff_fused_fp8: lda=%lld invalid (bytes, >= C, multiple of 16)",
+               (long long)d->lda);
+  SEVA_REQUIRE((!d->residual || d->ldr % 4 == 0) && (!d->out_f32 || d->ldo32 % 4 == 0) && (!d->out_f16 || d->ldo16 % 4 == 0),
+               "ff_fused_fp8: row pitches must be multiples of 4");
+  SEVA_REQUIRE(((uintptr_t)(d->ln_x ? nullptr : d->a) | (uintptr_t)d->w1 | (uintptr_t)d->b1 | (uintptr_t)d->w2 | (uintptr_t)d->b2 |
+                (uintptr_t)d->residual | (uintptr_t)d->out_f32 | (uintptr_t)d->out_f16) % 16 == 0,
+               "ff_fused_fp8: pointers must be 16-byte aligned");
+  Ff8Args a{};
+  a.f.a = (const half_t*)d->a; a.f.w1 = (const half_t*)d->w1; a.f.b1 = d->b1; a.f.w2 = (const half_t*)d->w2; a.f.b2 = d->b2;
+  a.f.residual = d->residual; a.f.out_f32 = d->out_f32; a.f.out_f16 = (half_t*)d->out_f16;
+  a.f.M = d->M; a.f.lda = d->lda; a.f.ldr = d->ldr; a.f.ldo32 = d->ldo32; a.f.ldo16 = d->ldo16;
+  a.f.ln_x = d->ln_x; a.f.ln_gamma = d->ln_gamma; a.f.ln_beta = d->ln_beta; a.f.ldx = d->ldx; a.f.ln_eps = d->ln_eps;
+  a.w1_exp = (const uint8_t*)d->w1_exp; a.w2_exp = (const uint8_t*)d->w2_exp;
+  const int64_t tiles = (d->M + 127) / 128;
+  SEVA_REQUIRE(tiles <= 0x7fffffff, "ff_fused_fp8: too many rows");
+  a.f.tiles_m = (int)tiles;
+  hipStream_t s = (hipStream_t)stream;
+  const double C = (double)d->C;
+  const double flops = 2.0 * (double)d->M * C * (8.0 * C) + 2.0 * (double)d->M * (4.0 * C) * C;
+  const double bytes = (double)d->M * C * ((d->ln_x ? 4.0 : 1.0) + (d->residual ? 4.0 : 0.0) + (d->out_f32 ? 4.0 : 0.0) + (d->out_f16 ? 2.0 : 0.0)) +
+                       (8.0 * C * FF8_KP(d->C) + 4.0 * C * C);
+  SevaProfScope prof(0, flops, s, bytes);
+  switch (d->C) {
+    case 64: return ff_launch8_fp8<64>(a, s);
+    case 128: return ff_launch8_fp8<128>(a, s);
+    case 256: return ff_launch8_fp8<256>(a, s);
+    default: return ff_launch8_fp8<320>(a, s);
   }
 }

@@ -93,7 +93,7 @@ class SevaEngine:
         _native.load()
         return params[0].device
 
-    def __init__(self, model, precision: str | None = None, attention: str | None = None):
+    def __init__(self, model, precision: str | None = None, attention: str | None = None, ff: str | None = None):
         """precision "f16" (default; the parity mode, fp16 operands / fp32 accumulation) or "fp8" (BASELINE config 5:
         e4m3 weights AND activations on the block-scaled fp8 MFMA for the QKV / GEGLU / FF2 projections and the ResBlock 3x3
         convs whose reduction length is a multiple of 128 -- the C = 640 / 1280 levels; the C = 320 level (opt-in through
@@ -120,6 +120,17 @@ class SevaEngine:
         # for the two-kernel fp8 path, the step stays at 86.1 ms and the error doubles (rel-L2 2.9e-2 -> 5.2e-2).
         self.fp8_pad = _os.environ.get("SEVA_FP8_PAD", "0") == "1"
         self.ff_fused = _os.environ.get("SEVA_FF_FUSED", "1") != "0"  # 0: two-kernel GEGLU + FF2 everywhere (A/B runs)
+        # fp8 mode's feed-forward sub-option: "fp8" runs the feed-forwards that take the fused f16 kernel in fp8 mode (reduction
+        # not a multiple of 128: the C = 320 level, the tiny net's C = 64) on its e4m3 sibling (seva_ff_fused_fp8); with
+        # SEVA_FP8_PAD=1 it takes precedence over the padded two-kernel chain there.  Not given: SEVA_FP8_FF=0|1.
+        if ff is None:
+            ff = "fp8" if self.fp8 and _os.environ.get("SEVA_FP8_FF", "0") == "1" else "f16"
+        if ff not in ("f16", "fp8"):
+            raise ValueError(f"unknown ff {ff!r} (f16 | fp8)")
+        if ff == "fp8" and not self.fp8:
+            raise ValueError('ff="fp8" needs precision "fp8" (the f16 parity mode stays pure)')
+        self.ff = ff
+        self.ff8 = ff == "fp8"
         # GroupNorm statistics from the producers' epilogues: 0 off (separate statistics pass everywhere, A/B runs),
         # 1 where it pays (default), 2 wherever hw % 64 == 0, even on launches that would otherwise run 64-row tiles (tests)
         self.gn_fused_stats = int(_os.environ.get("SEVA_GN_FUSED_STATS", "1"))
@@ -153,6 +164,11 @@ class SevaEngine:
         self.slice_frames = int(os.environ.get("SEVA_SLICE_FRAMES", "0"))
         self.slice_min_bytes = int(float(os.environ.get("SEVA_SLICE_MIN_MB", "96")) * (1 << 20))
         self.slice_attn = os.environ.get("SEVA_SLICE_ATTN", "0") == "1"  # also slice LN -> QKV -> attention -> out-proj
+
+    def _ff_fused_fp8(self, c: int) -> bool:
+        """Does a feed-forward of width c run on seva_ff_fused_fp8?  Exactly those that reach the fused f16 kernel in fp8 mode
+        without SEVA_FP8_PAD (reduction not a multiple of 128), when the ff="fp8" option is on."""
+        return self.ff8 and self.ff_fused and c in ops.FF_FUSED_CHANNELS and c % 128 != 0
 
     def _split_skip(self, cout: int) -> bool:
         """Does the 1x1 skip conv of a ResBlock with `cout` output channels take its raw input in split precision?"""
@@ -220,7 +236,10 @@ class SevaEngine:
             wi, bi = interleave_geglu(f16(pfx + ".net.0.proj.weight"), f32(pfx + ".net.0.proj.bias"))
             W[pfx + ".w1"], W[pfx + ".b1"] = wi, bi
             W[pfx + ".w2"], W[pfx + ".b2"] = f16(pfx + ".net.2.weight"), f32(pfx + ".net.2.bias")
-            if self.fp8:  # both or neither: the hidden activations travel as e4m3
+            if self._ff_fused_fp8(wi.shape[1]):  # e4m3 copies for seva_ff_fused_fp8 (W1 zero-padded to KP, W2 column-permuted)
+                W[pfx + ".w1f8"], W[pfx + ".w1f8e"], W[pfx + ".w2f8"], W[pfx + ".w2f8e"] = ops.pack_ff_fp8(
+                    interleave_geglu(f32(pfx + ".net.0.proj.weight"), f32(pfx + ".net.0.proj.bias"))[0], f32(pfx + ".net.2.weight"))
+            elif self.fp8:  # both or neither: the hidden activations travel as e4m3
                 q8(pfx + ".w1", interleave_geglu(f32(pfx + ".net.0.proj.weight"), f32(pfx + ".net.0.proj.bias"))[0])
                 if pfx + ".w18" in W:
                     q8(pfx + ".w2", f32(pfx + ".net.2.weight"))
@@ -370,6 +389,12 @@ class SevaEngine:
     def _ff(self, x32, ln_pfx, ff_pfx, rows, c, *, residual, out_f32=None, out_f16=None, unit=1):
         """GEGLU feed-forward on LayerNorm(x32): reference transformer.py:18-34."""
         W = self.W
+        if ff_pfx + ".w1f8" in W:
+            # fp8 mode, ff="fp8": LayerNorm prologue -> e4m3, GEGLU and FF2 on the scaled fp8 MFMA in ONE kernel
+            ops.ff_fused_fp8(None, W[ff_pfx + ".w1f8"], W[ff_pfx + ".w1f8e"], W[ff_pfx + ".b1"], W[ff_pfx + ".w2f8"],
+                             W[ff_pfx + ".w2f8e"], W[ff_pfx + ".b2"], residual=residual, out_f32=out_f32, out_f16=out_f16,
+                             ln_x=x32, ln_gamma=W[ln_pfx + ".g"], ln_beta=W[ln_pfx + ".b"], ln_eps=1e-5)
+            return
         if ff_pfx + ".w18" in W:
             # fp8 chain: LayerNorm -> e4m3, GEGLU on the fp8 MFMA -> e4m3 hidden, FF2 on the fp8 MFMA (+ fp32 residual)
             a8 = self._ln(x32, ln_pfx, rows, c, fp8=True)

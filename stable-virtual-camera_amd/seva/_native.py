@@ -16,7 +16,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SEVA_HIP_LIB: A/B benchmarking of two builds of the same library (tools/); default = the in-tree build
 LIB_PATH = os.environ.get("SEVA_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libseva_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 PROF_CLASSES = 5
 PROF_NAMES = ("gemm", "conv", "attention", "norm", "elementwise")
 
@@ -50,6 +50,7 @@ class FfDesc(C.Structure):
         ("M", c_int64), ("lda", c_int64), ("ldr", c_int64), ("ldo32", c_int64), ("ldo16", c_int64),
         ("C", c_int32),
         ("ln_x", c_void_p), ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ldx", c_int64), ("ln_eps", c_float),
+        ("w1_exp", c_void_p), ("w2_exp", c_void_p),
     ]
 
 
@@ -86,6 +87,7 @@ SYMBOLS = {
     "seva_gemm_f16": (c_int, [POINTER(GemmDesc), c_void_p]),
     "seva_gemm_fp8": (c_int, [POINTER(GemmDesc), c_void_p]),
     "seva_ff_fused_f16": (c_int, [POINTER(FfDesc), c_void_p]),
+    "seva_ff_fused_fp8": (c_int, [POINTER(FfDesc), c_void_p]),
     "seva_attention_f16": (c_int, [POINTER(AttnDesc), c_void_p]),
     "seva_attn_v_fp8_size": (c_int, [c_int32, c_int32, c_int32, POINTER(c_int64), POINTER(c_int64)]),
     "seva_attn_quant_v_fp8": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p]),

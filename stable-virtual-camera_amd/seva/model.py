@@ -158,20 +158,28 @@ class Seva(nn.Module):
         if self._engine is None:
             from ._engine import SevaEngine
 
-            self._engine = SevaEngine(self, getattr(self, "_precision", None), getattr(self, "_attention", None))
+            self._engine = SevaEngine(self, getattr(self, "_precision", None), getattr(self, "_attention", None),
+                                      getattr(self, "_ff_precision", None))
         return self._engine
 
-    def set_precision(self, precision: str, attention: str | None = None) -> "Seva":
+    def set_precision(self, precision: str, attention: str | None = None, ff: str | None = None) -> "Seva":
         """"f16" (default, the parity mode) or "fp8" (BASELINE config 5: e4m3 operands on the fp8 MFMA where the reduction
         length allows; separate accuracy class).  Re-packs the weights on the next forward.
         attention (fp8 mode only): "f16" (default) or "fp8" -- the long self-attention launches (L >= 2048) with P and V in e4m3
-        (seva_attention_pv8), an accuracy class of its own; None leaves the choice to SEVA_FP8_ATTENTION (0 / 1, default 0)."""
+        (seva_attention_pv8), an accuracy class of its own; None leaves the choice to SEVA_FP8_ATTENTION (0 / 1, default 0).
+        ff (fp8 mode only): "f16" (default) or "fp8" -- the feed-forwards that run the fused f16 kernel in fp8 mode (the C = 320
+        level) on its e4m3 sibling (seva_ff_fused_fp8); None leaves the choice to SEVA_FP8_FF (0 / 1, default 0)."""
         if attention not in (None, "f16", "fp8"):
             raise ValueError(f"unknown attention {attention!r} (f16 | fp8)")
         if attention == "fp8" and precision != "fp8":
             raise ValueError('attention="fp8" needs precision "fp8" (the f16 parity mode stays pure)')
+        if ff not in (None, "f16", "fp8"):
+            raise ValueError(f"unknown ff {ff!r} (f16 | fp8)")
+        if ff == "fp8" and precision != "fp8":
+            raise ValueError('ff="fp8" needs precision "fp8" (the f16 parity mode stays pure)')
         self._precision = precision
         self._attention = attention
+        self._ff_precision = ff
         self._engine = None
         return self
 

@@ -172,6 +172,59 @@ def ff_fused(a: torch.Tensor | None, w1: torch.Tensor, b1: torch.Tensor, w2: tor
     check(_lib().seva_ff_fused_f16(C.byref(d), stream_ptr(src.device)), "seva_ff_fused_f16")
 
 
+FF8_STEP = 128  # hidden features per stage-2 k-step of the e4m3 fused feed-forward (csrc/ff_fp8.h)
+
+
+def ff8_feature_of(pos: torch.Tensor) -> torch.Tensor:
+    """Byte P of a 128-feature step of the stored W2 row holds hidden feature 64 c + 32 q + 8 g + r of that step, where
+    P = 64 q + 16 g + 8 c + r (csrc/ff_fp8.h: ff8_feature_of)."""
+    return 64 * ((pos >> 3) & 1) + 32 * (pos >> 6) + 8 * ((pos >> 4) & 3) + (pos & 7)
+
+
+def pack_ff_fp8(w1: torch.Tensor, w2: torch.Tensor):
+    """Weights of `ff_fused_fp8` from the fp32 / f16 ones: w1 [8C, C] in the interleaved GEGLU row order, w2 [C, 4C].
+    Returns (w1_8 [8C, KP] uint8 e4m3 with zero columns >= C, w1_exp [8C], w2_8 [C, 4C] uint8 with columns permuted into the
+    kernel's hidden-feature order, w2_exp [C]); KP = the multiple of 128 at or above C.  Row scales: quantize_weight_fp8."""
+    c = w1.shape[1]
+    assert w1.shape == (8 * c, c) and w2.shape == (c, 4 * c) and c in FF_FUSED_CHANNELS
+    kp = (c + 127) // 128 * 128
+    w1p = torch.cat([w1.float(), w1.new_zeros((8 * c, kp - c), dtype=torch.float32)], 1) if kp != c else w1.float()
+    w1_8, w1_exp = quantize_weight_fp8(w1p)
+    w2_8, w2_exp = quantize_weight_fp8(w2)
+    perm = (torch.arange(4 * c, device=w2.device) // FF8_STEP) * FF8_STEP + ff8_feature_of(torch.arange(4 * c, device=w2.device) % FF8_STEP)
+    return w1_8, w1_exp, w2_8[:, perm].contiguous(), w2_exp
+
+
+def ff_fused_fp8(a: torch.Tensor | None, w1: torch.Tensor, w1_exp: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+                 w2_exp: torch.Tensor, b2: torch.Tensor, *, residual: torch.Tensor | None = None,
+                 out_f32: torch.Tensor | None = None, out_f16: torch.Tensor | None = None, ln_x: torch.Tensor | None = None,
+                 ln_gamma: torch.Tensor | None = None, ln_beta: torch.Tensor | None = None, ln_eps: float = 1e-5) -> None:
+    """e4m3 sibling of `ff_fused` (seva_ff_fused_fp8): weights from `pack_ff_fp8`; a: [M, >= C] uint8 e4m3 bytes (row pitch a
+    multiple of 16), or ln_x ([M, C] f32) for the LayerNorm prologue, whose normalised row is rounded once to e4m3.  The hidden
+    activations are rounded once to e4m3; fp32 accumulation.  Allocates nothing (graph-capture safe)."""
+    src = ln_x if ln_x is not None else a
+    require_cuda(src, w1, w2)
+    M = src.shape[0]
+    c = w2.shape[0]
+    kp = (c + 127) // 128 * 128
+    assert (ln_x is not None and ln_x.dtype == F32 and ln_x.shape[1] == c and ln_gamma is not None and ln_beta is not None) or \
+        (a is not None and a.dtype == U8 and a.shape[1] >= c and a.stride(1) == 1)
+    assert w1.dtype == U8 and w2.dtype == U8 and w1.shape == (8 * c, kp) and w2.shape == (c, 4 * c)
+    assert w1_exp.dtype == U8 and w2_exp.dtype == U8 and w1_exp.numel() == 8 * c and w2_exp.numel() == c
+    assert w1.is_contiguous() and w2.is_contiguous() and c in FF_FUSED_CHANNELS
+    d = nv.FfDesc()
+    d.a, d.w1, d.b1, d.w2, d.b2 = ptr(a) if ln_x is None else None, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
+    d.w1_exp, d.w2_exp = w1_exp.data_ptr(), w2_exp.data_ptr()
+    if ln_x is not None:
+        d.ln_x, d.ln_gamma, d.ln_beta, d.ldx, d.ln_eps = ln_x.data_ptr(), ln_gamma.data_ptr(), ln_beta.data_ptr(), ln_x.stride(0), ln_eps
+    d.residual, d.out_f32, d.out_f16 = ptr(residual), ptr(out_f32), ptr(out_f16)
+    d.M, d.lda, d.C = M, (a.stride(0) if ln_x is None else 0), c
+    d.ldr = residual.stride(0) if residual is not None else 0
+    d.ldo32 = out_f32.stride(0) if out_f32 is not None else 0
+    d.ldo16 = out_f16.stride(0) if out_f16 is not None else 0
+    check(_lib().seva_ff_fused_fp8(C.byref(d), stream_ptr(src.device)), "seva_ff_fused_fp8")
+
+
 def conv3x3(
     x: torch.Tensor,
     w: torch.Tensor,
