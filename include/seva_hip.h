@@ -49,6 +49,18 @@ const char* seva_target_arch(void);
  * mode 1 (conv3x3, pad 1): A is an NHWC f16 image [n][ih][iw][cin]; K = 9*cin ordered
  *   (ky, kx, ci); M = n*oh*ow.  `stride` is 1 or 2.  `upsample`=1 applies the conv to the
  *   nearest-neighbour 2x upsampling of A without materialising it (oh = 2*ih).
+ *   `upsample`=2 (seva_gemm_f16 only) is the same operator PHASE-DECOMPOSED: after a nearest-2x upsample, output rows 2i and
+ *   2i + 1 read source rows {i-1, i, i} and {i, i, i+1} (columns alike), so every output phase (py, px) is a 2x2 conv on the
+ *   source image with tap (a, b) at source offset (a + py - 1, b + px - 1): 4 taps instead of 9.  `w` is then f16
+ *   [4 phases 2*py+px][N][4*cin], K ordered (a, b, ci), each entry the sum of the 3x3 weights that meet on that source
+ *   pixel (py = 0: a = 0 <- W[0], a = 1 <- W[1] + W[2]; py = 1: a = 0 <- W[0] + W[1], a = 1 <- W[2]; columns alike), summed
+ *   by the caller BEFORE the one rounding to f16.  K = 4*cin per phase, oh = 2*ih, ow = 2*iw, M = n*oh*ow; output row of
+ *   source pixel (i, j) of image g and phase (py, px): g*oh*ow + (2i + py)*ow + 2j + px.  Runs on the window-staged kernel
+ *   only, with bias + out_f32 and nothing else: residual, row_add, out_f16, out_f8, a2, splitk_ws, ch_stats, col_scale,
+ *   seva_gemm_fp8, N % 160 != 0, or an image whose tiles do not fit the window (or conv_win knob 0) are an ERROR, never a
+ *   fall-back -- no other kernel reads this weight layout.  alg_K may be 9*cin (the reference-equivalent reduction).  The
+ *   result differs from `upsample`=1 by one f16 weight rounding (two draws of the same noise).  No new symbol and no change
+ *   to the struct: the ABI version is unchanged.
  * epilogue 0: linear.  epilogue 1 (GEGLU): W rows are interleaved in groups of 64 as
  *   [32 value rows | 32 gate rows] (same for bias); output has N/2 columns:
  *   out[m][f] = (v + bv) * gelu_erf(g + bg).

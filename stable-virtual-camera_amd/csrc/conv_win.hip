@@ -70,12 +70,22 @@ struct ConvWinGeom {
 //   linear tiles: the padded index space with bottom / right frame cells only (P(m) = img * Sp + 2y Wp + 2x, Wp = iw + 1 rounded up to even so
 //              that parity of P is parity of the column), split over the tile's window: even indices in slots [0, HALF), odd ones behind
 //              (RP = Wp / 2, HALF = half the tile's window, a workgroup-uniform scalar).
-template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false, bool S2 = false>
+//
+// PH (seva_gemm_desc.upsample = 2; the three Upsample convs of a step): the nearest-2x upsample + 3x3 conv as FOUR 2x2 convs on the source
+// image.  Output rows 2i and 2i + 1 read source rows {i-1, i, i} and {i, i, i+1}: the weight rows that meet on one source row are added on the
+// host, columns alike, so output phase (py, px) is a 2x2 conv whose tap (a, b) sits at source offset (a + py - 1, b + px - 1) -- 4 taps and
+// 4/9 of the FLOPs.  A workgroup computes ONE phase of a tile of consecutive SOURCE pixels: it is the plain kernel (same window, same
+// fragment addresses) restricted to the taps (ky, kx) = (a + py, b + px), with the phase's own [N][4 cin] weight matrix and an epilogue
+// that scatters source pixel (i, j) to output pixel (2i + py, 2j + px).  The four phases of a tile are neighbours in the remapped order
+// (they stage the same window).  Plain fp32 epilogue with bias only; M, hw, ow of the arguments describe the SOURCE image.
+template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false, bool S2 = false, bool PH = false>
 __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWinGeom g) {
   constexpr bool T2D = TW > 0;
   static_assert(TW == 0 || TW == 16, "2-D tiles are 16 output columns wide: an MFMA block is a tile row");
   static_assert(!O8 || FP8, "the e4m3 output epilogue belongs to the e4m3 instantiations");
   static_assert(!S2 || (FP8 && !UP && !O8), "stride 2: e4m3, no upsample, no e4m3 output (the encoder's downsample convs)");
+  static_assert(!PH || (!UP && TW == 0 && !FP8 && !S2 && !STATS), "phase mode: f16, linear tiles, no statistics");
+  constexpr int NT = PH ? 4 : 9;                               // taps per slab
   constexpr int TH = BM / 16;                                  // output rows of a 2-D tile
   constexpr int SW2 = UP ? 8 : 16, SH2 = UP ? TH / 2 : TH;     // its source extent; window = (SH2 + 2) x (SW2 + 2) pixels
   constexpr int PITCH2 = S2 ? 33 : SW2 + 2, WL2 = S2 ? (2 * TH + 1) * 33 : (SH2 + 2) * PITCH2;
@@ -103,7 +113,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
   const int sr = lane >> 3, sp = lane & 7;
   const int fr = lane & 15, fg = lane >> 4;
 
-  const int work = xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n);
+  const int work_ph = xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n * (PH ? 4 : 1));
+  const int ph = PH ? work_ph & 3 : 0, work = PH ? work_ph >> 2 : work_ph;  // PH: phase 2 py + px, the four of a tile side by side
   const int tm = work / g.tiles_n, tn = work - tm * g.tiles_n;  // sibling N-tiles of an M-tile are neighbours on one XCD
   // rows [m0, m_end) of the [M][N] output belong to this tile (2-D tiles: BM rows of ONE image that are not consecutive; see row_m)
   uint32_t m0, m_end;
@@ -224,7 +235,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
     const int q = sp ^ ((row >> 1) & 7);
     int64_t n = n0 + row;
     if (n >= p.N) n = p.N - 1;
-    b_ptr[i] = p.w + n * p.K + q * 8;
+    b_ptr[i] = p.w + (PH ? (int64_t)ph * p.N * p.K : (int64_t)0) + n * p.K + q * 8;
   }
   auto stage_w = [&](int buf, int kcol) {
 #pragma unroll
@@ -291,7 +302,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
   }
 
   f32x4 acc[MI][NJ];
-  if (p.residual) {  // the residual tile goes straight into the accumulators (clamped addresses; stores are guarded)
+  if (!PH && p.residual) {  // the residual tile goes straight into the accumulators (clamped addresses; stores are guarded)
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
       int64_t m = row_m(i);
@@ -329,14 +340,19 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
     const char* const win = lds_win + (DBW ? (s & 1) * WIN_BYTES : 0);
     const bool more = s + 1 < nslab;
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      if (t < 8) stage_w(cur ^ 1, (t + 1) * p.cin + BK * s);
+    for (int t = 0; t < NT; ++t) {
+      if (t < NT - 1) stage_w(cur ^ 1, (t + 1) * p.cin + BK * s);
       else if (more) stage_w(cur ^ 1, BK * (s + 1));
-      if constexpr (DBW) {  // the next slab's window, one piece per wave and tap, into the other buffer
+      if constexpr (DBW && !PH) {  // the next slab's window, one piece per wave and tap, into the other buffer
         if (more && t < PPW) fill_piece(t, s + 1, (s + 1) & 1);
       }
+      if constexpr (DBW && PH) {  // four taps: two pieces per wave and tap
+        static_assert(!PH || PPW <= 2 * NT, "phase mode: two window pieces per wave and tap");
+        if (more && 2 * t < PPW) fill_piece(2 * t, s + 1, (s + 1) & 1);
+        if (more && 2 * t + 1 < PPW) fill_piece(2 * t + 1, s + 1, (s + 1) & 1);
+      }
       const char* const tb = lds_b + cur * B_BYTES;
-      int toff = S2 ? (t / 3) * (T2D ? 33 : g.Wp >> 1) + ((t % 3) & 1) * s2_half + ((t % 3) >> 1) : UP ? 0 : (t / 3) * pitch + (t % 3);
+      int toff = S2 ? (t / 3) * (T2D ? 33 : g.Wp >> 1) + ((t % 3) & 1) * s2_half + ((t % 3) >> 1) : UP ? 0 : PH ? ((t >> 1) + (ph >> 1)) * pitch + (t & 1) + (ph & 1) : (t / 3) * pitch + (t % 3);
       asm volatile("" : "+s"(toff));  // opaque: the nine taps' fragment addresses are formed here, not hoisted out of the slab loop (45 registers)
       // fragment reads + MFMAs of the tap.  FIRST: every fragment read is ISSUED before the first MFMA (hipcc otherwise re-uses one
       // register quad for the second k-step's window fragments and waits for each read right in front of the five MFMAs that need it:
@@ -392,7 +408,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
           for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(acc[i][j]));
       }
       if constexpr (!DBW) {
-        if (t == 8 && more) {  // every wave has read the last tap's fragments: the window is free for the next slab
+        if (t == NT - 1 && more) {  // every wave has read the last tap's fragments: the window is free for the next slab
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
@@ -420,10 +436,16 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
   for (int i = 0; i < MI; ++i) {
     const int64_t m = row_m(i);
     const int64_t mc = m < m_end ? m : m_end - 1;
+    int64_t mo = m;  // output row; PH: source pixel (img, i, j) -> output pixel (img, 2i + py, 2j + px)
+    if constexpr (PH) {
+      const uint32_t img = __umulhi((uint32_t)mc, g.mul_hw), rem = (uint32_t)mc - img * (uint32_t)g.hw;
+      const uint32_t yi = __umulhi(rem, g.mul_iw), xj = rem - yi * (uint32_t)g.ow;
+      mo = (int64_t)img * (4 * g.hw) + (int64_t)(2 * yi + (uint32_t)(ph >> 1)) * (2 * g.ow) + 2 * xj + (uint32_t)(ph & 1);
+    }
     f32x4 v[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) v[j] = acc[i][j] + bj[j];
-    if (p.row_add) {
+    if (!PH && p.row_add) {
       const float* rp = p.row_add + (mc / p.rows_per_group) * p.ldra;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) v[j] += first_read(*(const f32x4*)(rp + fj[j]));
@@ -437,8 +459,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
     for (int j = 0; j < NJ; ++j) {
       const int64_t f = n0 + wn * WN + 16 * j + 4 * fg;
       if (!row_ok || f >= p.N) continue;
-      if (p.out_f32) *(f32x4*)(p.out_f32 + m * p.ldo32 + f) = v[j];
-      if (p.out_f16) {
+      if (p.out_f32) *(f32x4*)(p.out_f32 + mo * p.ldo32 + f) = v[j];
+      if (!PH && p.out_f16) {
         half4_t h = {(half_t)v[j][0], (half_t)v[j][1], (half_t)v[j][2], (half_t)v[j][3]};
         *(half4_t*)(p.out_f16 + m * p.ldo16 + f) = h;
       }
@@ -494,7 +516,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
 
 uint32_t magic_u32(uint32_t d) { return (uint32_t)(0x100000000ull / d) + 1u; }
 
-template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false, bool S2 = false>
+template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false, bool S2 = false, bool PH = false>
 int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
   constexpr int lds = (DBW ? 2 : 1) * WCAP * 128 + 2 * BN * 128;
   static_assert(lds <= 160 * 1024, "LDS per workgroup");
@@ -503,18 +525,18 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
   (void)hipGetDevice(&dev);
   const uint64_t dev_bit = 1ull << (dev & 63);
   if (!(attr_devs.load(std::memory_order_relaxed) & dev_bit)) {
-    (void)hipFuncSetAttribute((const void*)conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_devs.fetch_or(dev_bit, std::memory_order_relaxed);
   }
   ConvWinGeom g = g0;
   g.tiles_n = (int)((a.N + BN - 1) / BN);
   const auto go = [&](const GemmArgs& c, const ConvWinGeom& gc) {
-    const int64_t nb = (int64_t)gc.tiles_m * gc.tiles_n;
+    const int64_t nb = (int64_t)gc.tiles_m * gc.tiles_n * (PH ? 4 : 1);  // PH: one workgroup per tile and phase
     if (nb <= 0 || nb > 0x7fffffff) {
       seva_set_error("conv_win: bad grid %lld", (long long)nb);
       return SEVA_ERR_ARG;
     }
-    hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2>), dim3((unsigned)nb), dim3(64 * NW), lds, s, c, gc);
+    hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH>), dim3((unsigned)nb), dim3(64 * NW), lds, s, c, gc);
     return seva_check_launch("conv_win_kernel");
   };
   if constexpr (TW > 0) {
@@ -564,7 +586,7 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
     c.M = (int64_t)nc * g.hw;
     c.a = a.a + i0 * a.ih * a.iw * a.cin;
     if (c.residual) c.residual += r0 * a.ldr;
-    if (c.out_f32) c.out_f32 += r0 * a.ldo32;
+    if (c.out_f32) c.out_f32 += r0 * (PH ? 4 : 1) * a.ldo32;  // (PH: r0 counts source pixels, four output rows each)
     if (c.out_f16) c.out_f16 += r0 * a.ldo16;
     if (c.out_f8) c.out_f8 += r0 * a.ldo8;
     if (c.row_add) c.row_add += (r0 / a.rows_per_group) * a.ldra;
@@ -588,21 +610,11 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
 
 }  // namespace
 
-// 0 = launched, 1 = not applicable (the caller uses the per-tap gather of gemm.hip), < 0 = error
-int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
-  const int knob = g_seva_knobs.conv_win;
-  if (knob == 0) return 1;
-  // e4m3 stride 2 with bottom / right padding only (the VAE encoder's Downsample2D convs in its fp8 mode); the UNet's stride-2 convs (pad 1)
-  // and every f16 stride-2 conv keep the per-tap gather
-  const bool s2 = fp8 && a.stride == 2 && a.pad_lo == 0 && !a.upsample;
-  if (!s2 && (a.stride != 1 || a.pad_lo != 1)) return 1;
-  if (a.a2 != nullptr || a.sk_ws != nullptr) return 1;
-  const int up = a.upsample ? 2 : 1;
-  if (!s2 && (a.oh != up * a.ih || a.ow != up * a.iw)) return 1;  // (S2: oh = (ih - 2) / 2 + 1, checked by gemm.hip)
-  if (a.iw < 2 || a.ih < 2) return 1;
-  const bool narrow = a.N <= 32 && a.N % 4 == 0;  // the UNet's head (4 channels), the VAE's conv_out
-  if (a.cin % 64 != 0 || (a.N % 160 != 0 && a.N % 128 != 0 && !narrow) || a.K != 9LL * a.cin) return 1;
-  ConvWinGeom g{};
+namespace {
+// Geometry of a launch from its arguments (a.oh / a.ow: the image the kernel's M rows index; the phase mode passes the source image there).
+// 0 = ok, 1 = the window kernel does not apply
+int win_geometry(const GemmArgs& a, bool s2, ConvWinGeom& g) {
+  g = ConvWinGeom{};
   g.Wp = a.iw + 1;             // padded SOURCE space (UP: the image before the nearest-2x upsample)
   if (s2) g.Wp += g.Wp & 1;    // S2: frame columns on the right only, as many as make the row pitch even (parity of P = parity of x)
   g.Sp = (a.ih + 1) * g.Wp;
@@ -639,6 +651,38 @@ int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
   g.mul_iw = magic_u32((uint32_t)g.ow);
   g.mul_sp = magic_u32((uint32_t)g.Sp);
   g.mul_wp = magic_u32((uint32_t)g.Wp);
+  return 0;
+}
+
+// Which of the two bitwise-equal 160-column families a launch of M rows x N columns (x `mult` workgroups per tile) takes, from how it
+// quantises: see seva_conv_win_launch.  rows4: tile height of the 4-wave family
+bool eight_waves_quantise_better(int64_t M, int64_t N, int rows4, int mult) {
+  const double tn = (double)((N + 159) / 160) * mult;
+  const double t8 = (double)((M + 255) / 256) * tn, t4 = (double)((M + rows4 - 1) / rows4) * tn;
+  const double r8 = t8 / 256.0, r4 = t4 / 512.0;
+  const double f4 = r4 - (double)(int64_t)r4;
+  const double tail4 = f4 > 0.0 ? (f4 <= 0.5 ? 0.55 : 0.55 + 0.9 * (f4 - 0.5)) : 0.0;  // a partly filled round of 4-wave workgroups runs one per CU
+  const double cost8 = 0.95 * (double)(int64_t)(r8 + 0.999999) / r8, cost4 = ((double)(int64_t)r4 + tail4) / r4;
+  return t8 >= 256.0 && cost8 < cost4;
+}
+}  // namespace
+
+// 0 = launched, 1 = not applicable (the caller uses the per-tap gather of gemm.hip), < 0 = error
+int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
+  const int knob = g_seva_knobs.conv_win;
+  if (knob == 0) return 1;
+  // e4m3 stride 2 with bottom / right padding only (the VAE encoder's Downsample2D convs in its fp8 mode); the UNet's stride-2 convs (pad 1)
+  // and every f16 stride-2 conv keep the per-tap gather
+  const bool s2 = fp8 && a.stride == 2 && a.pad_lo == 0 && !a.upsample;
+  if (!s2 && (a.stride != 1 || a.pad_lo != 1)) return 1;
+  if (a.a2 != nullptr || a.sk_ws != nullptr) return 1;
+  const int up = a.upsample ? 2 : 1;
+  if (!s2 && (a.oh != up * a.ih || a.ow != up * a.iw)) return 1;  // (S2: oh = (ih - 2) / 2 + 1, checked by gemm.hip)
+  if (a.iw < 2 || a.ih < 2) return 1;
+  const bool narrow = a.N <= 32 && a.N % 4 == 0;  // the UNet's head (4 channels), the VAE's conv_out
+  if (a.cin % 64 != 0 || (a.N % 160 != 0 && a.N % 128 != 0 && !narrow) || a.K != 9LL * a.cin) return 1;
+  ConvWinGeom g;
+  if (win_geometry(a, s2, g) != 0) return 1;
   const bool stats = a.ch_stats != nullptr;
   if (fp8) {
     // e4m3 operands (the C >= 640 levels in fp8 mode): 128-column tiles only (with 160 columns the 8-register operand tuples of the scaled
@@ -724,15 +768,32 @@ int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
   if (knob == 1 || knob == 2) {
     eight = knob == 2;
   } else {
-    const double tn = (double)((a.N + 159) / 160);
-    const double t8 = (double)((a.M + 255) / 256) * tn, t4 = (double)((a.M + (stats ? 127 : 159)) / (stats ? 128 : 160)) * tn;
-    const double r8 = t8 / 256.0, r4 = t4 / 512.0;
-    const double f4 = r4 - (double)(int64_t)r4;
-    const double tail4 = f4 > 0.0 ? (f4 <= 0.5 ? 0.55 : 0.55 + 0.9 * (f4 - 0.5)) : 0.0;  // a partly filled round of 4-wave workgroups runs one per CU
-    const double cost8 = 0.95 * (double)(int64_t)(r8 + 0.999999) / r8, cost4 = ((double)(int64_t)r4 + tail4) / r4;
-    eight = t8 >= 256.0 && cost8 < cost4;
+    eight = eight_waves_quantise_better(a.M, a.N, stats ? 128 : 160, 1);
   }
   int rc = eight ? launch8() : launch4();
   if (rc == 1) rc = eight ? launch4() : launch8();  // the other family may still fit (window capacity is per family)
+  return rc;
+}
+
+// seva_gemm_desc.upsample = 2: the nearest-2x upsample + 3x3 conv as four 2x2 phase convs on the source image (see PH above).  `a` holds the
+// conv as the caller states it (oh = 2 ih, ow = 2 iw, K = 4 cin, w = [4][N][4 cin]); gemm.hip has refused every epilogue but bias + out_f32.
+// 0 = launched, 1 = the window kernel does not apply (an ERROR for the caller: no other kernel reads this weight layout), < 0 = error
+int seva_conv_win_phases_launch(const GemmArgs& a0, hipStream_t s) {
+  const int knob = g_seva_knobs.conv_win;
+  if (knob == 0) return 1;
+  if (a0.stride != 1 || a0.pad_lo != 1 || a0.oh != 2 * a0.ih || a0.ow != 2 * a0.iw || a0.iw < 2 || a0.ih < 2) return 1;
+  if (a0.cin % 64 != 0 || a0.N % 160 != 0 || a0.K != 4LL * a0.cin) return 1;
+  GemmArgs a = a0;  // the kernel's view: a plain conv over the SOURCE image, one launch row per source pixel
+  a.oh = a0.ih;
+  a.ow = a0.iw;
+  a.M = (int64_t)a0.n * a0.ih * a0.iw;
+  ConvWinGeom g;
+  if (win_geometry(a, false, g) != 0) return 1;
+  // the plain conv's two families, bitwise equal (same reduction order), chosen by the same quantisation rule with four workgroups per tile
+  const auto launch4 = [&]() { return launch_win<160, 160, 4, 320, false, false, false, 0, false, false, false, true>(a, g, s); };
+  const auto launch8 = [&]() { return launch_win<256, 160, 8, 416, true, false, false, 0, false, false, false, true>(a, g, s); };
+  const bool eight = knob == 1 || knob == 2 ? knob == 2 : eight_waves_quantise_better(a.M, a.N, 160, 4);
+  int rc = eight ? launch8() : launch4();
+  if (rc == 1) rc = eight ? launch4() : launch8();
   return rc;
 }

@@ -959,9 +959,21 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
                "gemm: col_scale needs mode 0 (no convolution) and the plain epilogue without residual / row_add");
   a.ldra = d->ld_row_add > 0 ? d->ld_row_add : d->N;
   SEVA_REQUIRE(a.ldra % 4 == 0, "gemm: ld_row_add must be a multiple of 4");
+  // upsample = 2: the fused nearest-2x upsample as four 2x2 phase convs on the source image (conv_win.hip: PH); w = [4][N][4 cin]
+  const bool phases = d->mode == 1 && d->upsample == 2;
+  SEVA_REQUIRE(d->mode != 1 || (d->upsample >= 0 && d->upsample <= 2), "conv: upsample=%d (0, 1 or 2)", d->upsample);
+  if (phases) {
+    // no other kernel reads this weight layout, so everything the phase family does not do is an error, never a fall-back
+    SEVA_REQUIRE(!FP8, "conv: the phase-decomposed upsample (upsample = 2) is an f16 operator");
+    SEVA_REQUIRE(d->out_f32 && !d->out_f16 && !d->residual && !d->row_add && !d->a2 && !d->splitk_ws && !d->ch_stats && d->col_scale_n == 0,
+                 "conv: the phase-decomposed upsample (upsample = 2) has the bias + out_f32 epilogue only (no residual, row_add, out_f16, "
+                 "a2, splitk_ws, ch_stats, col_scale)");
+    SEVA_REQUIRE(d->N % 160 == 0 && d->K == 4LL * d->cin, "conv: the phase-decomposed upsample needs N %% 160 == 0 and K = 4 * cin per phase "
+                 "(N=%lld K=%lld cin=%d)", (long long)d->N, (long long)d->K, d->cin);
+  }
   if (d->mode == 1) {
     SEVA_REQUIRE(d->cin > 0 && d->cin % (64 * KU) == 0, "conv: cin=%d not a multiple of %d", d->cin, 64 * KU);
-    SEVA_REQUIRE(d->K == 9LL * d->cin + (d->a2 ? d->K2 : 0), "conv: K=%lld != 9*cin (+ K2)", (long long)d->K);
+    SEVA_REQUIRE(phases || d->K == 9LL * d->cin + (d->a2 ? d->K2 : 0), "conv: K=%lld != 9*cin (+ K2)", (long long)d->K);
     if (d->a2) {
       SEVA_REQUIRE(!FP8 && !d->upsample && d->K2 > 0 && d->K2 % 64 == 0 && d->lda2 >= d->K2 && d->lda2 % 8 == 0 &&
                        (uintptr_t)d->a2 % 16 == 0 && d->N > 32 && d->out_f32,
@@ -986,17 +998,25 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
     SEVA_REQUIRE(d->lda >= d->K && d->lda % (8 * KU) == 0, "gemm: lda=%lld invalid", (long long)d->lda);
   }
   hipStream_t s = (hipStream_t)stream;
-  SEVA_REQUIRE(d->alg_K >= 0 && d->alg_K <= d->K, "gemm: alg_K=%lld outside [0, K]", (long long)d->alg_K);
+  // (phases: the reference-equivalent reduction is the nine taps, longer than the executed four)
+  SEVA_REQUIRE(d->alg_K >= 0 && d->alg_K <= (phases ? 9LL * d->cin : d->K), "gemm: alg_K=%lld outside [0, K]", (long long)d->alg_K);
   const double flops = 2.0 * (double)d->M * (double)d->N * (double)(d->alg_K > 0 ? d->alg_K : d->K);  // reference-equivalent FLOP (seva_hip.h)
   // algorithmic HBM bytes: A (conv: the NHWC image) and W read once, residual read once, each output written once
   const double a_elems = (d->mode == 1 ? (double)d->n * d->ih * d->iw * d->cin : (double)d->M * (double)d->K);
   const double a2_bytes = (d->mode == 1 && d->a2) ? 2.0 * (double)d->M * (double)d->K2 : 0.0;
   const double n_out = d->epilogue == 1 ? (double)d->N / 2 : (double)d->N;
   const double esz = FP8 ? 1.0 : 2.0;
-  const double alg_bytes = esz * a_elems + a2_bytes + esz * (double)d->N * (double)d->K + (d->bias ? 4.0 * (double)d->N : 0.0) +
+  const double alg_bytes = esz * a_elems + a2_bytes + esz * (double)d->N * (double)d->K * (phases ? 4.0 : 1.0) + (d->bias ? 4.0 * (double)d->N : 0.0) +
                            (double)d->M * n_out * ((d->residual ? 4.0 : 0.0) + (d->out_f32 ? 4.0 : 0.0) +
                                                    (d->out_f16 ? 2.0 : 0.0) + (d->out_f8 ? 1.0 : 0.0));
   SevaProfScope prof(d->mode == 1 ? 1 : 0, flops, s, alg_bytes);
+  if (phases) {
+    SEVA_REQUIRE(d->epilogue == 0, "conv: the phase-decomposed upsample has the plain epilogue only");
+    const int rc = seva_conv_win_phases_launch(a, s);
+    SEVA_REQUIRE(rc != 1, "conv: the phase-decomposed upsample runs on the window kernel only, which declined it (image %dx%d, cin %d, N %lld: "
+                 "stride 1, pad 1, one image's tiles must fit the window; conv_win knob not 0)", d->ih, d->iw, d->cin, (long long)d->N);
+    return rc;
+  }
   if (d->epilogue == 1) {
     SEVA_REQUIRE(d->N % 64 == 0, "geglu: N=%lld not a multiple of 64", (long long)d->N);
     SEVA_REQUIRE(d->mode == 0, "geglu: plain mode only");

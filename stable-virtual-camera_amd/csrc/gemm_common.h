@@ -128,3 +128,5 @@ static __device__ __forceinline__ f32x4 mfma_f8(int j, half8_t w_lo, half8_t w_h
 
 
 int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8 = false);
+// seva_gemm_desc.upsample = 2 (four 2x2 phase convs on the source image; f16, bias + out_f32 only).  1 = declined: an error for the caller
+int seva_conv_win_phases_launch(const GemmArgs& a, hipStream_t s);

@@ -23,6 +23,7 @@ Exact algebraic rewrites (each checked against the oracle in tests/):
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 
@@ -48,6 +49,29 @@ def pack_conv3x3(w: torch.Tensor, cin_pad: int | None = None) -> torch.Tensor:
     out = torch.zeros((cout, 3, 3, cin_pad), dtype=F16, device=w.device)
     out[..., :cin] = w.permute(0, 2, 3, 1).to(F16)
     return out.reshape(cout, 9 * cin_pad).contiguous()
+
+
+def combine_up_phases(w: torch.Tensor, dtype: torch.dtype = F16) -> torch.Tensor:
+    """[cout, cin, 3, 3] fp32 -> f16 [4, cout, 4*cin]: the weights of `ops.conv3x3_up_phases`.  After a nearest-2x upsample, output
+    row 2i + py reads source rows {i-1, i, i} (py = 0) or {i, i, i+1} (py = 1), columns alike, so output phase (py, px) is a 2x2 conv
+    on the source image whose tap (a, b) sits at source offset (a + py - 1, b + px - 1) and carries the sum of the 3x3 weights that
+    meet there:
+
+        py = 0:  a = 0 <- W[0]         a = 1 <- W[1] + W[2]
+        py = 1:  a = 0 <- W[0] + W[1]  a = 1 <- W[2]
+
+    Summed in fp64 from the fp32 weights and rounded to f16 ONCE (summing f16-rounded weights would round twice).  Phase
+    2 py + px, K ordered (a, b, ci).  (`dtype`: the tests look at the sums before the rounding.)"""
+    fold = ((0,), (1, 2)), ((0, 1), (2,))  # fold[p][a]: the 3x3 rows (columns) that meet on tap a of phase p
+    w64 = w.double()
+    cout, cin = w.shape[:2]
+    out = torch.empty((4, cout, 2, 2, cin), dtype=dtype, device=w.device)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for b in range(2):
+                    out[2 * py + px, :, a, b] = w64[:, :, list(fold[py][a])][:, :, :, list(fold[px][b])].sum((2, 3)).to(dtype)
+    return out.reshape(4, cout, 4 * cin).contiguous()
 
 
 def interleave_geglu(w: torch.Tensor, b: torch.Tensor):
@@ -305,6 +329,7 @@ class SevaEngine:
                 W[pfx + ".w"], W[pfx + ".b"] = pack_conv3x3(f32(pfx + ".op.weight")), f32(pfx + ".op.bias")
             elif spec.kind == "up":
                 W[pfx + ".w"], W[pfx + ".b"] = pack_conv3x3(f32(pfx + ".conv.weight")), f32(pfx + ".conv.bias")
+                W[pfx + ".w4"] = combine_up_phases(f32(pfx + ".conv.weight"))  # ops.conv3x3_up_phases (_resample)
         pack_ln("out.0")
         wh = f32("out.2.weight")
         W["out.2.w"] = pack_conv3x3(torch.cat([wh, wh], 1) if "head" in self.split else wh)  # head input [hi | lo] per tap
@@ -637,9 +662,16 @@ class SevaEngine:
         else:
             oh, ow = 2 * h, 2 * w
             out = self._buf("out:" + spec.prefix, (n, oh * ow, c), F32)
-            st_out = self._stats_buf("out:" + spec.prefix, n * oh * ow, oh * ow, c)
-            ops.conv3x3(x16, self.W[spec.prefix + ".w"], upsample=True, bias=self.W[spec.prefix + ".b"], out_f32=out,
-                        ch_stats=st_out)
+            phases = getattr(ops, "conv3x3_up_phases", None)
+            if phases is not None and c % 160 == 0 and os.environ.get("SEVA_UPSAMPLE_PHASES", "1") != "0":
+                # four 2x2 phase convs on the source image: 4/9 of the FLOPs.  The path emits no statistics (a 64-row block of one
+                # phase is not image-aligned), so the consuming GroupNorm runs its own pass over this tensor
+                st_out = None
+                phases(x16, self.W[spec.prefix + ".w4"], bias=self.W[spec.prefix + ".b"], out_f32=out, ch_stats=None, alg_k=9 * c)
+            else:
+                st_out = self._stats_buf("out:" + spec.prefix, n * oh * ow, oh * ow, c)
+                ops.conv3x3(x16, self.W[spec.prefix + ".w"], upsample=True, bias=self.W[spec.prefix + ".b"], out_f32=out,
+                            ch_stats=st_out)
         self._produced(out, st_out)
         return out, oh, ow
 

@@ -300,6 +300,34 @@ def conv3x3(
         check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), "seva_gemm_f16(conv)")
 
 
+def conv3x3_up_phases(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tensor | None = None, out_f32: torch.Tensor | None = None,
+                      ch_stats: torch.Tensor | None = None, alg_k: int = 0) -> None:
+    """Nearest-2x upsample + 3x3 pad-1 conv as four 2x2 phase convs on the source image (seva_gemm_desc.upsample = 2): 4/9 of the
+    FLOPs of `conv3x3(upsample=True)`.  x: [n, ih, iw, cin] f16 NHWC; w4: [4, cout, 4*cin] f16, phase 2 py + px, K ordered
+    (a, b, ci): the 3x3 weights that meet on one source pixel, summed (the engine's `combine_up_phases`); out_f32: [n, 2 ih * 2 iw,
+    cout].  bias + out_f32 only, cout % 160 == 0.  The path emits no GroupNorm statistics: `ch_stats` must be None (the keyword
+    names what the caller has to leave to the consumer's own statistics pass).  alg_k: reduction length the profiler credits
+    (9 * cin: the reference operator).  Raises where the window kernel declines: no other kernel reads this weight layout."""
+    require_cuda(x, w4)
+    assert x.dtype == w4.dtype == F16 and x.dim() == 4 and x.is_contiguous() and w4.is_contiguous()
+    n, ih, iw, cin = x.shape
+    assert w4.dim() == 3 and w4.shape[0] == 4 and w4.shape[2] == 4 * cin, "w4: [4, cout, 4 * cin]"
+    if ch_stats is not None:
+        raise ValueError("conv3x3_up_phases emits no GroupNorm statistics (ch_stats must be None)")
+    if out_f32 is None:
+        raise ValueError("conv3x3_up_phases needs out_f32")
+    oh, ow = 2 * ih, 2 * iw
+    d = GemmDesc()
+    d.a, d.w, d.bias, d.out_f32 = x.data_ptr(), w4.data_ptr(), ptr(bias), out_f32.data_ptr()
+    d.M, d.N, d.K = n * oh * ow, w4.shape[1], 4 * cin
+    d.alg_K = alg_k
+    d.lda, d.ldo32 = cin, out_f32.stride(-2)
+    d.mode, d.epilogue = 1, 0
+    d.n, d.ih, d.iw, d.cin, d.oh, d.ow = n, ih, iw, cin, oh, ow
+    d.stride, d.upsample = 1, 2
+    check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), "seva_gemm_f16(conv, upsample phases)")
+
+
 def attention(
     q: torch.Tensor,
     k: torch.Tensor,
