@@ -61,6 +61,16 @@ const char* seva_target_arch(void);
  *   fall-back -- no other kernel reads this weight layout.  alg_K may be 9*cin (the reference-equivalent reduction).  The
  *   result differs from `upsample`=1 by one f16 weight rounding (two draws of the same noise).  No new symbol and no change
  *   to the struct: the ABI version is unchanged.
+ *   `upsample`=4 (seva_gemm_f16 only) is value 2 on the 128-column tiles, for the VAE decoders' upsample convs (128 / 256 / 512
+ *   channels, source rows up to 288 pixels): the same `w` [4][N][4*cin], K = 4*cin, oh = 2*ih, ow = 2*iw and output rows, with
+ *   N % 128 == 0 and cin % 64 == 0, and bias + out_f32 + optional ch_stats.  Tiles are consecutive source pixels where one
+ *   image's window fits, else 16 source columns x 8 source rows (iw % 16 == 0 and ih % 8 == 0); which is decided from one
+ *   image's dimensions.  ch_stats needs ih*iw % 64 == 0 (else an ERROR): a block is then 64 source pixels of ONE phase, i.e.
+ *   64 output pixels of one image, stored as block 4*(source block) + 2*py + px, so that the oh*ow/64 blocks of image i are
+ *   exactly [i*oh*ow/64, (i+1)*oh*ow/64), each written once; consumers rely only on the blocks of an image adding up to that
+ *   image.  residual, row_add, out_f16, out_f8, a2, splitk_ws, col_scale, GEGLU, seva_gemm_fp8, a shape neither tiling
+ *   takes, or conv_win knob 0 are an ERROR, never a fall-back.  Values 2 and 3 are unchanged (3 is an error); no new symbol,
+ *   no change to the struct, the ABI version is unchanged.
  * epilogue 0: linear.  epilogue 1 (GEGLU): W rows are interleaved in groups of 64 as
  *   [32 value rows | 32 gate rows] (same for bias); output has N/2 columns:
  *   out[m][f] = (v + bv) * gelu_erf(g + bg).
@@ -104,7 +114,7 @@ typedef struct seva_gemm_desc {
    * sum of squares ([..][1][n]) of the fp32 values stored (after bias / row_add / residual); rows >= M contribute
    * nothing.  A block is 64 consecutive rows aligned to multiples of 64 rows of the whole tensor, EXCEPT for 3x3
    * convolutions over images at least 144 pixels wide with N % 160 != 0, or any such e4m3 convolution (ABI 10), or an e4m3 stride-2
-   * pad_br_only convolution whose image is too wide for its linear tiles (ABI 11) (the 2-D tiles of the window-staged kernel), where the blocks [i * hw / 64, (i + 1) * hw / 64) partition the pixels of image i in tile order: consumers must
+   * pad_br_only convolution whose image is too wide for its linear tiles (ABI 11) (the 2-D tiles of the window-staged kernel), or a phase-decomposed upsample conv (`upsample` = 4: blocks of one output phase), where the blocks [i * hw / 64, (i + 1) * hw / 64) partition the pixels of image i in tile order: consumers must
    * only rely on the blocks of an image adding up to that image (seva_groupnorm does).  Per channel, so any grouping or
    * channel concatenation can be formed by the consumer.  Plain epilogue with out_f32 and N >= 128 only; forces 128-row tiles. */
   float* ch_stats;

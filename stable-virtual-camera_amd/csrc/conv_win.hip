@@ -78,13 +78,18 @@ struct ConvWinGeom {
 // fragment addresses) restricted to the taps (ky, kx) = (a + py, b + px), with the phase's own [N][4 cin] weight matrix and an epilogue
 // that scatters source pixel (i, j) to output pixel (2i + py, 2j + px).  The four phases of a tile are neighbours in the remapped order
 // (they stage the same window).  Plain fp32 epilogue with bias only; M, hw, ow of the arguments describe the SOURCE image.
+// upsample = 4 is the same operator on the 128-column family (the VAE decoders' three upsample convs: 128 / 256 / 512 channels, 72 .. 288 px
+// source rows): linear tiles where one image's windows fit, else 2-D tiles of 16 SOURCE columns x BM / 16 source rows -- the plain 2-D window
+// of (rows + 2) x 18 source pixels, tap (a, b) of phase (py, px) the uniform shift (a + py) * 18 + (b + px) -- and GroupNorm statistics: a
+// wave's 64 source pixels are 64 output pixels of one phase, written as block 4 * (source block) + phase (needs ih * iw % 64 == 0).
 template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false, bool S2 = false, bool PH = false>
 __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWinGeom g) {
   constexpr bool T2D = TW > 0;
   static_assert(TW == 0 || TW == 16, "2-D tiles are 16 output columns wide: an MFMA block is a tile row");
   static_assert(!O8 || FP8, "the e4m3 output epilogue belongs to the e4m3 instantiations");
   static_assert(!S2 || (FP8 && !UP && !O8), "stride 2: e4m3, no upsample, no e4m3 output (the encoder's downsample convs)");
-  static_assert(!PH || (!UP && TW == 0 && !FP8 && !S2 && !STATS), "phase mode: f16, linear tiles, no statistics");
+  static_assert(!PH || (!UP && !FP8 && !S2), "phase mode: f16 operands on the source image");
+  static_assert(!PH || (TW == 0 && !STATS) || BN == 128, "phase mode: 2-D tiles and statistics belong to the 128-column family");
   constexpr int NT = PH ? 4 : 9;                               // taps per slab
   constexpr int TH = BM / 16;                                  // output rows of a 2-D tile
   constexpr int SW2 = UP ? 8 : 16, SH2 = UP ? TH / 2 : TH;     // its source extent; window = (SH2 + 2) x (SW2 + 2) pixels
@@ -437,7 +442,10 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
     const int64_t m = row_m(i);
     const int64_t mc = m < m_end ? m : m_end - 1;
     int64_t mo = m;  // output row; PH: source pixel (img, i, j) -> output pixel (img, 2i + py, 2j + px)
-    if constexpr (PH) {
+    if constexpr (PH && T2D) {  // the tile knows its image and origin: no division (the multiply-high ones hold for linear launches only)
+      const uint32_t yi = t_y0 + (uint32_t)(wm * (WM / 16) + i), xj = t_x0 + (uint32_t)fr;
+      mo = (int64_t)t_img * (4 * g.hw) + (int64_t)(2 * yi + (uint32_t)(ph >> 1)) * (2 * g.ow) + 2 * xj + (uint32_t)(ph & 1);
+    } else if constexpr (PH) {
       const uint32_t img = __umulhi((uint32_t)mc, g.mul_hw), rem = (uint32_t)mc - img * (uint32_t)g.hw;
       const uint32_t yi = __umulhi(rem, g.mul_iw), xj = rem - yi * (uint32_t)g.ow;
       mo = (int64_t)img * (4 * g.hw) + (int64_t)(2 * yi + (uint32_t)(ph >> 1)) * (2 * g.ow) + 2 * xj + (uint32_t)(ph & 1);
@@ -488,7 +496,10 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
     if (p.ch_stats != nullptr) {  // per 64-row block and channel: sum and sum of squares (gemm.hip, same association)
       // block number: linear tiles: 64 consecutive rows of the tensor; 2-D tiles: the wave's 4 tile rows x 16 pixels, numbered inside the image
       const int64_t mw = (int64_t)m0 + wm * WM;
-      const int64_t blk = T2D ? (int64_t)t_img * (g.hw >> 6) + (int64_t)t_k * (BM / 64) + wm : mw >> 6;
+      // PH: the wave's 64 source pixels are 64 OUTPUT pixels of one phase and one image (hw % 64 == 0): block 4 * (source block) + phase,
+      // so the hw_out / 64 blocks of image i fill [i hw_out / 64, (i + 1) hw_out / 64), each written once
+      const int64_t sblk = T2D ? (int64_t)t_img * (g.hw >> 6) + (int64_t)t_k * (BM / 64) + wm : mw >> 6;
+      const int64_t blk = PH ? 4 * sblk + ph : sblk;
       float* const sp_ = p.ch_stats + blk * 2 * p.N;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
@@ -590,7 +601,7 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
     if (c.out_f16) c.out_f16 += r0 * a.ldo16;
     if (c.out_f8) c.out_f8 += r0 * a.ldo8;
     if (c.row_add) c.row_add += (r0 / a.rows_per_group) * a.ldra;
-    if (c.ch_stats) c.ch_stats += (r0 / 64) * 2 * a.N;
+    if (c.ch_stats) c.ch_stats += (r0 / 64) * (PH ? 4 : 1) * 2 * a.N;
     ConvWinGeom gc = g;
     // consecutive pixels of the whole range where that fits (a tile may then straddle images: fewer, fuller tiles), else one image's
     // (the scan is bounded: a window of BM pixels + two rows cannot fit once a row exceeds the capacity)
@@ -775,20 +786,35 @@ int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
   return rc;
 }
 
-// seva_gemm_desc.upsample = 2: the nearest-2x upsample + 3x3 conv as four 2x2 phase convs on the source image (see PH above).  `a` holds the
-// conv as the caller states it (oh = 2 ih, ow = 2 iw, K = 4 cin, w = [4][N][4 cin]); gemm.hip has refused every epilogue but bias + out_f32.
+// seva_gemm_desc.upsample = 2 / 4: the nearest-2x upsample + 3x3 conv as four 2x2 phase convs on the source image (see PH above).  `a` holds
+// the conv as the caller states it (oh = 2 ih, ow = 2 iw, K = 4 cin, w = [4][N][4 cin]); gemm.hip has refused every epilogue but bias +
+// out_f32 (4: + ch_stats).
 // 0 = launched, 1 = the window kernel does not apply (an ERROR for the caller: no other kernel reads this weight layout), < 0 = error
 int seva_conv_win_phases_launch(const GemmArgs& a0, hipStream_t s) {
   const int knob = g_seva_knobs.conv_win;
   if (knob == 0) return 1;
   if (a0.stride != 1 || a0.pad_lo != 1 || a0.oh != 2 * a0.ih || a0.ow != 2 * a0.iw || a0.iw < 2 || a0.ih < 2) return 1;
-  if (a0.cin % 64 != 0 || a0.N % 160 != 0 || a0.K != 4LL * a0.cin) return 1;
+  const bool vae = a0.upsample == 4;  // the 128-column family (2-D tiles, statistics); 2: the 160-column one
+  if (a0.cin % 64 != 0 || a0.N % (vae ? 128 : 160) != 0 || a0.K != 4LL * a0.cin) return 1;
   GemmArgs a = a0;  // the kernel's view: a plain conv over the SOURCE image, one launch row per source pixel
   a.oh = a0.ih;
   a.ow = a0.iw;
   a.M = (int64_t)a0.n * a0.ih * a0.iw;
   ConvWinGeom g;
   if (win_geometry(a, false, g) != 0) return 1;
+  if (vae) {
+    // As the plain 128-column family: two 4-wave workgroups per CU on 128-row tiles, linear where the window fits (72 px source rows), else
+    // 2-D; the 8-wave 256-row tiles behind knob 2.  No other kernel reads these weights, so where the 8-wave tiles do not apply (a 2-D
+    // tile of 16 source rows on an image of 8) knob 2 still takes the 4-wave ones: same reduction order, same bits.
+    int rc = 1;
+    if (knob == 2) {
+      rc = launch_win<256, 128, 8, 416, true, true, false, 0, false, false, false, true>(a, g, s);
+      if (rc == 1) rc = launch_win<256, 128, 8, 328, true, true, false, 16, false, false, false, true>(a, g, s);
+    }
+    if (rc == 1) rc = launch_win<128, 128, 4, 288, false, true, false, 0, false, false, false, true>(a, g, s);
+    if (rc == 1) rc = launch_win<128, 128, 4, 184, false, true, false, 16, false, false, false, true>(a, g, s);
+    return rc;
+  }
   // the plain conv's two families, bitwise equal (same reduction order), chosen by the same quantisation rule with four workgroups per tile
   const auto launch4 = [&]() { return launch_win<160, 160, 4, 320, false, false, false, 0, false, false, false, true>(a, g, s); };
   const auto launch8 = [&]() { return launch_win<256, 160, 8, 416, true, false, false, 0, false, false, false, true>(a, g, s); };

@@ -960,9 +960,21 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
   a.ldra = d->ld_row_add > 0 ? d->ld_row_add : d->N;
   SEVA_REQUIRE(a.ldra % 4 == 0, "gemm: ld_row_add must be a multiple of 4");
   // upsample = 2: the fused nearest-2x upsample as four 2x2 phase convs on the source image (conv_win.hip: PH); w = [4][N][4 cin]
-  const bool phases = d->mode == 1 && d->upsample == 2;
-  SEVA_REQUIRE(d->mode != 1 || (d->upsample >= 0 && d->upsample <= 2), "conv: upsample=%d (0, 1 or 2)", d->upsample);
-  if (phases) {
+  // upsample = 4: the same on the 128-column family, with GroupNorm statistics (the VAE decoders' upsample convs)
+  const bool phases128 = d->mode == 1 && d->upsample == 4;
+  const bool phases = (d->mode == 1 && d->upsample == 2) || phases128;
+  SEVA_REQUIRE(d->mode != 1 || (d->upsample >= 0 && d->upsample <= 2) || d->upsample == 4, "conv: upsample=%d (0, 1, 2 or 4)", d->upsample);
+  if (phases128) {
+    // as for value 2: what the family does not do is an error, never a fall-back
+    SEVA_REQUIRE(!FP8, "conv: the phase-decomposed upsample (upsample = 4) is an f16 operator");
+    SEVA_REQUIRE(d->out_f32 && !d->out_f16 && !d->residual && !d->row_add && !d->a2 && !d->splitk_ws && d->col_scale_n == 0,
+                 "conv: the phase-decomposed upsample (upsample = 4) has the bias + out_f32 (+ ch_stats) epilogue only (no residual, row_add, "
+                 "out_f16, a2, splitk_ws, col_scale)");
+    SEVA_REQUIRE(d->N % 128 == 0 && d->K == 4LL * d->cin, "conv: the phase-decomposed upsample (upsample = 4) needs N %% 128 == 0 and "
+                 "K = 4 * cin per phase (N=%lld K=%lld cin=%d)", (long long)d->N, (long long)d->K, d->cin);
+    SEVA_REQUIRE(!d->ch_stats || ((int64_t)d->ih * d->iw) % 64 == 0, "conv: the phase-decomposed upsample (upsample = 4) emits ch_stats only "
+                 "where a 64-pixel block of one phase stays inside one image: ih * iw %% 64 == 0 (source %dx%d)", d->ih, d->iw);
+  } else if (phases) {
     // no other kernel reads this weight layout, so everything the phase family does not do is an error, never a fall-back
     SEVA_REQUIRE(!FP8, "conv: the phase-decomposed upsample (upsample = 2) is an f16 operator");
     SEVA_REQUIRE(d->out_f32 && !d->out_f16 && !d->residual && !d->row_add && !d->a2 && !d->splitk_ws && !d->ch_stats && d->col_scale_n == 0,
@@ -1014,7 +1026,8 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
     SEVA_REQUIRE(d->epilogue == 0, "conv: the phase-decomposed upsample has the plain epilogue only");
     const int rc = seva_conv_win_phases_launch(a, s);
     SEVA_REQUIRE(rc != 1, "conv: the phase-decomposed upsample runs on the window kernel only, which declined it (image %dx%d, cin %d, N %lld: "
-                 "stride 1, pad 1, one image's tiles must fit the window; conv_win knob not 0)", d->ih, d->iw, d->cin, (long long)d->N);
+                 "stride 1, pad 1, one image's tiles must fit the window -- upsample = 4: or iw %% 16 == 0 and ih %% 8 == 0 for the 2-D tiles; conv_win "
+                 "knob not 0)", d->ih, d->iw, d->cin, (long long)d->N);
     return rc;
   }
   if (d->epilogue == 1) {

@@ -5,6 +5,9 @@ into the gather.  The single-head d=512 mid-block attention runs as GEMM(QK^T) -
 GEMM(P V^T) with V produced already transposed by swapping the GEMM operand roles; the value
 bias is added after P*V (rows of P sum to 1, exact).
 
+The decoder's three upsample convs can run as four 2x2 phase convs on the source image (`AutoEncoder.set_upsample("phases")`, or
+SEVA_VAE_UPSAMPLE_PHASES=1 when that was not called): see `VaeDecoderEngine.phase_weights`.
+
 The decoder has an opt-in fp8 precision (`AutoEncoder.set_precision("fp8")`, or SEVA_VAE_PRECISION=fp8 when that was not
 called): see `fp8_decoder_convs`.  The encoder has one of its own (`AutoEncoder.set_precision(..., encode="fp8")`, or
 SEVA_VAE_ENCODE_PRECISION=fp8 when no `encode=` was given): see `fp8_encoder_convs`.
@@ -17,12 +20,13 @@ import os
 import torch
 
 from . import ops
-from ._engine import CIN_PAD, _Arena, pack_conv3x3
+from ._engine import CIN_PAD, _Arena, combine_up_phases, pack_conv3x3
 from ._native import SevaNativeError, require_cuda
 
 F16, F32 = torch.float16, torch.float32
 U8 = torch.uint8  # e4m3 bytes (ops.py)
 VAE_PRECISIONS = ("f16", "fp8")
+VAE_UPSAMPLES = ("taps", "phases")
 
 
 def check_vae_precision(precision: str) -> str:
@@ -39,6 +43,33 @@ def vae_precision_from_env() -> str:
 def vae_encode_precision_from_env() -> str:
     """SEVA_VAE_ENCODE_PRECISION=f16|fp8 (unset: f16); used only where `AutoEncoder.set_precision` was not given `encode=`."""
     return check_vae_precision(os.environ.get("SEVA_VAE_ENCODE_PRECISION") or "f16")
+
+
+def check_vae_upsample(upsample: str) -> str:
+    if upsample not in VAE_UPSAMPLES:
+        raise ValueError(f"unknown VAE upsample mode {upsample!r} (taps | phases)")
+    return upsample
+
+
+def vae_upsample_from_env() -> str:
+    """SEVA_VAE_UPSAMPLE_PHASES=1: "phases" (unset or anything else: "taps"); used only where `AutoEncoder.set_upsample` was not called."""
+    return "phases" if os.environ.get("SEVA_VAE_UPSAMPLE_PHASES", "0") == "1" else "taps"
+
+
+def up_phases128_applies(ih: int, iw: int) -> bool:
+    """Whether `ops.conv3x3_up_phases128` takes a source image of ih x iw pixels (the window kernel's rule, from one image's dimensions):
+    linear tiles where the window of every 128-pixel tile of the image -- its pixels in the padded index space, row pitch iw + 1, plus
+    a halo of one padded row and one pixel on either side -- fits 288 pixels, else 2-D tiles of 16 x 8 source pixels."""
+    if ih < 2 or iw < 2:
+        return False
+    wp, hw = iw + 1, ih * iw
+
+    def padded(m):
+        return (m // iw + 1) * wp + m % iw + 1
+
+    if all(padded(min(m0 + 128, hw) - 1) - padded(m0) + 2 * wp + 3 <= 288 for m0 in range(0, hw, 128)):
+        return True
+    return iw % 16 == 0 and ih % 8 == 0
 
 
 def fp8_downsample_from_env() -> bool:
@@ -320,12 +351,28 @@ class VaeDecoderEngine(_VaeEngineBase):
     PREFIXES = ("decoder.", "post_quant_conv.")
     CONV_IN, CONV_OUT = "decoder.conv_in", "decoder.conv_out"
 
-    def __init__(self, weights, precision: str = "f16"):
+    def __init__(self, weights, precision: str = "f16", upsample: str | None = None):
         super().__init__(weights)
         self.precision = check_vae_precision(precision)  # decode precision; may be changed between decodes (AutoEncoder.set_precision)
+        # "taps" | "phases"; may be changed between decodes (AutoEncoder.set_upsample).  None: the environment, read here
+        self.upsample = vae_upsample_from_env() if upsample is None else check_vae_upsample(upsample)
         self._src = weights
         self.fp8_upsample = fp8_upsample_from_env()
         self.W8 = None  # e4m3 conv weights, packed the first time an fp8 decode runs
+        self.W4 = None  # phase weights of the upsample convs, packed the first time a "phases" decode runs
+
+    def phase_weights(self) -> dict:
+        """{prefix + ".w4": f16 [4, cout, 4 * cin]} (`combine_up_phases`: one rounding of the fp64 sums) for the f16 upsample convs that the
+        "phases" decode runs through `ops.conv3x3_up_phases128`: those with cout % 128 == 0 (the kernel's tile width; a per-conv rule, so a
+        narrower conv of the same decoder keeps the nine-tap call)."""
+        if self.W4 is None:
+            sd = self._src.state_dict()
+            self.W4 = {}
+            for i, cout in enumerate(reversed(self.block_out)):
+                p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
+                if i != len(self.block_out) - 1 and cout % 128 == 0:
+                    self.W4[p + ".w4"] = combine_up_phases(sd[p + ".weight"].detach().to(self.device).float())
+        return self.W4
 
     def fp8_weights(self) -> dict:
         if self.W8 is None:
@@ -352,6 +399,9 @@ class VaeDecoderEngine(_VaeEngineBase):
         self.gn_ws = self._buf("gn_ws", (n * ops.GN_WORKSPACE_SLABS * 32 * 2,), F32)
         self._stats = {}
         self._w8 = W8 = self.fp8_weights() if check_vae_precision(self.precision) == "fp8" else {}
+        # the upsample convs as four 2x2 phase convs (4/9 of the FLOPs), where the operator exists: the f16 ones only
+        phases = getattr(ops, "conv3x3_up_phases128", None) if check_vae_upsample(self.upsample) == "phases" else None
+        W4 = self.phase_weights() if phases is not None else {}
         inv = torch.full((n,), 1.0 / scale_factor, dtype=F32, device=self.device)
         z16 = self._buf("v_z16", (n, h * w, CIN_PAD), F16)
         ops.nchw_to_nhwc_f16(z, None, z16, scale=inv)                      # z / 0.18215, channels-last, padded
@@ -384,6 +434,12 @@ class VaeDecoderEngine(_VaeEngineBase):
                 st = self._stats_buf("out:" + p, n * h * w, h * w, cout)
                 if up8:
                     ops.conv3x3(x8, W8[p + ".w8"], w_exp=W8[p + ".w8e"], upsample=True, bias=W[p + ".b"], out_f32=x, ch_stats=st)
+                elif p + ".w4" in W4 and up_phases128_applies(h // 2, w // 2):  # (a per-image rule; else the nine taps)
+                    # statistics as for the nine taps, where a block of 64 source pixels of one phase stays inside an image (every latent
+                    # whose sides are multiples of 8); else the consuming GroupNorm runs its own pass
+                    if (h * w // 4) % ops.STATS_ROWS:
+                        st = None
+                    phases(x16, W4[p + ".w4"], bias=W[p + ".b"], out_f32=x, ch_stats=st, alg_k=9 * cout)
                 else:
                     ops.conv3x3(x16, W[p + ".w"], upsample=True, bias=W[p + ".b"], out_f32=x, ch_stats=st)
                 self._produced(x, st)

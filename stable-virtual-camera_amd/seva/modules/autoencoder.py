@@ -181,6 +181,33 @@ class AutoEncoder(nn.Module):
         self._enc_engine = None
         self._precision = None  # decode precision set by set_precision; None: SEVA_VAE_PRECISION, else "f16"
         self._encode_precision = None  # encode precision set by set_precision(encode=); None: SEVA_VAE_ENCODE_PRECISION, else "f16"
+        self._upsample = None  # decoder upsample convs set by set_upsample; None: SEVA_VAE_UPSAMPLE_PHASES=1 -> "phases", else "taps"
+
+    def set_upsample(self, upsample: str) -> "AutoEncoder":
+        """How the decoder's three upsample convs run: "taps" (the default: the nine-tap conv on the fused nearest-2x upsample) or
+        "phases" (four 2x2 convs on the source image with summed weights, 4/9 of the FLOPs, GroupNorm statistics still from the
+        epilogue; seva/_vae_engine.py:VaeDecoderEngine.phase_weights).  Applies to the f16 decode and to the f16 upsample convs of
+        the fp8 decode; a conv whose channel count is not a multiple of 128 keeps the nine taps.  The result differs from "taps"
+        by one f16 weight rounding.  Switching back to "taps" gives exactly the default results; the phase weights are packed
+        the first time a "phases" decode runs.  A refused value changes nothing."""
+        from .._vae_engine import check_vae_upsample
+
+        self._upsample = check_vae_upsample(upsample)
+        if self._engine is not None:
+            self._engine.upsample = self._upsample
+        return self
+
+    @property
+    def upsample(self) -> str:
+        """The upsample mode in effect: set_upsample's value, else SEVA_VAE_UPSAMPLE_PHASES (read when the decoder engine is
+        built), else "taps"."""
+        if self._upsample is not None:
+            return self._upsample
+        if self._engine is not None:
+            return self._engine.upsample
+        from .._vae_engine import vae_upsample_from_env
+
+        return vae_upsample_from_env()
 
     def set_precision(self, precision: str, *, encode: str | None = None) -> "AutoEncoder":
         """Decode precision: "f16" (the default) or "fp8" (the decoder's 3x3 convs with 128k channels on e4m3 weights and
@@ -246,7 +273,7 @@ class AutoEncoder(nn.Module):
         if self._engine is None:
             from .._vae_engine import VaeDecoderEngine
 
-            self._engine = VaeDecoderEngine(self.module, precision=self.precision)
+            self._engine = VaeDecoderEngine(self.module, precision=self.precision, upsample=self.upsample)
         return self._engine
 
     def _encode(self, x: torch.Tensor) -> torch.Tensor:

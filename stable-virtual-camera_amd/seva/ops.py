@@ -328,6 +328,32 @@ def conv3x3_up_phases(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tensor |
     check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), "seva_gemm_f16(conv, upsample phases)")
 
 
+def conv3x3_up_phases128(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tensor | None = None, out_f32: torch.Tensor | None = None,
+                         ch_stats: torch.Tensor | None = None, alg_k: int = 0) -> None:
+    """`conv3x3_up_phases` on the 128-column tiles (seva_gemm_desc.upsample = 4): the VAE decoders' upsample convs.  Same operands
+    (x: [n, ih, iw, cin] f16 NHWC; w4: [4, cout, 4*cin] f16 from `combine_up_phases`; out_f32: [n, 2 ih * 2 iw, cout]), cout % 128 == 0,
+    linear or 2-D tiles by one image's dimensions, and GroupNorm statistics: `ch_stats` (`channel_stats_shape(n * 4 ih iw, cout)`) gets
+    one block per 64 output pixels of one phase, the blocks of an image adding up to that image; it needs ih * iw % 64 == 0.  Raises
+    where the window kernel declines: no other kernel reads this weight layout."""
+    require_cuda(x, w4)
+    assert x.dtype == w4.dtype == F16 and x.dim() == 4 and x.is_contiguous() and w4.is_contiguous()
+    n, ih, iw, cin = x.shape
+    assert w4.dim() == 3 and w4.shape[0] == 4 and w4.shape[2] == 4 * cin, "w4: [4, cout, 4 * cin]"
+    if out_f32 is None:
+        raise ValueError("conv3x3_up_phases128 needs out_f32")
+    oh, ow = 2 * ih, 2 * iw
+    d = GemmDesc()
+    d.a, d.w, d.bias, d.out_f32 = x.data_ptr(), w4.data_ptr(), ptr(bias), out_f32.data_ptr()
+    d.M, d.N, d.K = n * oh * ow, w4.shape[1], 4 * cin
+    d.alg_K = alg_k
+    d.lda, d.ldo32 = cin, out_f32.stride(-2)
+    d.mode, d.epilogue = 1, 0
+    d.n, d.ih, d.iw, d.cin, d.oh, d.ow = n, ih, iw, cin, oh, ow
+    d.stride, d.upsample = 1, 4
+    d.ch_stats = _stats_ptr(ch_stats, n * oh * ow, w4.shape[1], out_f32)
+    check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), "seva_gemm_f16(conv, upsample phases, 128 columns)")
+
+
 def attention(
     q: torch.Tensor,
     k: torch.Tensor,
