@@ -1,17 +1,25 @@
 """TEST INFRASTRUCTURE -- CPU fp32 restatement of the CLIP image conditioner.
 
-**Parity unpinned.**  The reference (seva/modules/conditioner.py:7-39) delegates to two third-party packages that are
-absent from /root/reference and from this image: `open_clip` (`create_model_and_transforms("ViT-H-14",
-pretrained="laion2b_s32b_b79k")`, `.encode_image`) and `kornia` (`geometry.resize(..., bicubic, align_corners=True,
-antialias=True)`, `enhance.normalize`); pyproject.toml lists both unpinned.  The reference holds no fixture for them
-and the weights need the network, so this file restates their published algorithms and the HIP path is checked
-against it only (self-consistency), exactly like the VAE (oracle/vae_ref.py):
+**Tower pinned, resize restated.**  The reference (seva/modules/conditioner.py:7-39) delegates to two third-party
+packages that are not installed and that the reference tree does not vendor: `open_clip`
+(`create_model_and_transforms("ViT-H-14", pretrained="laion2b_s32b_b79k")`, `.encode_image`) and `kornia`
+(`geometry.resize(..., bicubic, align_corners=True, antialias=True)`, `enhance.normalize`); pyproject.toml lists both
+without a version.  The reference holds no fixture for them and the weights need the network, so this file restates
+their published algorithms:
 
   * open_clip `VisionTransformer.forward` for the ViT-H-14 config (image 224, patch 14, width 1280, 32 layers, 16 heads
     = head width 80, MLP 5120 with exact-erf GELU, LayerNorm eps 1e-5, class token + learned positional embedding,
-    `ln_pre`, pooled = `ln_post(x[:, 0]) @ proj`), key names of the `visual.` sub-module of the open_clip state_dict;
+    `ln_pre`, pooled = `ln_post(x[:, 0]) @ proj`), key names of the `visual.` sub-module of the open_clip state_dict.
+    `encode_image` IS PINNED against an independent implementation of the same network, transformers'
+    `CLIPVisionModelWithProjection`, on synthetic weights, through the fixtures tests/golden/g11_clip_*.npz
+    (oracle/make_goldens_clip.py): fp32 here vs fp64 there, rel-L2 5.4e-7 (3 layers, width 320), 4.6e-7 (2 layers,
+    width 1280), 6.3e-7 (the full 32 layers), asserted < 1e-5 by tests/test_clip_parity_cpu.py, which also shows that
+    a tanh- or quick-GELU, an eps of 1e-6, a wrong head count or swapped k / v thirds miss that bound by 16x or more;
   * kornia `resize(antialias=True)`: when down-scaling, Gaussian blur with sigma = max((factor - 1) / 2, 0.001), kernel
     size int(max(4 sigma, 3)) made odd, 'reflect' border; then `F.interpolate(mode="bicubic", align_corners=True)`.
+    This part REMAINS A RESTATEMENT (no independent implementation is at hand); the fixtures' images are 224 x 224,
+    where it is the identity, so they say nothing about it.  Like the VAE (oracle/vae_ref.py), the HIP resize is
+    checked for self-consistency only.
 
 Only tests/ import this module.
 """
@@ -49,6 +57,46 @@ def vit_shapes(width=1280, layers=32, patch=14, image=224, mlp=5120, embed=1024)
             f"{b}.mlp.c_proj.weight": (width, mlp), f"{b}.mlp.c_proj.bias": (width,),
         })
     return s
+
+
+def synthetic_state_dict(params, seed: int = 11) -> dict:
+    """Seeded open_clip-named `visual.*` state_dict for a tower with the hyper-parameters of `params` (a `ViTParams`:
+    width, layers, patch_size, image_size, mlp_ratio, embed_dim).  `seva.synthetic.synth_state_dict` for every entry,
+    then -- from one generator, in this order -- the 0.02 randn class / positional embeddings and the fan-in-scaled
+    `proj` and fused q/k/v `in_proj_weight` (none of them a `.weight` name the synthetic rule would scale).  The
+    fixture generator (oracle/make_goldens_clip.py) and the CPU and GPU tests all take their weights from here; the
+    fixtures store sums of |w| (`weight_sums`) so that a change of these values is reported as such."""
+    from seva import synthetic as synth
+    shapes = vit_shapes(params.width, params.layers, params.patch_size, params.image_size,
+                        int(params.width * params.mlp_ratio), params.embed_dim)
+    sd = synth.synth_state_dict(shapes, seed)
+    g = torch.Generator().manual_seed(seed)
+    for k in ("visual.class_embedding", "visual.positional_embedding"):
+        sd[k] = 0.02 * torch.randn(shapes[k], generator=g)
+    sd["visual.proj"] = torch.randn(shapes["visual.proj"], generator=g) * params.width ** -0.5
+    for k in shapes:  # not a `.weight` name: give the fused q/k/v projection a proper fan-in scale
+        if k.endswith("in_proj_weight"):
+            sd[k] = torch.randn(shapes[k], generator=g) * params.width ** -0.5
+    return sd
+
+
+def weight_sums(sd: dict) -> dict:
+    """fp64 sums of |w| of three entries of a `synthetic_state_dict` (first, last block, projection), as the fixtures
+    store them."""
+    last = max(int(k.split(".")[3]) for k in sd if k.startswith("visual.transformer.resblocks."))
+    keys = {"wsum_conv1": "visual.conv1.weight", "wsum_c_proj": f"visual.transformer.resblocks.{last}.mlp.c_proj.weight",
+            "wsum_proj": "visual.proj"}
+    return {n: float(sd[k].double().abs().sum()) for n, k in keys.items()}
+
+
+def assert_weight_sums(sd: dict, fixture: dict) -> None:
+    """Fails, naming the RNG and not parity, if `sd` is not the state dict the fixture was generated with."""
+    for k, got in weight_sums(sd).items():
+        want = float(fixture[k])
+        assert abs(got - want) <= 1e-9 * want, (  # 1e-9: the order of an fp64 sum of <= 6.6 M terms, nothing else
+            f"the seeded synthetic CLIP weights are not the ones the fixture was made with: {k} sums to {got!r}, the "
+            f"fixture stores {want!r}.  This is a change of the torch RNG stream or of seva.synthetic / "
+            f"clip_ref.synthetic_state_dict, NOT a parity failure: regenerate with oracle/make_goldens_clip.py")
 
 
 def gaussian_kernel1d(ks: int, sigma: float) -> torch.Tensor:

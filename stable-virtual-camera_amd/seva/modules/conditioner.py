@@ -4,8 +4,10 @@ The reference builds `open_clip.create_model_and_transforms("ViT-H-14", pretrain
 with kornia; neither package, nor the weights, exist offline.  This module owns (a) a parameter holder with open_clip's
 key names for the vision tower (`module.visual.*`), so a real open_clip checkpoint loads strictly (`load_open_clip`:
 text-tower keys are dropped knowingly, every vision key must match), and (b) the forward on HIP kernels
-(`seva/_clip_engine.py`).  Parity with open_clip / kornia is UNPINNED (no fixture can be produced here): tests compare
-against our own restatement of the published algorithms (oracle/clip_ref.py).
+(`seva/_clip_engine.py`).  The TOWER is pinned against transformers' `CLIPVisionModelWithProjection`, an independent
+implementation of the same network, on synthetic weights, through fixtures (tests/golden/g11_clip_*.npz,
+tests/test_clip_parity_cpu.py, tests/test_clip_gpu.py).  The RESIZE (kornia's Gaussian antialias rule, bicubic
+`align_corners=True`) is checked against our own restatement of the published algorithm only (oracle/clip_ref.py).
 
 Kept API: `CLIPConditioner()`, `.forward(x)` with x (n,3,H,W) in [-1,1] -> (n,1024), `.preprocess(x)`, buffers
 `mean` / `std`, `.to(device)`.  Called once per window on the input views (reference seva/eval.py:1248).
