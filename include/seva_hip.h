@@ -142,6 +142,12 @@ typedef struct seva_gemm_desc {
   int64_t alg_K;
 } seva_gemm_desc;
 int seva_gemm_f16(const seva_gemm_desc* d, seva_stream_t stream);
+/* The same operator in GEMM mode (mode 0) whose f16 output is a split-precision operand (no ABI change: a new symbol only):
+ * out_f16 (required) is written as [hi(NO) | lo(NO)] with ldo16 >= 2 NO, NO = N (plain epilogue) or N / 2 (GEGLU): hi = f16(v),
+ * lo = f16(v - f32(hi)) of the fp32 epilogue value v (after bias / row_add / residual / col_scale / GEGLU).  Columns >= 2 NO of a
+ * wider row are not touched.  out_f32 may be written beside it.  Conv mode, out_f8, w_exp and ch_stats are an ERROR, never a
+ * fall-back to a plain f16 output.  One tile shape per epilogue and width, whatever M. */
+int seva_gemm_f16_split_out(const seva_gemm_desc* d, seva_stream_t stream);
 /* BASELINE config 5 ("fp8 weights, CDNA4 fp8 MFMA"): the same operator with BOTH operands in OCP e4m3 (a: [M][lda]
  * bytes or an NHWC e4m3 image, w: [N][K] bytes) on v_mfma_scale_f32_16x16x128_f8f6f4 with fp32 accumulation; the
  * per-output-channel power-of-two weight scale enters as the MFMA's E8M0 block scale, so the accumulator holds the
@@ -295,6 +301,11 @@ int seva_groupnorm_f16(const seva_groupnorm_desc* d, seva_stream_t stream);
 /* LayerNorm over the last dim, fp32 in, f16 out (nn.LayerNorm, transformer.py:102-104,124,141-143). */
 int seva_layernorm_f16(const float* x, const float* gamma, const float* beta, void* out_f16,
                        int64_t rows, int32_t c, float eps, seva_stream_t stream);
+/* Same normalisation as a split-precision operand (no ABI change: a new symbol only): out_f16 is [rows][2 c]; columns [0, c) hold
+ * hi = f16(y), bit for bit seva_layernorm_f16's output, columns [c, 2 c) hold lo = f16(y - f32(hi)).  Against weights duplicated
+ * [W | W] (K = 2 c) the fp32-accumulating MFMA then sees the normalised row to ~22 bits. */
+int seva_layernorm_f16_split(const float* x, const float* gamma, const float* beta, void* out_f16,
+                             int64_t rows, int32_t c, float eps, seva_stream_t stream);
 /* Same normalisation with OCP e4m3 output (saturating at +-448): the A operand of seva_gemm_fp8. */
 int seva_layernorm_fp8(const float* x, const float* gamma, const float* beta, void* out_f8, int64_t rows,
                        int32_t c, float eps, int64_t ld_out /* row pitch in bytes, >= c; 0 = c; pad bytes untouched */,
@@ -329,6 +340,10 @@ int seva_nhwc_to_nchw_f32(const float* x, int64_t ld, float* out, int32_t n, int
 /* concat-cast: [rows][c1] f32 ‖ [rows][c2] f32 -> [rows][c1+c2] f16 (x2 may be NULL). */
 int seva_cast_concat_f16(const float* x1, int32_t c1, const float* x2, int32_t c2, void* out_f16,
                          int64_t rows, seva_stream_t stream);
+/* Same, split precision (the contract of seva_nchw_to_nhwc_f16_split for the channels-last cast): out_f16 is [rows][2 C],
+ * C = c1 + c2; columns [0, C) hold f16(v), columns [C, 2C) hold lo = f16(v - f32(f16(v))). */
+int seva_cast_concat_f16_split(const float* x1, int32_t c1, const float* x2, int32_t c2, void* out_f16,
+                               int64_t rows, seva_stream_t stream);
 /* Bilinear resize, align_corners=True, [n][c][sh][sw] f32 -> channels-last [n][oh*ow][c] f32
  * (F.interpolate at seva/modules/layers.py:126-130; step-invariant). */
 int seva_bilinear_to_nhwc_f32(const float* src, float* out, int32_t n, int32_t c, int32_t sh,

@@ -72,6 +72,26 @@ __global__ void cast_concat_f16_kernel(const float* __restrict__ x1, int c1,
   }
 }
 
+// the same cast as a split-precision operand: row pitch 2 C (C = c1 + c2), columns [0, C) hold hi = f16(v), columns [C, 2C) lo = f16(v - f32(hi))
+__global__ void cast_concat_f16_split_kernel(const float* __restrict__ x1, int c1,
+                                             const float* __restrict__ x2, int c2,
+                                             half_t* __restrict__ out, int64_t rows) {
+  const int C = c1 + c2, cq = C >> 2;
+  const int64_t total = rows * cq;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = i / cq;
+    const int c = (int)(i - row * cq) * 4;
+    const f32x4 v = (c < c1) ? *(const f32x4*)(x1 + row * c1 + c)
+                             : *(const f32x4*)(x2 + row * c2 + (c - c1));
+    const half4_t h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+    const half4_t l = {(half_t)(v[0] - (float)h[0]), (half_t)(v[1] - (float)h[1]), (half_t)(v[2] - (float)h[2]),
+                       (half_t)(v[3] - (float)h[3])};
+    *(half4_t*)(out + row * 2 * C + c) = h;
+    *(half4_t*)(out + row * 2 * C + C + c) = l;
+  }
+}
+
 // F.interpolate(mode="bilinear", align_corners=True): src = dst * (in-1)/(out-1)
 __global__ void bilinear_to_nhwc_kernel(const float* __restrict__ src, float* __restrict__ out,
                                         int n, int c, int sh, int sw, int oh, int ow) {
@@ -310,6 +330,15 @@ extern "C" int seva_cast_concat_f16(const float* x1, int32_t c1, const float* x2
   SEVA_REQUIRE(c2 == 0 || x2, "cast_concat: c2 > 0 needs x2");
   SevaProfScope prof(4, (double)rows * (c1 + c2) * 6.0, (hipStream_t)stream);
   EW_LAUNCH(cast_concat_f16_kernel, rows * ((c1 + c2) / 4), x1, c1, x2, c2, (half_t*)out_f16, rows);
+}
+
+extern "C" int seva_cast_concat_f16_split(const float* x1, int32_t c1, const float* x2, int32_t c2,
+                                          void* out_f16, int64_t rows, seva_stream_t stream) {
+  SEVA_REQUIRE(x1 && out_f16 && rows > 0 && c1 > 0 && c1 % 4 == 0 && c2 % 4 == 0 && c2 >= 0,
+               "cast_concat_split: bad args c1=%d c2=%d", c1, c2);
+  SEVA_REQUIRE(c2 == 0 || x2, "cast_concat_split: c2 > 0 needs x2");
+  SevaProfScope prof(4, (double)rows * (c1 + c2) * 8.0, (hipStream_t)stream);
+  EW_LAUNCH(cast_concat_f16_split_kernel, rows * ((c1 + c2) / 4), x1, c1, x2, c2, (half_t*)out_f16, rows);
 }
 
 extern "C" int seva_bilinear_to_nhwc_f32(const float* src, float* out, int32_t n, int32_t c,

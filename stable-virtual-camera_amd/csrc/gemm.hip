@@ -50,9 +50,15 @@ __device__ __forceinline__ void wait_vm() {
 // NW: waves per workgroup.  4 (2 x 2 wave tiles, two workgroups per CU) everywhere in production; the experimental library also
 // instantiates 8 (2 x 4 wave tiles, ONE workgroup per CU): two N-sibling 128 x 160 tiles fused so that their A rows are staged once
 // (128 x 320: 0.0109 operand bytes per FLOP; same per-wave tile, registers and waves per SIMD as 128 x 160) -- measured slower.
-template <int BM, int BN, int MODE, int EPI, bool DBGK, bool PAIRED, bool ASTAT, bool FP8 = false, bool SPLITK = false, int NW = 4>
+// SPLIT16 (seva_gemm_f16_split_out; its own instantiations, every other kernel stays as it is): out_f16 is a split-precision operand
+// [hi | lo] -- columns [0, NO) hold hi = f16(v), columns [NO, 2 NO) hold lo = f16(v - f32(hi)) of the fp32 epilogue value v, NO = the
+// epilogue's output width (N, GEGLU: N / 2).  Plain GEMM mode, the fp32-capable plain epilogue and the GEGLU epilogue only.
+template <int BM, int BN, int MODE, int EPI, bool DBGK, bool PAIRED, bool ASTAT, bool FP8 = false, bool SPLITK = false, int NW = 4,
+          bool SPLIT16 = false>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
   const int dbg = DBGK ? p.dbg : 0;
+  static_assert(!SPLIT16 || (MODE == 0 && !DBGK && !ASTAT && !FP8 && !SPLITK && NW == 4 && PAIRED == (EPI == 1)),
+                "split-precision f16 output: plain GEMM mode, the unpaired plain epilogue or the GEGLU epilogue");
   static_assert(NW == 4 || (NW == 8 && !DBGK && !PAIRED && !ASTAT && !FP8 && !SPLITK), "8 waves: plain fp32-output kernels only");
   constexpr int WNW = NW / 2;  // waves along N
   constexpr int WM = ASTAT ? BM / 4 : BM / 2, WN = ASTAT ? BN : BN / WNW;  // per-wave tile
@@ -616,8 +622,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
     }
     // ASYNC bookkeeping: S_ST is exact only for an interior tile (every guarded store executes) with
     // 16-byte stores; anything else falls back to vmcnt(0)-strength waits (a smaller count is always safe)
-    stores_flying = ASYNC && m0 + BM <= p.M && n0 + BN <= p.N && (p.ldo16 & 7) == 0 && !p.out_f32 &&
-                    !(FP8 && p.out_f8 && p.out_f16) && tn + 1 < tn_end;  // (f8 + f16 together: twice the stores)
+    stores_flying = ASYNC && !SPLIT16 && m0 + BM <= p.M && n0 + BN <= p.N && (p.ldo16 & 7) == 0 && !p.out_f32 &&
+                    !(FP8 && p.out_f8 && p.out_f16) && tn + 1 < tn_end;  // (f8 + f16 together, hi + lo: twice the stores)
 
     // ---- epilogue: lane holds features f..f+3 (rows of D) of token m (column of D) ----
     if constexpr (EPI == 0 && PAIRED) {
@@ -712,7 +718,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
           for (int j = 0; j < NJ; ++j) acc[i][j] = v[j];  // (a register rename) the statistics pass reads the final values
         }
         const int64_t ms = (dbg & 256) ? (m & 127) : m;  // ablation bit 256: stores land in an L2-resident region
-        const bool pitch16_ok = (p.ldo16 & 7) == 0;  // 16-byte f16 stores need an 8-element row pitch
+        [[maybe_unused]] const bool pitch16_ok = (p.ldo16 & 7) == 0;  // 16-byte f16 stores need an 8-element row pitch
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           const int64_t f = n0 + wn * WN + feat_of(j, fg);
@@ -722,7 +728,13 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
             continue;
           }
           if (p.out_f32) *(f32x4*)(p.out_f32 + ms * p.ldo32 + f) = v[j];
-          if (p.out_f16) {
+          if constexpr (SPLIT16) {
+            const half4_t h = {(half_t)v[j][0], (half_t)v[j][1], (half_t)v[j][2], (half_t)v[j][3]};
+            const half4_t l = {(half_t)(v[j][0] - (float)h[0]), (half_t)(v[j][1] - (float)h[1]), (half_t)(v[j][2] - (float)h[2]),
+                               (half_t)(v[j][3] - (float)h[3])};
+            *(half4_t*)(p.out_f16 + ms * p.ldo16 + f) = h;
+            *(half4_t*)(p.out_f16 + ms * p.ldo16 + p.N + f) = l;
+          } else if (p.out_f16) {
             if (j + 1 < NJP && (j & 1) == 0 && f + 8 <= p.N && pitch16_ok) {
               // both halves of the pair in range: one 16-byte store of 8 consecutive features
               half8_t h = {(half_t)v[j][0],     (half_t)v[j][1],     (half_t)v[j][2],     (half_t)v[j][3],
@@ -793,6 +805,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
             half8_t h = {(half_t)o0[0], (half_t)o0[1], (half_t)o0[2], (half_t)o0[3],
                          (half_t)o1[0], (half_t)o1[1], (half_t)o1[2], (half_t)o1[3]};
             *(half8_t*)(p.out_f16 + m * p.ldo16 + fo) = h;
+            if constexpr (SPLIT16) {
+              const half8_t l = {(half_t)(o0[0] - (float)h[0]), (half_t)(o0[1] - (float)h[1]), (half_t)(o0[2] - (float)h[2]),
+                                 (half_t)(o0[3] - (float)h[3]), (half_t)(o1[0] - (float)h[4]), (half_t)(o1[1] - (float)h[5]),
+                                 (half_t)(o1[2] - (float)h[6]), (half_t)(o1[3] - (float)h[7])};
+              *(half8_t*)(p.out_f16 + m * p.ldo16 + p.N / 2 + fo) = l;
+            }
           }
           if constexpr (FP8) {
             if (p.out_f8) {  // e4m3 hidden activations, saturating (8 consecutive features = one 8-byte store)
@@ -808,11 +826,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
   }
 }
 
-template <int BM, int BN, int MODE, int EPI, bool PAIRED, bool ASTAT = false, bool FP8 = false, bool SPLITK = false, int NW = 4>
+template <int BM, int BN, int MODE, int EPI, bool PAIRED, bool ASTAT = false, bool FP8 = false, bool SPLITK = false, int NW = 4,
+          bool SPLIT16 = false>
 int launch_p(const GemmArgs& a, hipStream_t s) {
   // + bias slots (ASYNC) + weight-scale slots (FP8 ASYNC)
   constexpr int lds = 2 * ((ASTAT ? 0 : BM) + BN) * 128 + (ASTAT ? 8192 : PAIRED ? 4096 : 0) + (FP8 && PAIRED ? 4096 : 0);
-  constexpr bool DBG_BUILD = !ASTAT && !FP8 && !SPLITK && NW == 4;  // the ablation instantiation only exists for the staged-A f16 kernels
+  constexpr bool DBG_BUILD = !ASTAT && !FP8 && !SPLITK && NW == 4 && !SPLIT16;  // the ablation instantiation only exists for the staged-A f16 kernels
   // the dynamic-LDS attribute is per device: one bit per device ordinal and instantiation (a second GPU in the
   // same process would otherwise launch 72-80 KB kernels without it)
   static std::atomic<uint64_t> attr_devs{0};
@@ -820,7 +839,7 @@ int launch_p(const GemmArgs& a, hipStream_t s) {
   (void)hipGetDevice(&dev);
   const uint64_t dev_bit = 1ull << (dev & 63);
   if (!(attr_devs.load(std::memory_order_relaxed) & dev_bit)) {
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, MODE, EPI, false, PAIRED, ASTAT, FP8, SPLITK, NW>,
+    (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, MODE, EPI, false, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if constexpr (DBG_BUILD)
       (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, MODE, EPI, true, PAIRED, false>,
@@ -873,7 +892,7 @@ int launch_p(const GemmArgs& a, hipStream_t s) {
       return seva_check_launch("gemm_kernel");
     }
   }
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, MODE, EPI, false, PAIRED, ASTAT, FP8, SPLITK, NW>), dim3((unsigned)nb), dim3(64 * NW), lds, s, args);
+  hipLaunchKernelGGL((gemm_kernel<BM, BN, MODE, EPI, false, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16>), dim3((unsigned)nb), dim3(64 * NW), lds, s, args);
   return seva_check_launch("gemm_kernel");
 }
 
@@ -905,9 +924,19 @@ int launch(const GemmArgs& a, hipStream_t s) {
 }  // namespace
 
 namespace {
-template <bool FP8>
+template <bool FP8, bool SPLIT16 = false>
 int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
   SEVA_REQUIRE(d != nullptr, "gemm: null desc");
+  if constexpr (SPLIT16) {
+    // what the split-precision output does not do is an error, never a fall-back to a plain f16 output
+    SEVA_REQUIRE(d->mode == 0, "gemm split_out: GEMM mode only (no convolution)");
+    SEVA_REQUIRE(!d->out_f8 && !d->w_exp, "gemm split_out: an f16 operator (no out_f8 / w_exp)");
+    SEVA_REQUIRE(!d->ch_stats, "gemm split_out: no ch_stats (GroupNorm statistics belong to an fp32 output of seva_gemm_f16)");
+    SEVA_REQUIRE(d->out_f16 != nullptr, "gemm split_out: out_f16 is required");
+    SEVA_REQUIRE(d->epilogue == 0 || d->epilogue == 1, "gemm: bad epilogue %d", d->epilogue);
+    const int64_t n_out = d->epilogue == 1 ? d->N / 2 : d->N;
+    SEVA_REQUIRE(d->ldo16 >= 2 * n_out, "gemm split_out: ldo16=%lld must hold [hi | lo] = 2 x %lld columns", (long long)d->ldo16, (long long)n_out);
+  }
   SEVA_REQUIRE(d->a && d->w, "gemm: null operand");
   SEVA_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "gemm: empty problem M=%lld N=%lld K=%lld",
                (long long)d->M, (long long)d->N, (long long)d->K);
@@ -1036,7 +1065,12 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
     SEVA_REQUIRE(!d->out_f16 || d->ldo16 % 8 == 0, "geglu: f16 row pitch must be a multiple of 8");
   }
   const bool narrow = d->N <= 32;
-  if constexpr (FP8) {
+  if constexpr (SPLIT16) {
+    // one tile shape per epilogue and width, whatever M: nothing about a row's result depends on the batch
+    if (d->epilogue == 1) return launch_p<128, 128, 0, 1, true, false, false, false, 4, true>(a, s);
+    if (d->N % 160 == 0) return launch_p<128, 160, 0, 0, false, false, false, false, 4, true>(a, s);
+    return launch_p<128, 128, 0, 0, false, false, false, false, 4, true>(a, s);
+  } else if constexpr (FP8) {
     // e4m3 operands: the K >= 640 GEMMs / cin >= 640 convs of the ds2..ds8 levels.  Same tile-shape heuristics.
     bool half_m8 = ((d->M + 127) / 128) * ((d->N + 159) / 160) < 320 && d->M > 64;
     if (g_seva_knobs.gemm_bm > 0) half_m8 = g_seva_knobs.gemm_bm == 64;
@@ -1153,6 +1187,10 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
 }  // namespace
 
 extern "C" int seva_gemm_f16(const seva_gemm_desc* d, seva_stream_t stream) { return gemm_entry<false>(d, stream); }
+
+// seva_gemm_f16 in GEMM mode whose out_f16 is a split-precision operand [hi(NO) | lo(NO)] of the fp32 epilogue value (NO = N, GEGLU: N / 2;
+// ldo16 >= 2 NO): the A operand of a GEMM whose weights are duplicated [W | W]
+extern "C" int seva_gemm_f16_split_out(const seva_gemm_desc* d, seva_stream_t stream) { return gemm_entry<false, true>(d, stream); }
 
 // e4m3 x e4m3 -> fp32 on the block-scaled MFMA (BASELINE config 5): A and W are OCP e4m3 bytes, K counts e4m3 elements
 // (K % 128 == 0; conv: cin % 128 == 0), w_exp[n] = 127 + e[n] is the weight row's power-of-two scale.

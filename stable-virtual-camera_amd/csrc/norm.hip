@@ -340,7 +340,9 @@ __device__ __forceinline__ float group16_sum(float v) {
 // LN_ROWS rows are walked by one 16-lane group: gamma / beta stay in registers, the next row is prefetched.  4 for big
 // tensors (ds1 93 -> 79 us); 1 when that would leave fewer workgroups than ~4 per CU.
 // OUT: 0 = f16, 1 = e4m3 bytes, 2 = fp32 (a LayerNorm whose result IS the residual stream: CLIP's ln_pre)
-template <int NV, int LN_ROWS, int OUT = 0>
+// SPLIT (OUT 0 only; its own instantiations, the plain ones stay as they are): the row pitch is 2 c, columns [0, c) hold hi = f16(y), bit
+// for bit the plain kernel's output, columns [c, 2 c) hold lo = f16(y - f32(hi)): a split-precision A operand for [W | W] weights
+template <int NV, int LN_ROWS, int OUT = 0, bool SPLIT = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta,
@@ -406,10 +408,15 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             if constexpr (OUT == 1) *(int*)((uint8_t*)out + row * ld_out + i * 4) = pack_fp8x4(y[0], y[1], y[2], y[3]);
             else *(f32x4*)((float*)out + row * ld_out + i * 4) = f32x4{y[0], y[1], y[2], y[3]};
           } else {
-            half4_t h;
+            half4_t h, l;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) h[r] = (half_t)((v[k][r] - mean) * rstd * g4[r] + b4[r]);
+            for (int r = 0; r < 4; ++r) {
+              const float y = (v[k][r] - mean) * rstd * g4[r] + b4[r];
+              h[r] = (half_t)y;
+              if constexpr (SPLIT) l[r] = (half_t)(y - (float)h[r]);
+            }
             *(half4_t*)(orow + i * 4) = h;
+            if constexpr (SPLIT) *(half4_t*)(orow + c + i * 4) = l;
           }
         }
       }
@@ -540,16 +547,16 @@ extern "C" int seva_groupnorm_f16(const seva_groupnorm_desc* d, seva_stream_t st
 }
 
 namespace {
-template <int OUT>
+template <int OUT, bool SPLIT = false>
 int layernorm_entry(const float* x, const float* gamma, const float* beta, void* out, int64_t rows, int32_t c, float eps,
                     seva_stream_t stream, int64_t ld_out = 0) {
   SEVA_REQUIRE(x && gamma && beta && out, "layernorm: null pointer");
-  if (ld_out <= 0) ld_out = c;
+  if (ld_out <= 0) ld_out = SPLIT ? 2 * (int64_t)c : c;
   SEVA_REQUIRE(ld_out >= c && ld_out % 4 == 0, "layernorm: output row pitch %lld invalid", (long long)ld_out);
   SEVA_REQUIRE(rows > 0 && c > 0 && c % 4 == 0 && c <= 16 * 4 * LN_MAXV,
                "layernorm: rows=%lld c=%d unsupported", (long long)rows, c);
   hipStream_t s = (hipStream_t)stream;
-  SevaProfScope prof(3, (double)rows * c * (OUT == 1 ? 5.0 : OUT == 2 ? 8.0 : 6.0), s);
+  SevaProfScope prof(3, (double)rows * c * (OUT == 1 ? 5.0 : OUT == 2 || SPLIT ? 8.0 : 6.0), s);
   const int lr = rows >= 64 * 1024 ? 4 : 1;
   const int64_t blocks = (rows + 16 * lr - 1) / (16 * lr);
   SEVA_REQUIRE(blocks <= 0x7fffffff, "layernorm: too many rows");
@@ -557,10 +564,10 @@ int layernorm_entry(const float* x, const float* gamma, const float* beta, void*
 #define SEVA_LN_LAUNCH(NV)                                                                                  \
   do {                                                                                                      \
     if (lr == 4)                                                                                            \
-      hipLaunchKernelGGL((layernorm_kernel<NV, 4, OUT>), dim3((unsigned)blocks), dim3(256), 0, s, x, gamma,  \
+      hipLaunchKernelGGL((layernorm_kernel<NV, 4, OUT, SPLIT>), dim3((unsigned)blocks), dim3(256), 0, s, x, gamma,  \
                          beta, (half_t*)out, rows, c, eps, ld_out);                                         \
     else                                                                                                    \
-      hipLaunchKernelGGL((layernorm_kernel<NV, 1, OUT>), dim3((unsigned)blocks), dim3(256), 0, s, x, gamma,  \
+      hipLaunchKernelGGL((layernorm_kernel<NV, 1, OUT, SPLIT>), dim3((unsigned)blocks), dim3(256), 0, s, x, gamma,  \
                          beta, (half_t*)out, rows, c, eps, ld_out);                                         \
   } while (0)
   if (nv <= 2) SEVA_LN_LAUNCH(2);
@@ -576,6 +583,13 @@ extern "C" int seva_layernorm_f16(const float* x, const float* gamma, const floa
                                   void* out_f16, int64_t rows, int32_t c, float eps,
                                   seva_stream_t stream) {
   return layernorm_entry<0>(x, gamma, beta, out_f16, rows, c, eps, stream);
+}
+
+// split-precision output: out_f16 is [rows][2 c] = [hi | lo], hi bitwise seva_layernorm_f16's output, lo = f16(y - f32(hi))
+extern "C" int seva_layernorm_f16_split(const float* x, const float* gamma, const float* beta,
+                                        void* out_f16, int64_t rows, int32_t c, float eps,
+                                        seva_stream_t stream) {
+  return layernorm_entry<0, true>(x, gamma, beta, out_f16, rows, c, eps, stream);
 }
 
 // same normalisation, output as OCP e4m3 bytes (saturating): A operand of seva_gemm_fp8

@@ -84,6 +84,33 @@ def interleave_geglu(w: torch.Tensor, b: torch.Tensor):
     return wi.contiguous(), bi.contiguous()
 
 
+# Split-precision operand classes (SEVA_SPLIT_PRECISION / Seva.set_precision(split=...)): the operand travels as [hi | lo] f16 pairs
+# against weights duplicated [W | W] -- K doubles, no consumer kernel changes
+SPLIT_TOKENS = ("stem", "head", "skip", "skip_deep", "conv", "resample", "proj_in", "proj_out", "qkv", "ff")
+SPLIT_ALL = frozenset(t for t in SPLIT_TOKENS if t != "skip_deep")  # "all" ("skip" covers "skip_deep")
+SPLIT_DEFAULT = "stem,head,skip_deep"
+
+
+def parse_split(spec, strict: bool = False) -> set:
+    """Token set of a split-precision request: a comma list (or a sequence) of SPLIT_TOKENS, "all" = every class, "none" / "" = every
+    operand plain fp16.  strict (the `split=` keyword): an unknown token is a ValueError; the environment variable stays lenient."""
+    toks = [t.strip() for t in (spec.split(",") if isinstance(spec, str) else list(spec))]
+    toks = [t for t in toks if t]
+    if strict:
+        bad = [t for t in toks if t not in SPLIT_TOKENS + ("all", "none")]
+        if bad:
+            raise ValueError(f"unknown split-precision token(s) {bad} (any of {', '.join(SPLIT_TOKENS)}, or all / none)")
+    out = set(toks)
+    if "all" in out:
+        out = (out - {"all"}) | SPLIT_ALL
+    return out
+
+
+def dup_k(w: torch.Tensor) -> torch.Tensor:
+    """[N, K] -> [N, 2K] = [W | W]: the weights a split-precision [hi | lo] operand meets."""
+    return torch.cat([w, w], 1).contiguous()
+
+
 class _Arena:
     """Shape-keyed buffer cache: the second forward of a shape allocates nothing."""
 
@@ -104,6 +131,8 @@ class _Arena:
 
 
 class SevaEngine:
+    split: frozenset = frozenset()  # split-precision operand classes; set per instance in __init__ (an engine built without it: none)
+
     @staticmethod
     def _resolve_device(model) -> torch.device:
         params = [p for p in model.parameters()]
@@ -117,11 +146,12 @@ class SevaEngine:
         _native.load()
         return params[0].device
 
-    def __init__(self, model, precision: str | None = None, attention: str | None = None, ff: str | None = None):
+    def __init__(self, model, precision: str | None = None, attention: str | None = None, ff: str | None = None, split=None):
         """precision "f16" (default; the parity mode, fp16 operands / fp32 accumulation) or "fp8" (BASELINE config 5:
         e4m3 weights AND activations on the block-scaled fp8 MFMA for the QKV / GEGLU / FF2 projections and the ResBlock 3x3
         convs whose reduction length is a multiple of 128 -- the C = 640 / 1280 levels; the C = 320 level (opt-in through
-        zero-padding, SEVA_FP8_PAD=1: no gain, see below), attention, the small projections and the resampling convs stay f16)."""
+        zero-padding, SEVA_FP8_PAD=1: no gain, see below), attention, the small projections and the resampling convs stay f16).
+        split (f16 only): the split-precision operand classes (`parse_split`); None leaves the choice to SEVA_SPLIT_PRECISION."""
         import os as _os
 
         self.device = self._resolve_device(model)
@@ -171,8 +201,16 @@ class SevaEngine:
         # comma list of "stem", "head", "skip" / "skip_deep"; "none" = every operand plain fp16 (the round-2 numerics).
         # "skip_deep" = the skip convs below the top level only (cout >= 640: 11 of the 14, where M is small and the doubled K and
         # the extra lo half of the raw input cost ~0.3 ms per step; the three 72x72 ones cost ~0.8 ms for 3.6e-4 of the error budget).
-        sp = _os.environ.get("SEVA_SPLIT_PRECISION", "stem,head,skip_deep")
-        self.split = {t for t in sp.split(",") if t} if not self.fp8 else set()
+        # The further classes finish the scheme ("all": the near-fp32 mode, every GEMM / conv A operand of the UNet but attention's and
+        # the time-embedding MLP's): "conv" (both 3x3 convs of every ResBlock), "resample" (the Down / Upsample convs), "proj_in",
+        # "proj_out", "qkv", "ff" (GEGLU-in and FF2; the C <= 320 feed-forwards then take the two-kernel path: the fused kernel has no
+        # split hidden tensor).  Each is a per-layer decision from per-sample dimensions only (batch invariance holds).
+        if split is not None:
+            if self.fp8:
+                raise ValueError('split precision needs precision "f16" (the fp8 mode has no split operands)')
+            self.split = parse_split(split, strict=True)
+        else:  # (fp8 mode: the environment variable is ignored)
+            self.split = parse_split(_os.environ.get("SEVA_SPLIT_PRECISION", SPLIT_DEFAULT)) if not self.fp8 else set()
         self.p = model.params
         self.layout: Layout = model._layout
         self.arena = _Arena(self.device)
@@ -237,10 +275,14 @@ class SevaEngine:
                 w = torch.cat([w, w.new_zeros((w.shape[0], kp - k))], 1)
             W[name + "8"], W[name + "8e"] = ops.quantize_weight_fp8(w)
 
+        sp = self.split
+
         def pack_attn_self(pfx):
             W[pfx + ".qkv"] = torch.cat(
                 [f16(pfx + ".to_q.weight"), f16(pfx + ".to_k.weight"), f16(pfx + ".to_v.weight")], 0
             ).contiguous()
+            if "qkv" in sp:  # the LayerNorm output arrives as [hi | lo]
+                W[pfx + ".qkv"] = dup_k(W[pfx + ".qkv"])
             q8(pfx + ".qkv", torch.cat([f32(pfx + ".to_q.weight"), f32(pfx + ".to_k.weight"), f32(pfx + ".to_v.weight")], 0))
             W[pfx + ".out.w"], W[pfx + ".out.b"] = f16(pfx + ".to_out.0.weight"), f32(pfx + ".to_out.0.bias")
 
@@ -260,6 +302,8 @@ class SevaEngine:
             wi, bi = interleave_geglu(f16(pfx + ".net.0.proj.weight"), f32(pfx + ".net.0.proj.bias"))
             W[pfx + ".w1"], W[pfx + ".b1"] = wi, bi
             W[pfx + ".w2"], W[pfx + ".b2"] = f16(pfx + ".net.2.weight"), f32(pfx + ".net.2.bias")
+            if "ff" in sp:  # LayerNorm output and GEGLU hidden tensor arrive as [hi | lo]
+                W[pfx + ".w1"], W[pfx + ".w2"] = dup_k(W[pfx + ".w1"]), dup_k(W[pfx + ".w2"])
             if self._ff_fused_fp8(wi.shape[1]):  # e4m3 copies for seva_ff_fused_fp8 (W1 zero-padded to KP, W2 column-permuted)
                 W[pfx + ".w1f8"], W[pfx + ".w1f8e"], W[pfx + ".w2f8"], W[pfx + ".w2f8e"] = ops.pack_ff_fp8(
                     interleave_geglu(f32(pfx + ".net.0.proj.weight"), f32(pfx + ".net.0.proj.bias"))[0], f32(pfx + ".net.2.weight"))
@@ -283,9 +327,12 @@ class SevaEngine:
                 assert spec.cin % 64 == 0 and spec.cout % 64 == 0, "channel counts must be multiples of 64"
                 pack_ln(pfx + ".in_layers.0")
                 pack_ln(pfx + ".out_layers.0")
-                W[pfx + ".conv1.w"] = pack_conv3x3(f32(pfx + ".in_layers.2.weight"))
+                wc1, wc2 = f32(pfx + ".in_layers.2.weight"), f32(pfx + ".out_layers.3.weight")
+                if "conv" in sp:  # [w | w] per tap: both GroupNorms write [hi | lo] channels
+                    wc1, wc2 = torch.cat([wc1, wc1], 1), torch.cat([wc2, wc2], 1)
+                W[pfx + ".conv1.w"] = pack_conv3x3(wc1)
                 W[pfx + ".conv1.b"] = f32(pfx + ".in_layers.2.bias")
-                W[pfx + ".conv2.w"] = pack_conv3x3(f32(pfx + ".out_layers.3.weight"))
+                W[pfx + ".conv2.w"] = pack_conv3x3(wc2)
                 W[pfx + ".conv2.b"] = f32(pfx + ".out_layers.3.bias")
                 if self.fp8:  # K = 9*cin_pad ordered (ky, kx, ci): a 128-deep K-tile must not straddle taps -> channels padded
                     for tag, key, ch in (("conv1", "in_layers.2", spec.cin), ("conv2", "out_layers.3", spec.cout)):
@@ -311,6 +358,10 @@ class SevaEngine:
                 pack_ln(pfx + ".norm")
                 W[pfx + ".proj_in.w"], W[pfx + ".proj_in.b"] = f16(pfx + ".proj_in.weight"), f32(pfx + ".proj_in.bias")
                 W[pfx + ".proj_out.w"], W[pfx + ".proj_out.b"] = f16(pfx + ".proj_out.weight"), f32(pfx + ".proj_out.bias")
+                if "proj_in" in sp:
+                    W[pfx + ".proj_in.w"] = dup_k(W[pfx + ".proj_in.w"])
+                if "proj_out" in sp:
+                    W[pfx + ".proj_out.w"] = dup_k(W[pfx + ".proj_out.w"])
                 for i in range(spec.depth):
                     b = f"{pfx}.transformer_blocks.{i}"
                     pack_attn_self(b + ".attn1")
@@ -326,10 +377,14 @@ class SevaEngine:
                     for n in ("norm_in", "norm1", "norm2", "norm3"):
                         pack_ln(f"{m}.{n}")
             elif spec.kind == "down":
-                W[pfx + ".w"], W[pfx + ".b"] = pack_conv3x3(f32(pfx + ".op.weight")), f32(pfx + ".op.bias")
+                wr = f32(pfx + ".op.weight")
+                W[pfx + ".w"], W[pfx + ".b"] = pack_conv3x3(torch.cat([wr, wr], 1) if "resample" in sp else wr), f32(pfx + ".op.bias")
             elif spec.kind == "up":
-                W[pfx + ".w"], W[pfx + ".b"] = pack_conv3x3(f32(pfx + ".conv.weight")), f32(pfx + ".conv.bias")
-                W[pfx + ".w4"] = combine_up_phases(f32(pfx + ".conv.weight"))  # ops.conv3x3_up_phases (_resample)
+                wr = f32(pfx + ".conv.weight")
+                if "resample" in sp:  # duplicated along cin, also under the phase operator's taps
+                    wr = torch.cat([wr, wr], 1)
+                W[pfx + ".w"], W[pfx + ".b"] = pack_conv3x3(wr), f32(pfx + ".conv.bias")
+                W[pfx + ".w4"] = combine_up_phases(wr)  # ops.conv3x3_up_phases (_resample)
         pack_ln("out.0")
         wh = f32("out.2.weight")
         W["out.2.w"] = pack_conv3x3(torch.cat([wh, wh], 1) if "head" in self.split else wh)  # head input [hi | lo] per tap
@@ -387,7 +442,11 @@ class SevaEngine:
             return None, None
         return s1, s2
 
-    def _ln(self, x, pfx, rows, c, fp8=False):
+    def _ln(self, x, pfx, rows, c, fp8=False, split=False):
+        if split:  # [hi | lo] for duplicated weights
+            out = self._buf("ln16s", (rows, 2 * c), F16)
+            ops.layernorm_split(x, self.W[pfx + ".g"], self.W[pfx + ".b"], out)
+            return out
         if fp8:
             # e4m3 output, K padded to a multiple of 128: the pad columns are zeroed once (nothing ever writes them again)
             out = self._buf("ln8", (rows, _pad128(c)), U8, zero=True)
@@ -428,6 +487,19 @@ class SevaEngine:
             ops.gemm(h8, W[ff_pfx + ".w28"], w_exp=W[ff_pfx + ".w28e"], bias=W[ff_pfx + ".b2"], residual=residual,
                      out_f32=out_f32, out_f16=out_f16)
             return
+        sp_ff = "ff" in self.split
+        sp_o16 = out_f16 is not None and "proj_out" in self.split  # out_f16 is `last16`, proj_out's operand
+        if sp_ff or sp_o16:
+            # split precision: the two-kernel path at every width (the fused kernel has neither a split hidden tensor nor a split out_f16)
+            if self._slice_rows(rows, c, unit) < rows:
+                raise SevaNativeError("split-precision feed-forwards do not run frame-sliced (SEVA_SLICE_FRAMES)")
+            a = self._ln(x32, ln_pfx, rows, c, split=sp_ff)
+            hidden = self._buf("ffhs" if sp_ff else "ffh", (rows, (8 if sp_ff else 4) * c), F16)
+            (ops.gemm_split_out if sp_ff else ops.gemm)(a, W[ff_pfx + ".w1"], bias=W[ff_pfx + ".b1"], out_f16=hidden, geglu=True,
+                                                      **({"alg_k": c} if sp_ff else {}))
+            (ops.gemm_split_out if sp_o16 else ops.gemm)(hidden, W[ff_pfx + ".w2"], bias=W[ff_pfx + ".b2"], residual=residual,
+                                                       out_f32=out_f32, out_f16=out_f16, **({"alg_k": 4 * c} if sp_ff else {}))
+            return
         if self.ff_fused and c in ops.FF_FUSED_CHANNELS:
             # narrow levels (ds1: C = 320): GEGLU -> FF2 in ONE kernel, the 4C-wide hidden tensor never exists in HBM
             # ... and its LayerNorm runs in that kernel's prologue (x32 rows read as fp32, normalised in registers)
@@ -454,7 +526,9 @@ class SevaEngine:
         W, pfx, hw = self.W, spec.prefix, h * w
         cin, cout = spec.cin, spec.cout
         f8_1, f8_2 = pfx + ".conv1.w8" in W, pfx + ".conv2.w8" in W  # fp8 mode: the conv consumes e4m3 activations
-        a16 = None if f8_1 else self._buf("gn16", (n, hw, cin), F16)
+        sp_conv = "conv" in self.split  # both GroupNorms write [hi | lo] channels, the convs see 2 cin / 2 cout input channels
+        k1, k2 = (2 * cin, 2 * cout) if sp_conv else (cin, cout)
+        a16 = None if f8_1 else self._buf("gn16", (n, hw, k1), F16)
         cin8, cout8 = _pad128(cin), _pad128(cout)  # fp8 convs see channel counts padded to a multiple of 128 (pad stays zero)
         a8 = self._buf("gn8", (n, hw, cin8), U8, zero=True) if f8_1 else None
         # the 1x1 skip conv (cin != cout) consumes the raw input as f16: emitted by the same GroupNorm pass
@@ -463,7 +537,7 @@ class SevaEngine:
         s1, s2 = self._gn_stats(x1, x2)
         ops.groupnorm(x1, x2, W[pfx + ".in_layers.0.g"], W[pfx + ".in_layers.0.b"], a16, self.gn_ws,
                       eps=1e-5, silu=True, dense=dense, dense_w=W[pfx + ".dense.w"], dense_b=W[pfx + ".dense.b"],
-                      raw_f16=xs16, out_f8=a8, stats1=s1, stats2=s2, split_raw=sp_skip)
+                      raw_f16=xs16, out_f8=a8, stats1=s1, stats2=s2, split_raw=sp_skip, **({"split_out": True} if sp_conv else {}))
         hmid = self._buf("res_mid", (n, hw, cout), F32)
         st_mid = self._stats_buf("res_mid", n * hw, hw, cout)
         off = self.emb_off[pfx]
@@ -471,13 +545,13 @@ class SevaEngine:
             ops.conv3x3(a8.view(n, h, w, cin8), W[pfx + ".conv1.w8"], w_exp=W[pfx + ".conv1.w8e"], bias=W[pfx + ".conv1.b"],
                         row_add=emb_all[:, off:], rows_per_group=hw, ld_row_add=self.emb_total, out_f32=hmid, ch_stats=st_mid)
         else:
-            ops.conv3x3(a16.view(n, h, w, cin), W[pfx + ".conv1.w"], bias=W[pfx + ".conv1.b"],
+            ops.conv3x3(a16.view(n, h, w, k1), W[pfx + ".conv1.w"], bias=W[pfx + ".conv1.b"],
                         row_add=emb_all[:, off:], rows_per_group=hw, ld_row_add=self.emb_total, out_f32=hmid, ch_stats=st_mid,
-                        splitk_ws=self._sk(n * hw, hw, cout))
-        b16 = None if f8_2 else self._buf("gn16", (n, hw, cout), F16)
+                        splitk_ws=self._sk(n * hw, hw, cout), **({"alg_k": 9 * cin} if sp_conv else {}))
+        b16 = None if f8_2 else self._buf("gn16", (n, hw, k2), F16)
         b8 = self._buf("gn8", (n, hw, cout8), U8, zero=True) if f8_2 else None
         ops.groupnorm(hmid, None, W[pfx + ".out_layers.0.g"], W[pfx + ".out_layers.0.b"], b16, self.gn_ws,
-                      eps=1e-5, silu=True, out_f8=b8, stats1=st_mid)
+                      eps=1e-5, silu=True, out_f8=b8, stats1=st_mid, **({"split_out": True} if sp_conv else {}))
         fold = cin != cout and self.fold_skip and not f8_2 and (hw > 128 or not self.conv_splitk)
         if fold:
             res = None
@@ -490,14 +564,15 @@ class SevaEngine:
         out = self._buf("out:" + pfx, (n, hw, cout), F32)
         st_out = self._stats_buf("out:" + pfx, n * hw, hw, cout)
         if fold:
-            ops.conv3x3(b16.view(n, h, w, cout), W[pfx + ".conv2.wf"], bias=W[pfx + ".conv2.bf"], a2=xs16, out_f32=out,
+            ops.conv3x3(b16.view(n, h, w, k2), W[pfx + ".conv2.wf"], bias=W[pfx + ".conv2.bf"], a2=xs16, out_f32=out,
                         ch_stats=st_out)
         elif f8_2:
             ops.conv3x3(b8.view(n, h, w, cout8), W[pfx + ".conv2.w8"], w_exp=W[pfx + ".conv2.w8e"], bias=W[pfx + ".conv2.b"],
                         residual=res, out_f32=out, ch_stats=st_out)
         else:
-            ops.conv3x3(b16.view(n, h, w, cout), W[pfx + ".conv2.w"], bias=W[pfx + ".conv2.b"],
-                        residual=res, out_f32=out, ch_stats=st_out, splitk_ws=self._sk(n * hw, hw, cout))
+            ops.conv3x3(b16.view(n, h, w, k2), W[pfx + ".conv2.w"], bias=W[pfx + ".conv2.b"],
+                        residual=res, out_f32=out, ch_stats=st_out, splitk_ws=self._sk(n * hw, hw, cout),
+                        **({"alg_k": 9 * cout} if sp_conv else {}))
         self._produced(out, st_out)
         return out
 
@@ -506,6 +581,9 @@ class SevaEngine:
         """Attention.forward (self), reference transformer.py:59-74, + residual (+ folded attn2)."""
         W = self.W
         c3 = 3 * c
+        sp_qkv = "qkv" in self.split  # the LayerNorm output travels as [hi | lo]; q / k / v themselves stay f16
+        if sp_qkv and regime == "frame" and self.slice_attn and self._slice_rows(rows, c, hw) < rows:
+            raise SevaNativeError("the split-precision QKV projection does not run frame-sliced (SEVA_SLICE_ATTN)")
         if regime == "frame" and self.slice_attn and self._slice_rows(rows, c, hw) < rows:
             # per-frame attention: the whole chain LN -> QKV -> attention -> out-projection runs a few frames at a time
             step = self._slice_rows(rows, c, hw)
@@ -532,8 +610,8 @@ class SevaEngine:
             a8 = self._ln(x32, ln_pfx, rows, c, fp8=True)
             ops.gemm(a8, W[at_pfx + ".qkv8"], w_exp=W[at_pfx + ".qkv8e"], out_f16=qkv, col_scale=QK_SCALE_LOG2E, col_scale_n=c)
         else:
-            a = self._ln(x32, ln_pfx, rows, c)
-            ops.gemm(a, W[at_pfx + ".qkv"], out_f16=qkv, col_scale=QK_SCALE_LOG2E, col_scale_n=c)
+            a = self._ln(x32, ln_pfx, rows, c, split=sp_qkv)
+            ops.gemm(a, W[at_pfx + ".qkv"], out_f16=qkv, col_scale=QK_SCALE_LOG2E, col_scale_n=c, **({"alg_k": c} if sp_qkv else {}))
         att = self._buf("att", (rows, c), F16)
         q, k, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
         if regime == "frame":  # batch = frame, tokens = pixels
@@ -584,11 +662,13 @@ class SevaEngine:
         """MultiviewTransformer.forward, reference transformer.py:215-247."""
         W, pfx, hw, c, heads = self.W, spec.prefix, h * w, spec.channels, spec.heads
         rows = n * hw
-        g16 = self._buf("gn16", (n, hw, c), F16)
+        sp_in, sp_out = "proj_in" in self.split, "proj_out" in self.split
+        cs = 2 * c if sp_in else c
+        g16 = self._buf("gn16", (n, hw, cs), F16)
         ops.groupnorm(x, None, W[pfx + ".norm.g"], W[pfx + ".norm.b"], g16, self.gn_ws, eps=1e-6, silu=False,
-                      stats1=self._gn_stats(x, None)[0])
+                      stats1=self._gn_stats(x, None)[0], **({"split_out": True} if sp_in else {}))
         cur = self._buf("t_h", (rows, c), F32)
-        ops.gemm(g16.view(rows, c), W[pfx + ".proj_in.w"], bias=W[pfx + ".proj_in.b"], out_f32=cur)
+        ops.gemm(g16.view(rows, cs), W[pfx + ".proj_in.w"], bias=W[pfx + ".proj_in.b"], out_f32=cur, **({"alg_k": c} if sp_in else {}))
         collapse = lc == 1
         ldra_frame, ldra_scene = self.ctx_total, T * self.ctx_total
         last16 = None
@@ -638,27 +718,29 @@ class SevaEngine:
             # x = x_spatial + ff(norm3 x_mix)   (time-mix ff has no residual; SkipConnect adds)
             final = i == spec.depth - 1
             nxt = None if final else self._buf("t_h", (rows, c), F32)
-            last16 = self._buf("t_h16", (rows, c), F16)
+            last16 = self._buf("t_h16", (rows, 2 * c if sp_out else c), F16)  # (split: [hi | lo], written by _ff's FF2)
             self._ff(m2, m + ".norm3", m + ".ff", rows, c, residual=h2, out_f32=nxt, out_f16=last16, unit=hw)
             cur = nxt
         out = self._buf("out:" + pfx, (n, hw, c), F32)
         st_out = self._stats_buf("out:" + pfx, rows, hw, c)
         ops.gemm(last16, W[pfx + ".proj_out.w"], bias=W[pfx + ".proj_out.b"], residual=x.view(rows, c),
-                 out_f32=out.view(rows, c), ch_stats=st_out)
+                 out_f32=out.view(rows, c), ch_stats=st_out, **({"alg_k": c} if sp_out else {}))
         self._produced(out, st_out)
         return out
 
     def _resample(self, spec, x, n, h, w):
         """Downsample (layers.py:49-58) / Upsample (layers.py:35-46)."""
         c = spec.channels
-        x16 = self._buf("rs16", (n, h, w, c), F16)
-        ops.cast_concat_f16(x, None, x16)
+        sp_rs = "resample" in self.split
+        x16 = self._buf("rs16", (n, h, w, 2 * c if sp_rs else c), F16)
+        (ops.cast_concat_f16_split if sp_rs else ops.cast_concat_f16)(x, None, x16)
+        ak = {"alg_k": 9 * c} if sp_rs else {}
         if spec.kind == "down":
             oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
             out = self._buf("out:" + spec.prefix, (n, oh * ow, c), F32)
             st_out = self._stats_buf("out:" + spec.prefix, n * oh * ow, oh * ow, c)
             ops.conv3x3(x16, self.W[spec.prefix + ".w"], stride=2, bias=self.W[spec.prefix + ".b"], out_f32=out, ch_stats=st_out,
-                        splitk_ws=self._sk(n * oh * ow, oh * ow, c))
+                        splitk_ws=self._sk(n * oh * ow, oh * ow, c), **ak)
         else:
             oh, ow = 2 * h, 2 * w
             out = self._buf("out:" + spec.prefix, (n, oh * ow, c), F32)
@@ -671,7 +753,7 @@ class SevaEngine:
             else:
                 st_out = self._stats_buf("out:" + spec.prefix, n * oh * ow, oh * ow, c)
                 ops.conv3x3(x16, self.W[spec.prefix + ".w"], upsample=True, bias=self.W[spec.prefix + ".b"], out_f32=out,
-                            ch_stats=st_out)
+                            ch_stats=st_out, **ak)
         self._produced(out, st_out)
         return out, oh, ow
 

@@ -85,6 +85,7 @@ SYMBOLS = {
     "seva_abi_version": (c_int, []),
     "seva_target_arch": (c_char_p, []),
     "seva_gemm_f16": (c_int, [POINTER(GemmDesc), c_void_p]),
+    "seva_gemm_f16_split_out": (c_int, [POINTER(GemmDesc), c_void_p]),
     "seva_gemm_fp8": (c_int, [POINTER(GemmDesc), c_void_p]),
     "seva_ff_fused_f16": (c_int, [POINTER(FfDesc), c_void_p]),
     "seva_ff_fused_fp8": (c_int, [POINTER(FfDesc), c_void_p]),
@@ -94,6 +95,7 @@ SYMBOLS = {
     "seva_attention_pv8": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p]),
     "seva_groupnorm_f16": (c_int, [POINTER(GroupNormDesc), c_void_p]),
     "seva_layernorm_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
+    "seva_layernorm_f16_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
     "seva_layernorm_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_int64, c_void_p]),
     "seva_layernorm_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
     "seva_clip_preprocess_f16": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
@@ -105,6 +107,7 @@ SYMBOLS = {
     "seva_nchw_to_nhwc_f16_split": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "seva_nhwc_to_nchw_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "seva_cast_concat_f16": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    "seva_cast_concat_f16_split": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "seva_bilinear_to_nhwc_f32": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "seva_timestep_embedding_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "seva_silu_f16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -159,16 +159,26 @@ class Seva(nn.Module):
             from ._engine import SevaEngine
 
             self._engine = SevaEngine(self, getattr(self, "_precision", None), getattr(self, "_attention", None),
-                                      getattr(self, "_ff_precision", None))
+                                      getattr(self, "_ff_precision", None), getattr(self, "_split", None))
         return self._engine
 
-    def set_precision(self, precision: str, attention: str | None = None, ff: str | None = None) -> "Seva":
+    def set_precision(self, precision: str, attention: str | None = None, ff: str | None = None, split=None) -> "Seva":
         """"f16" (default, the parity mode) or "fp8" (BASELINE config 5: e4m3 operands on the fp8 MFMA where the reduction
         length allows; separate accuracy class).  Re-packs the weights on the next forward.
         attention (fp8 mode only): "f16" (default) or "fp8" -- the long self-attention launches (L >= 2048) with P and V in e4m3
         (seva_attention_pv8), an accuracy class of its own; None leaves the choice to SEVA_FP8_ATTENTION (0 / 1, default 0).
         ff (fp8 mode only): "f16" (default) or "fp8" -- the feed-forwards that run the fused f16 kernel in fp8 mode (the C = 320
-        level) on its e4m3 sibling (seva_ff_fused_fp8); None leaves the choice to SEVA_FP8_FF (0 / 1, default 0)."""
+        level) on its e4m3 sibling (seva_ff_fused_fp8); None leaves the choice to SEVA_FP8_FF (0 / 1, default 0).
+        split (f16 mode only): the operand classes that travel in split precision ([hi | lo] f16 pairs against duplicated weights,
+        DESIGN.md section 2) -- "all" (the near-fp32 mode: about twice the GEMM / conv work), a comma list or sequence of stem, head,
+        skip, skip_deep, conv, resample, proj_in, proj_out, qkv, ff, or "none"; an unknown token is a ValueError.  It wins over
+        SEVA_SPLIT_PRECISION; None leaves the choice to that variable (default stem,head,skip_deep)."""
+        if split is not None:
+            from ._engine import parse_split
+
+            if precision != "f16":
+                raise ValueError('split precision needs precision "f16" (the fp8 mode has no split operands)')
+            parse_split(split, strict=True)  # unknown tokens: ValueError here, not at the next forward
         if attention not in (None, "f16", "fp8"):
             raise ValueError(f"unknown attention {attention!r} (f16 | fp8)")
         if attention == "fp8" and precision != "fp8":
@@ -180,6 +190,7 @@ class Seva(nn.Module):
         self._precision = precision
         self._attention = attention
         self._ff_precision = ff
+        self._split = split
         self._engine = None
         return self
 

@@ -42,8 +42,11 @@ def gemm(
     ch_stats: torch.Tensor | None = None,
     splitk_ws: torch.Tensor | None = None,
     alg_k: int = 0,
+    split_out: bool = False,
 ) -> None:
     """out = a @ w.T (+bias +row_add[group] +residual); a:[M,K] f16, w:[N,K] f16 (seva_gemm_f16).
+    split_out (seva_gemm_f16_split_out): out_f16 is [M, >= 2 NO] and receives [hi | lo] of the fp32 epilogue value (NO = N, GEGLU:
+    N / 2); f16 GEMM mode only -- with fp8 operands, out_f8 or ch_stats the call raises.
     alg_k: accounting only -- the reference-equivalent reduction length when K is padded / split-precision (seva_gemm_desc.alg_K).
     splitk_ws (`splitk_workspace`): only convolutions use it (seva_gemm_desc.splitk_ws); accepted and ignored for plain GEMMs.
     ch_stats (`channel_stats_buffer`): receives per-64-row-block, per-channel sum / sum of squares of out_f32 (GroupNorm
@@ -53,6 +56,8 @@ def gemm(
     out_f8 (GEGLU epilogue only) receives the hidden activations as e4m3."""
     fp8 = w_exp is not None
     require_cuda(a, w)
+    if split_out and (fp8 or out_f8 is not None or ch_stats is not None or out_f16 is None):
+        raise ValueError("gemm(split_out=True) is the f16 GEMM with an out_f16 (no fp8 operands, out_f8 or ch_stats)")
     assert a.dim() == 2 and w.dim() == 2 and a.dtype == w.dtype == (U8 if fp8 else F16)
     M, K = a.shape
     N = w.shape[0]
@@ -79,10 +84,17 @@ def gemm(
         d.w_exp, d.out_f8 = w_exp.data_ptr(), ptr(out_f8)
         d.ldo8 = out_f8.stride(0) if out_f8 is not None else 0
         check(_lib().seva_gemm_fp8(C.byref(d), stream_ptr(a.device)), "seva_gemm_fp8")
+    elif split_out:
+        assert out_f16.dtype == F16 and out_f16.stride(-1) == 1  # (a pitch below 2 NO is the library's error)
+        check(_lib().seva_gemm_f16_split_out(C.byref(d), stream_ptr(w.device)), "seva_gemm_f16_split_out")
     else:
         assert out_f8 is None
         check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(w.device)), "seva_gemm_f16")
 
+
+def gemm_split_out(a: torch.Tensor, w: torch.Tensor, **kw) -> None:
+    """`gemm` whose out_f16 is the split-precision operand [hi | lo] of the next GEMM (seva_gemm_f16_split_out)."""
+    gemm(a, w, split_out=True, **kw)
 
 
 STATS_ROWS = 64  # rows per block of the epilogue-emitted GroupNorm statistics (include/seva_hip.h: seva_gemm_desc.ch_stats)
@@ -543,6 +555,17 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_f16:
           "seva_layernorm_f16")
 
 
+def layernorm_split(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_f16: torch.Tensor, eps: float = 1e-5) -> None:
+    """LayerNorm over the last dim as a split-precision operand (seva_layernorm_f16_split): out_f16 [rows, 2 c] f16 = [hi | lo], hi
+    bitwise `layernorm`'s f16 output, lo = f16(y - f32(hi))."""
+    require_cuda(x, out_f16)
+    c = x.shape[-1]
+    rows = x.numel() // c
+    assert x.dtype == F32 and x.is_contiguous() and out_f16.dtype == F16 and out_f16.is_contiguous() and out_f16.numel() == 2 * rows * c
+    check(_lib().seva_layernorm_f16_split(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out_f16.data_ptr(), rows, c, eps,
+                                          stream_ptr(x.device)), "seva_layernorm_f16_split")
+
+
 def quantize_weight_fp8(w: torch.Tensor):
     """[N, K] weights -> (e4m3 bytes [N, K] uint8, E8M0 scale bytes [N] uint8): row n holds e4m3(w[n] * 2^-e[n]) with the
     power-of-two scale 2^e[n] chosen so that max|row| lands in (224, 448] (the top binade of e4m3); the scale byte is
@@ -628,6 +651,17 @@ def cast_concat_f16(x1: torch.Tensor, x2: torch.Tensor | None, out_f16: torch.Te
     c2 = x2.shape[-1] if x2 is not None else 0
     check(_lib().seva_cast_concat_f16(x1.data_ptr(), c1, ptr(x2), c2, out_f16.data_ptr(), rows,
                                       stream_ptr(x1.device)), "seva_cast_concat_f16")
+
+
+def cast_concat_f16_split(x1: torch.Tensor, x2: torch.Tensor | None, out_f16: torch.Tensor) -> None:
+    """`cast_concat_f16` as a split-precision operand (seva_cast_concat_f16_split): out_f16 [rows, 2 (c1 + c2)] = [f16(v) | f16(v - f32(f16(v)))]."""
+    require_cuda(x1, out_f16)
+    c1 = x1.shape[-1]
+    rows = x1.numel() // c1
+    c2 = x2.shape[-1] if x2 is not None else 0
+    assert out_f16.dtype == F16 and out_f16.is_contiguous() and out_f16.numel() == 2 * rows * (c1 + c2)
+    check(_lib().seva_cast_concat_f16_split(x1.data_ptr(), c1, ptr(x2), c2, out_f16.data_ptr(), rows,
+                                            stream_ptr(x1.device)), "seva_cast_concat_f16_split")
 
 
 def bilinear_to_nhwc(src: torch.Tensor, out: torch.Tensor, oh: int, ow: int) -> None:
