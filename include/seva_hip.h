@@ -377,6 +377,16 @@ int seva_add_noise_f32(const float* x, const float* eps, const float* noise_scal
 int seva_cfg_euler_f32(const float* x, const float* den2, const float* scale,
                        const float* sigma_hat, const float* dt, float* out, int32_t n, int64_t chw,
                        seva_stream_t stream);
+/* CFG + DPM-Solver++(2M) update in one pass (the `dpmpp2m` solver of seva/sampling.py; sgm's DPMPP2MSampler with
+ * mult1 = a, -mult2*mult3 = b, mult2*mult4 = c):
+ *   D = scale ? u + scale[n]*(cd - u) : den;   out = a[n]*x + b[n]*D + c[n]*old_den;   den_out = D
+ * scale != NULL: `den` = [2n][chw] with the uncond half first; scale == NULL: `den` = [n][chw], already combined.
+ * Where c[n] == 0 the history term is not evaluated at all (a select, not a multiply): a NaN/Inf in `old_den` cannot
+ * reach `out`.  old_den == NULL means "no history term"; the caller guarantees c[n] == 0 for every n then (the entry
+ * cannot check device values without a sync).  den_out may be NULL (D is not kept), may alias old_den; out may alias x. */
+int seva_cfg_multistep_f32(const float* x, const float* den, const float* scale, const float* old_den,
+                           const float* a, const float* b, const float* c, float* out, float* den_out,
+                           int32_t n, int64_t chw, seva_stream_t stream);
 
 /* Classifier-free guidance combine alone (ConstantGuidance, sampling.py:204-213):
  *   out = u + scale[n]*(c - u), den2 = [2n][chw] with the uncond half first. */

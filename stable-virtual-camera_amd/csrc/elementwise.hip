@@ -199,6 +199,33 @@ __global__ void cfg_euler_kernel(const float* __restrict__ x, const float* __res
   }
 }
 
+// DPM-Solver++(2M) update with the CFG combine in the same pass (include/seva_hip.h):
+//   D = scale ? u + scale[n]*(cd - u) : den;  out = a[n]*x + b[n]*D (+ c[n]*old_den where c[n] != 0);  den_out = D
+// c[n] == 0 SELECTS the two-term form: whatever an aborted trajectory left in the history buffer (NaN included) never reaches
+// `out`.  `out` may alias `x` and `den_out` may alias `old_den` (neither pair is __restrict__): every index is read before
+// it is written, by the one thread that owns it.
+__global__ void cfg_multistep_kernel(const float* x, const float* __restrict__ den,
+                                     const float* __restrict__ scale, const float* old_den,
+                                     const float* __restrict__ a, const float* __restrict__ b,
+                                     const float* __restrict__ c, float* out, float* den_out, int n,
+                                     int64_t chw) {
+  const int64_t total = (int64_t)n * chw;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int img = (int)(i / chw);
+    float d = den[i];
+    if (scale) {
+      const float cd = den[total + i];
+      d = d + scale[img] * (cd - d);
+    }
+    const float cc = c[img];
+    float r = a[img] * x[i] + b[img] * d;
+    if (old_den && cc != 0.f) r += cc * old_den[i];
+    if (den_out) den_out[i] = d;
+    out[i] = r;
+  }
+}
+
 __global__ void cfg_combine_kernel(const float* __restrict__ den2, const float* __restrict__ scale,
                                    float* __restrict__ out, int n, int64_t chw) {
   const int64_t total = (int64_t)n * chw;
@@ -400,6 +427,16 @@ extern "C" int seva_cfg_euler_f32(const float* x, const float* den2, const float
                "cfg_euler: bad args");
   SevaProfScope prof(4, (double)n * chw * 16.0, (hipStream_t)stream);
   EW_LAUNCH(cfg_euler_kernel, (int64_t)n * chw, x, den2, scale, sigma_hat, dt, out, n, chw);
+}
+
+extern "C" int seva_cfg_multistep_f32(const float* x, const float* den, const float* scale,
+                                      const float* old_den, const float* a, const float* b,
+                                      const float* c, float* out, float* den_out, int32_t n,
+                                      int64_t chw, seva_stream_t stream) {
+  SEVA_REQUIRE(x && den && a && b && c && out && n > 0 && chw > 0, "cfg_multistep: bad args");
+  const int streams = 2 + (scale ? 2 : 1) + (old_den ? 1 : 0) + (den_out ? 1 : 0);  // x, out, den, history in and out
+  SevaProfScope prof(4, (double)n * chw * 4.0 * streams, (hipStream_t)stream);
+  EW_LAUNCH(cfg_multistep_kernel, (int64_t)n * chw, x, den, scale, old_den, a, b, c, out, den_out, n, chw);
 }
 
 extern "C" int seva_cfg_combine_f32(const float* den2, const float* scale, float* out, int32_t n,

@@ -726,6 +726,32 @@ def cfg_euler(x: torch.Tensor, den2: torch.Tensor, scale: torch.Tensor, sigma_ha
                                     x.numel() // n, stream_ptr(x.device)), "seva_cfg_euler_f32")
 
 
+def cfg_multistep(x: torch.Tensor, den: torch.Tensor, scale: torch.Tensor | None, old_den: torch.Tensor | None,
+                  a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, out: torch.Tensor,
+                  den_out: torch.Tensor | None = None) -> None:
+    """out = a[n]*x + b[n]*D + c[n]*old_den and den_out = D in one pass (seva_cfg_multistep_f32), D = u + scale[n]*(cd - u)
+    from `den` = [uncond ; cond] when `scale` is given, D = `den` when it is None.  Rows with c[n] == 0 never read their
+    history; `old_den=None` is for calls in which every c[n] is 0 (caller's contract).  `den_out` may be `old_den`, `out` may be `x`."""
+    require_cuda(x, den, scale, old_den, a, b, c, out, den_out)
+    n = x.shape[0]
+    for name, t in (("x", x), ("den", den), ("scale", scale), ("old_den", old_den), ("a", a), ("b", b), ("c", c),
+                    ("out", out), ("den_out", den_out)):
+        if t is not None and (t.dtype != F32 or not t.is_contiguous()):
+            raise nv.SevaNativeError(f"cfg_multistep: {name} must be contiguous float32 (got {t.dtype}, strides {t.stride()})")
+    for name, t in (("old_den", old_den), ("out", out), ("den_out", den_out)):
+        if t is not None and t.shape != x.shape:
+            raise nv.SevaNativeError(f"cfg_multistep: {name} has shape {tuple(t.shape)}, x has {tuple(x.shape)}")
+    want = ((2 * n if scale is not None else n),) + tuple(x.shape[1:])
+    if tuple(den.shape) != want:
+        raise nv.SevaNativeError(f"cfg_multistep: den has shape {tuple(den.shape)}, expected {want}")
+    for name, t in (("scale", scale), ("a", a), ("b", b), ("c", c)):
+        if t is not None and t.numel() != n:
+            raise nv.SevaNativeError(f"cfg_multistep: {name} has {t.numel()} entries for {n} images")
+    check(_lib().seva_cfg_multistep_f32(x.data_ptr(), den.data_ptr(), ptr(scale), ptr(old_den), a.data_ptr(),
+                                        b.data_ptr(), c.data_ptr(), out.data_ptr(), ptr(den_out), n,
+                                        x.numel() // max(n, 1), stream_ptr(x.device)), "seva_cfg_multistep_f32")
+
+
 def cfg_combine(den2: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> None:
     require_cuda(den2, scale, out)
     n = out.shape[0]

@@ -190,9 +190,11 @@ def second_pass_schedule(n_windows: int, world: int, cfg_split: bool) -> list[li
 
 def run_window(win: Window, latents_of: dict, denoise_net: Callable, c2ws, Ks, *, hw, num_steps, cfg, cfg_min, guider,
                camera_scale, noise: torch.Tensor, step_seed: int, clip_token: torch.Tensor, device,
-               sampler_hook: Callable | None = None, cfg_split: tuple | None = None) -> torch.Tensor:
+               sampler_hook: Callable | None = None, cfg_split: tuple | None = None,
+               solver: str | None = None) -> torch.Tensor:
     """One window = the reference's get_value_dict + do_sample (eval.py:1152-1321) on this package's parts.
-    `latents_of[frame_id]` -> (4,h,w) latent of every conditioning frame.  Returns the (T,4,h,w) sample."""
+    `latents_of[frame_id]` -> (4,h,w) latent of every conditioning frame.  Returns the (T,4,h,w) sample.
+    `solver`: `EulerEDMSampler(solver=...)` ("euler", "dpmpp2m"; None = SEVA_SOLVER, default "euler")."""
     T = len(win.slot_frame)
     h, w = hw
     frames = win.slot_frame
@@ -205,7 +207,8 @@ def run_window(win: Window, latents_of: dict, denoise_net: Callable, c2ws, Ks, *
     disc = S.DDPMDiscretization()
     den = S.DiscreteDenoiser(disc, num_idx=1000, device=device)
     g = [S.VanillaCFG(), S.MultiviewCFG(cfg_min), S.MultiviewTemporalCFG(T, cfg_min)][guider]
-    sampler = S.EulerEDMSampler(disc, g, num_steps=num_steps, verbose=False, device=device, s_churn=0.0)
+    sampler = S.EulerEDMSampler(disc, g, num_steps=num_steps, verbose=False, device=device, s_churn=0.0,
+                                solver=solver)
     gen = torch.Generator(device=device)
     gen.manual_seed(int(step_seed))
     sampler.noise_fn = lambda x: torch.randn(x.shape, generator=gen, device=x.device, dtype=x.dtype)
@@ -225,11 +228,12 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
                    handoff: str = "latent",
                    plan: TrajectoryPlan | None = None, timers: dict | None = None,
                    sampler_hook: Callable | None = None, conditioner: Callable | None = None,
-                   input_rgb: torch.Tensor | None = None, cfg_split: bool = False) -> dict:
+                   input_rgb: torch.Tensor | None = None, cfg_split: bool = False, solver: str | None = None) -> dict:
     """Generate every non-input frame of a trajectory.  `denoise_net(x, t, cond, num_frames=T)` is the network call
     (`SGMWrapper(model)`); `input_latents` (n_in,4,h,w) are the VAE-encoded input views (x 0.18215), frame ids
     `input_ids` index `c2ws` (n,4,4) / `Ks` (n,3,3).  Returns, on rank 0, {"latents": (n,4,h,w) in frame order,
-    "frame_ids", "plan", "anchor_latents" (first-pass anchors as pass 2 saw them), ["rgb"]}; other ranks get {"plan"} only."""
+    "frame_ids", "plan", "anchor_latents" (first-pass anchors as pass 2 saw them), ["rgb"]}; other ranks get {"plan"} only.
+    `solver` goes to every window's sampler (`run_window`)."""
     rank, world = _rank_world(group)
     device = torch.device(device) if device is not None else input_latents.device
     h, w = input_latents.shape[-2:]
@@ -259,7 +263,7 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
 
     latents_of = {fid: input_latents[i].to(device) for i, fid in enumerate(plan.input_ids)}
     common = dict(hw=(h, w), num_steps=num_steps, cfg=cfg, cfg_min=cfg_min, guider=guider, camera_scale=camera_scale,
-                  device=device, sampler_hook=sampler_hook)
+                  device=device, sampler_hook=sampler_hook, solver=solver)
 
     def mark(name):
         if timers is not None:

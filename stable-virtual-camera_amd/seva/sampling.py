@@ -19,6 +19,8 @@ Division of labour
 
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 from tqdm import tqdm
@@ -350,12 +352,33 @@ class MultiviewTemporalCFG(MultiviewCFG):
 
 
 # ------------------------------------------------------------------------------ sampler
+SOLVERS = ("euler", "dpmpp2m")
+
+
 class EulerEDMSampler(object):
-    """Reference sampling.py:301-405 (Euler discretisation of the EDM probability-flow ODE)."""
+    """Reference sampling.py:301-405 (Euler discretisation of the EDM probability-flow ODE).
+
+    `solver` (opt-in, not in the reference): "euler" = the reference's step; "dpmpp2m" = DPM-Solver++(2M), the
+    deterministic second-order multistep solver (`DPMPP2MSampler` of sgm), same one network call per step.  None reads
+    the environment variable SEVA_SOLVER (default "euler"), so code that constructs or subclasses this class by name can
+    opt in unchanged; an explicit argument wins over the variable."""
 
     def __init__(self, discretization: DDPMDiscretization, guider, num_steps: int | None = None,
                  verbose: bool = False, device: str | torch.device = "cuda", s_churn=0.0, s_tmin=0.0,
-                 s_tmax=float("inf"), s_noise=1.0):
+                 s_tmax=float("inf"), s_noise=1.0, solver: str | None = None):
+        if solver is None:
+            solver = os.environ.get("SEVA_SOLVER") or "euler"
+        if solver not in SOLVERS:
+            raise ValueError(f"unknown solver {solver!r}: expected one of {SOLVERS}")
+        if solver == "dpmpp2m" and s_churn > 0:
+            raise ValueError("solver 'dpmpp2m' is deterministic: it has no stochastic form here, s_churn must be 0")
+        self.solver = solver
+        # multistep history (dpmpp2m only): the previous step's guided denoised latent D-, its sigma, and whether they are valid.
+        # Owned by the sampler and cleared by `prepare_sampling_loop`; the buffer itself persists (the whole-step hipGraph holds
+        # its address) and is never read while `_ms_have` is False.
+        self._ms_den: torch.Tensor | None = None
+        self._ms_sigma: torch.Tensor | None = None
+        self._ms_have = False
         self.num_steps = num_steps
         self.discretization = discretization
         self.guider = guider
@@ -381,6 +404,7 @@ class EulerEDMSampler(object):
         _need_gpu(x)
         if hasattr(self.guider, "reset_rule_cache"):
             self.guider.reset_rule_cache()
+        self._ms_sigma, self._ms_have = None, False  # a new trajectory starts without multistep history
         sigmas = self.discretization(num_steps, device=self.device)
         # x *= sqrt(1 + sigma_0^2), in place on the caller's tensor like the reference (l.331)
         s0 = torch.sqrt(1.0 + sigmas[0] ** 2.0).to(device=x.device, dtype=torch.float32)
@@ -464,6 +488,89 @@ class EulerEDMSampler(object):
             return tuple(out)
         return (obj,)
 
+    @staticmethod
+    def multistep_coefficients(sigma: torch.Tensor, next_sigma: torch.Tensor, prev_sigma: torch.Tensor):
+        """DPM-Solver++(2M) coefficients as f32 vectors on the sigmas' device, without a host sync:
+        x+ = a x + b D + c D-.   a = s+/s.   Rows without history (prev_sigma <= 0) and rows that land on s+ = 0:
+        b = 1 - a, c = 0 (the first-order / DDIM step; with s+ = 0 exactly a = 0, b = 1).   Otherwise, with
+        r = ln(s-/s) / ln(s/s+):  b = (1 - a)(1 + 1/(2r)),  c = -(1 - a)/(2r)   (sgm: mult1 = a, mult2 = -(1 - a),
+        mult3 = 1 + 1/(2r), mult4 = 1/(2r))."""
+        a = next_sigma / sigma
+        one_a = 1.0 - a
+        second = (prev_sigma > 0) & (next_sigma > 0)
+        # rows where `second` is False evaluate logs of 0 or of a negative ratio; torch.where discards them
+        inv_2r = torch.log(sigma / next_sigma) / (2.0 * torch.log(prev_sigma / sigma))
+        zero = torch.zeros_like(a)
+        b = torch.where(second, one_a * (1.0 + inv_2r), one_a)
+        c = torch.where(second, -one_a * inv_2r, zero)
+        return a, b, c
+
+    def _multistep_math(self, sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs):
+        """One DPM-Solver++(2M) step on f32 contiguous device tensors: no noise, no sigma_hat; guidance, update and the new
+        history in ONE kernel (`ops.cfg_multistep`), which reads D- from `hist` and leaves D there.  Sync-free like
+        `_step_math`, and the same code for the first, the second-order and the last step (they differ in a, b, c only), so
+        one hipGraph serves them all."""
+        if self.cfg_split is None:
+            denoised2 = denoiser(*self.guider.prepare_inputs(x, sigma, cond, uc))
+        else:
+            denoised2 = self._denoise_cfg_split(denoiser, x, sigma, cond, uc)
+        a, b, c = self.multistep_coefficients(sigma, next_sigma, prev_sigma)
+        out = torch.empty_like(x)
+        if hasattr(self.guider, "frame_scale"):
+            fs = self.guider.frame_scale(denoised2, sigma, scale, **guider_kwargs)
+            ops.cfg_multistep(x, _f32c(denoised2), _scale_vector(fs, x.shape[0], x.device), hist, a, b, c, out, hist)
+        else:
+            denoised = self.guider(denoised2, sigma, scale, **guider_kwargs)
+            ops.cfg_multistep(x, _f32c(denoised), None, hist, a, b, c, out, hist)
+        return out
+
+    def _multistep_step(self, sigma, next_sigma, denoiser, x, scale, cond, uc, guider_kwargs):
+        """`sampler_step` under solver="dpmpp2m": same eager warm-up / capture / replay protocol as the Euler step."""
+        hist = self._ms_den
+        if hist is None or hist.shape != x.shape or hist.device != x.device:
+            # an ordinary tensor even under torch.inference_mode(), like the static buffers of `_stepgraph.StepGraph`
+            with torch.inference_mode(False):
+                hist = self._ms_den = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+            self._ms_have = False
+        prev_sigma = self._ms_sigma if self._ms_have else torch.zeros_like(sigma)  # 0 = "no history" to the coefficients
+        out = self._multistep_dispatch(sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs)
+        self._ms_sigma, self._ms_have = sigma, True
+        return out
+
+    def _multistep_dispatch(self, sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs):
+        cache = self._step_graphs
+        use_graph = (x.is_cuda and not cache.disabled and _stepgraph.enabled() and self.cfg_split is None
+                     and not torch.cuda.is_current_stream_capturing())
+        if not use_graph:
+            return self._multistep_math(sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs)
+        key = ("dpmpp2m", tuple(x.shape), hist, self.guider, denoiser) + self._flat_key((scale, cond, uc, guider_kwargs))
+        ent = cache.lookup(key)
+        if ent.state == 0:
+            with _native.eager_network():
+                out = self._multistep_math(sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs)
+            ent.state = 1
+            return out
+        if ent.graph is None:
+            try:
+                # capture records the step without running it: the history buffer is updated by the replays alone
+                ent.graph = _stepgraph.StepGraph(
+                    lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, denoiser, scale, cond, uc, guider_kwargs),
+                    (sigma, next_sigma, x, prev_sigma))
+                cache.captures += 1
+            except Exception as e:
+                import warnings
+
+                cache.disabled = True
+                cache.reset()
+                try:
+                    torch.cuda.synchronize(x.device)
+                except Exception:
+                    pass
+                warnings.warn(f"seva: whole-step hipGraph capture failed ({type(e).__name__}: {e}); "
+                              "falling back to eager steps", RuntimeWarning)
+                return self._multistep_math(sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs)
+        return ent.graph(sigma, next_sigma, x, prev_sigma).clone()
+
     def sampler_step(self, sigma: torch.Tensor, next_sigma: torch.Tensor, denoiser, x: torch.Tensor,
                      scale, cond: dict, uc: dict, gamma: float = 0.0, **guider_kwargs) -> torch.Tensor:
         """One Euler-EDM step (reference sampling.py:347-368).  From the second step of a trajectory on, the whole
@@ -473,6 +580,8 @@ class EulerEDMSampler(object):
         x = _f32c(x)
         sigma = _f32c(sigma)
         next_sigma = _f32c(next_sigma)
+        if self.solver == "dpmpp2m":  # deterministic: no noise draw, no add_noise; `gamma` has nothing to act on
+            return self._multistep_step(sigma, next_sigma, denoiser, x, scale, cond, uc, guider_kwargs)
         eps = _f32c(self.noise_fn(x))  # drawn eagerly: the generator advances per step exactly as in the reference
         gamma = float(gamma)
         cache = self._step_graphs
@@ -530,3 +639,11 @@ class EulerEDMSampler(object):
         if x.is_cuda:
             ops.check_handoffs()
         return x
+
+
+class DPMPP2MSampler(EulerEDMSampler):
+    """`EulerEDMSampler` with solver="dpmpp2m" fixed (sgm's DPMPP2MSampler; not part of the reference's sampler file)."""
+
+    def __init__(self, *args, **kwargs):
+        kwargs["solver"] = "dpmpp2m"
+        super().__init__(*args, **kwargs)
