@@ -101,11 +101,13 @@ typedef struct seva_gemm_desc {
   /* conv mode: 1 = zero padding only at the bottom / right edge (taps start AT pixel (stride*oy, stride*ox)); the
    * stride-2 Downsample2D of the diffusers VAE encoder pads (0,1,0,1).  0 = symmetric pad 1 (every UNet conv). */
   int32_t pad_br_only;
-  /* seva_gemm_fp8 only (NULL / 0 for seva_gemm_f16): */
+  /* seva_gemm_fp8 only (NULL / 0 for seva_gemm_f16).  EVERY e4m3 output of this library ("saturating" below) is one round-to-nearest-even
+   * of the fp32 value: finite and infinite values saturate at +-448, NaN stays NaN (byte 0x7F or 0xFF), as torch's float8_e4m3fn cast
+   * of the value clamped to +-448 (tests/test_output_rounding_gpu.py). */
   const void* w_exp;     /* uint8 [N]: E8M0 scale byte 127 + e[n]; weight row n holds e4m3(w[n] * 2^-e[n]) */
-  void* out_f8;          /* GEGLU epilogue: e4m3 [M][ldo8] (saturating), the next fp8 GEMM's A operand; or NULL.  ABI 10: also the
+  void* out_f8;          /* GEGLU epilogue: e4m3 [M][ldo8] (saturating, NaN kept), the next fp8 GEMM's A operand; or NULL.  ABI 10: also the
                           * plain epilogue of a 3x3 convolution of seva_gemm_fp8 (window kernel only): the fp32 result (bias, residual,
-                          * row_add) as saturating RNE e4m3, alone or beside out_f32 / out_f16, e.g. the A operand of the next fp8 conv.
+                          * row_add) as saturating RNE e4m3 (NaN kept), alone or beside out_f32 / out_f16, e.g. the A operand of the next fp8 conv.
                           * ldo8 and the pointer must be multiples of 8.  Not together with `upsample` (an ERROR). */
   int64_t ldo8;
   /* optional (NULL = off): GroupNorm statistics of out_f32, emitted by the epilogue while the values are in registers,
@@ -196,10 +198,10 @@ typedef struct seva_ff_desc {
 int seva_ff_fused_f16(const seva_ff_desc* d, seva_stream_t stream);
 /* e4m3 sibling (ABI 12; the fp8 mode's `ff="fp8"` option): the same operator on v_mfma_scale_f32_16x16x128_f8f6f4 with fp32
  * accumulation.  a: e4m3 [M][lda] bytes (lda >= C, a multiple of 16; columns >= C are not read) or the LayerNorm prologue, whose
- * normalised row is rounded once to e4m3 (saturating, round-to-nearest-even, unit scale); w1: e4m3 [8C][KP] with KP = the multiple
+ * normalised row is rounded once to e4m3 (saturating, NaN kept, round-to-nearest-even, unit scale); w1: e4m3 [8C][KP] with KP = the multiple
  * of 128 at or above C and zero columns >= C, interleaved GEGLU rows as above; w2: e4m3 [C][4C] with its columns permuted into the
  * kernel's order of the hidden features (csrc/ff_fp8.h; seva.ops.pack_ff_fp8 writes both).  The hidden value v * gelu_erf(g) is
- * rounded once to e4m3 (saturating), the value the two-kernel e4m3 chain stores through seva_gemm_desc.out_f8.  w1_exp and w2_exp
+ * rounded once to e4m3 (saturating, NaN kept), the value the two-kernel e4m3 chain stores through seva_gemm_desc.out_f8.  w1_exp and w2_exp
  * are required.  Every output row depends on its own input row only. */
 int seva_ff_fused_fp8(const seva_ff_desc* d, seva_stream_t stream);
 
@@ -277,7 +279,7 @@ typedef struct seva_groupnorm_desc {
    * the ResBlock's 1x1 skip convolution (seva/modules/layers.py:137), written in the same pass instead of by a
    * separate seva_cast_concat_f16 read of both sources.  NULL = off. */
   void* raw_f16;
-  /* optional e4m3 output (saturating), same layout: the A operand of seva_gemm_fp8 / an fp8 conv.  When set, out_f16
+  /* optional e4m3 output (saturating, NaN kept), same layout: the A operand of seva_gemm_fp8 / an fp8 conv.  When set, out_f16
    * may be NULL. */
   void* out_f8;
   int64_t ld_out_f8; /* pixel pitch of out_f8 in bytes (>= c1 + c2; 0 = c1 + c2): lets a 320-channel tensor feed an fp8 conv whose
@@ -306,7 +308,7 @@ int seva_layernorm_f16(const float* x, const float* gamma, const float* beta, vo
  * [W | W] (K = 2 c) the fp32-accumulating MFMA then sees the normalised row to ~22 bits. */
 int seva_layernorm_f16_split(const float* x, const float* gamma, const float* beta, void* out_f16,
                              int64_t rows, int32_t c, float eps, seva_stream_t stream);
-/* Same normalisation with OCP e4m3 output (saturating at +-448): the A operand of seva_gemm_fp8. */
+/* Same normalisation with OCP e4m3 output (saturating at +-448; NaN stays NaN, byte 0x7F / 0xFF): the A operand of seva_gemm_fp8. */
 int seva_layernorm_fp8(const float* x, const float* gamma, const float* beta, void* out_f8, int64_t rows,
                        int32_t c, float eps, int64_t ld_out /* row pitch in bytes, >= c; 0 = c; pad bytes untouched */,
                        seva_stream_t stream);

@@ -23,6 +23,15 @@
 #include <type_traits>
 
 namespace {
+// Two softmax probabilities -> one f16 pair, round to nearest even (v_cvt_pk_f16_f32, one instruction like the round-toward-zero pack
+// it replaces).  A truncating pack cancels in O = sum(p v) / sum(p) to first order only: the key that sets the exponent reference has
+// P = 1.0 exactly and loses nothing while every other key loses 2^-11 of its weight on average, so each row leaned towards its heaviest
+// key and came out 3e-5 .. 6e-5 too large (tests/test_output_rounding_gpu.py::test_c_attention: `gain`).  A P above the f16 range now
+// packs to inf, not 65504: its row sum is then inf, which every caller already routes to its rescale path (the sum / maximum tests).
+typedef __fp16 p16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ p16x2_t pack_p(float e0, float e1) {
+  return __builtin_bit_cast(p16x2_t, __builtin_convertvector(f32x2{e0, e1}, half2_t));
+}
 
 struct AttnArgs {
   const half_t* q;
@@ -290,9 +299,9 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_kernel(AttnArgs p) {
         for (int r = 0; r < 16; ++r) acc_o[d][r] *= alpha;
     }
     }
-    // P = exp2(S*c - m) packed to fp16 pairs (round-toward-zero); the row sum is taken from the
+    // P = exp2(S*c - m) packed to fp16 pairs (pack_p: round to nearest even); the row sum is taken from the
     // ROUNDED values (v_dot2_f32_f16 with ones) so numerator (P*V) and normaliser see identical
-    // probabilities and the truncation cancels in O = sum(p v) / sum(p).
+    // probabilities and the rounding cancels in O = sum(p v) / sum(p).
     typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
     const fp16x2_t ones2 = {(__fp16)1.0f, (__fp16)1.0f};
     float lsum4[4] = {0.f, 0.f, 0.f, 0.f};  // four independent dot2 chains
@@ -317,7 +326,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_kernel(AttnArgs p) {
             e0 = sc[kb][8 * s2 + 2 * j];
             e1 = sc[kb][8 * s2 + 2 * j + 1];
           }
-          pk[j] = __builtin_amdgcn_cvt_pkrtz(e0, e1);
+          pk[j] = pack_p(e0, e1);
           if (!(dbg & 2)) lsum4[j] = __builtin_amdgcn_fdot2(pk[j], ones2, lsum4[j], false);
         }
         pf[kb][s2] = __builtin_bit_cast(half8_t, pk);
@@ -603,8 +612,9 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
       }
       // exp2 / pack / row sums FIRST, straight off the scores relative to m_run; the running maximum is looked at only when a
       // partial row sum says a probability may have left the safe range (any P >= 2^14 makes its lane's sum >= 2^14; f16 holds
-      // 2^16 - 32 and cvt_pkrtz never rounds up), and on the first tile (m_run = 0 there: the true maximum protects the small
-      // probabilities from underflow).  The 21 v_max3 + the half-wave exchange per query block leave the steady-state loop.
+      // 2^16 - 32 and a larger P packs to inf, which makes the sum inf: the test below sees that too), and on the first tile
+      // (m_run = 0 there: the true maximum protects the small probabilities from underflow).  The 21 v_max3 + the half-wave
+      // exchange per query block leave the steady-state loop.
       float ls[4];
       const auto exp_pack = [&]() {
         ls[0] = ls[1] = ls[2] = ls[3] = 0.f;  // four partial sums: short dependent dot2 chains
@@ -617,7 +627,7 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
             for (int j = 0; j < 4; ++j) {
               const float e0 = __builtin_amdgcn_exp2f(sc[c][kb][8 * s2 + 2 * j]);
               const float e1 = __builtin_amdgcn_exp2f(sc[c][kb][8 * s2 + 2 * j + 1]);
-              pk[j] = __builtin_amdgcn_cvt_pkrtz(e0, e1);
+              pk[j] = pack_p(e0, e1);
               ls[j] = __builtin_amdgcn_fdot2(pk[j], ones2, ls[j], false);
             }
             pf[c][kb][s2] = __builtin_bit_cast(half8_t, pk);
@@ -926,7 +936,7 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
               for (int e = 0; e < 2; ++e) {
                 const float e0 = __builtin_amdgcn_exp2f(sc[c][2 * j + h][2 * e]);
                 const float e1 = __builtin_amdgcn_exp2f(sc[c][2 * j + h][2 * e + 1]);
-                pk[2 * h + e] = __builtin_amdgcn_cvt_pkrtz(e0, e1);
+                pk[2 * h + e] = pack_p(e0, e1);
                 ls[2 * h + e] = __builtin_amdgcn_fdot2(pk[2 * h + e], ones2, ls[2 * h + e], false);
               }
             pf[c][j] = __builtin_bit_cast(half8_t, pk);

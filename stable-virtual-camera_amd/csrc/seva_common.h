@@ -92,9 +92,12 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-// four floats -> four OCP e4m3 bytes (round to nearest even, saturating at +-448), byte i = value i
+// four floats -> four OCP e4m3 bytes (round to nearest even; finite and infinite values saturate at +-448; NaN stays NaN: byte 0x7F
+// or 0xFF), byte i = value i.  The clamp is the NaN-propagating IEEE 754-2019 minimum / maximum (v_minimum3_f32 / v_maximum3_f32):
+// fminf / fmaxf return the bound for a NaN, and a diverged trajectory then decodes to a plausible image.  It is one VALU instruction
+// per value more than the v_med3_f32 of fminf / fmaxf; what that costs is measured in profiles/output_rounding.log.
 __device__ __forceinline__ int pack_fp8x4(float a, float b, float c, float d) {
-  const auto cl = [](float v) { return __builtin_fminf(__builtin_fmaxf(v, -448.f), 448.f); };
+  const auto cl = [](float v) { return __builtin_elementwise_minimum(__builtin_elementwise_maximum(v, -448.f), 448.f); };
   int r = __builtin_amdgcn_cvt_pk_fp8_f32(cl(a), cl(b), 0, false);
   return __builtin_amdgcn_cvt_pk_fp8_f32(cl(c), cl(d), r, true);
 }

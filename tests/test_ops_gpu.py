@@ -3,6 +3,7 @@
 Run on the MI355X box: `python -m pytest tests -m gpu`.  GEMM-type ops are checked twice: exactly
 (small-integer data, where fp16 inputs + fp32 accumulation are exact) and on random data against
 fp32 math on the fp16-rounded operands (tolerance = accumulation-order noise only).
+The rounding of the f16 / e4m3 outputs themselves (mode, ties, subnormals, overflow, NaN) is pinned in tests/test_output_rounding_gpu.py.
 """
 import math
 import os
