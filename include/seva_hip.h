@@ -441,6 +441,49 @@ int seva_attention_small_f16(const void* q, const void* k, const void* v, void* 
                              int32_t L, int32_t head_dim, float scale, seva_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image front and back end (seva/eval.py:160-322 load_img_and_K / transform_img_and_K, 974-975 save_output).
+ *
+ * One kernel fuses source conversion, alpha compositing, F.interpolate(mode="area"), crop or pad and an affine output
+ * map; only the H x W output pixels are computed (the reference resizes the whole image, then crops).  The arithmetic
+ * is the reference's CPU expression operation by operation, every fp32 operation rounded on its own (no FMA, correctly
+ * rounded divisions), so the result equals the reference's bit for bit:
+ *   uint8 source     v = float(u8) / 255.0f
+ *   4 channels       v = rgb * a + bg * (1 - a): mul, sub, mul, add; bg = 1.0f, or context_rgb when given
+ *   area             resized pixel (i, j) = mean of source rows floor(i*h/rh) .. ceil((i+1)*h/rh) - 1 and columns
+ *                    floor(j*w/rw) .. ceil((j+1)*w/rw) - 1: summed in fp32 in row-major order starting from 0, then
+ *                    divided by the row count, then by the column count (a 1 x 1 window copies the value)
+ *   window           out[y][x] = resized[ct + y][cl + x]; (ct, cl) is signed and a pixel outside the resized image
+ *                    takes pad_value
+ *   output           v * out_mul + out_add as two operations, padding pixels included, skipped when (out_mul,
+ *                    out_add) == (1, 0)
+ * The result of an image depends on nothing but that image: not on n, on the pitches or on what surrounds the output;
+ * only the H x W pixels of each of the 3 planes of an image are written.
+ */
+typedef struct seva_image_desc {
+  const void* src;          /* u8: [n][h][w][src_c], src_c = 3 (RGB) or 4 (RGBA); f32: [n][3][h][w] */
+  const float* context_rgb; /* optional alpha background, fp32 [h][w][3] dense, shared by the n images (src_c = 4 only);
+                               NULL = white */
+  float* out;               /* [n][3][H][W] fp32: planes and rows dense, images out_pitch_n floats apart */
+  int64_t src_pitch_n;      /* source elements (u8: bytes, f32: floats) between images, */
+  int64_t src_pitch_c;      /*   between channel planes (f32 only), */
+  int64_t src_pitch_row;    /*   between rows; src_c = 4 reads a pixel as one 32-bit word: src and both pitches % 4 == 0 */
+  int64_t out_pitch_n;      /* >= 3*H*W */
+  int32_t n, h, w, src_c;
+  int32_t rh, rw;           /* size of the resized image, never materialised */
+  int32_t ct, cl;           /* origin of the output window inside it (signed) */
+  int32_t H, W;
+  float pad_value, out_mul, out_add;
+} seva_image_desc;
+int seva_image_area_crop_u8(const seva_image_desc* d, seva_stream_t stream);
+int seva_image_area_crop_f32(const seva_image_desc* d, seva_stream_t stream);
+/* save_output's frame rule (eval.py:974-975): x [n][3][H][W] fp32, images x_pitch_n floats apart -> out [n][H][W][3] uint8
+ * dense; t = (v + 1.0f) / 2.0f; t = t * 255.0f; clamp to [0, 255]; truncate -- separate fp32 operations.  +-inf clamp to
+ * 255 / 0.  NaN writes 0: the reference leaves NaN -> uint8 undefined (the result of a C++ cast), this is this
+ * library's choice. */
+int seva_rgb_to_u8(const float* x, int64_t x_pitch_n, uint8_t* out, int32_t n, int32_t H, int32_t W,
+                   seva_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Benchmark / debugging knobs.  The library reads its SEVA_* environment variables ONCE, when it is loaded (nothing
  * on the launch path calls getenv); a host changes a knob at run time with seva_set_knob (tests, tools).  Names:
  * gemm_chunks, gemm_dbg, gemm_stagger, gemm_bm, gemm_bn, gemm_astat, attn_dbg, attn_no_tr, attn_two, attn_split,

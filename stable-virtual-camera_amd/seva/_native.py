@@ -79,6 +79,16 @@ class GroupNormDesc(C.Structure):
     ]
 
 
+class ImageDesc(C.Structure):
+    _fields_ = [
+        ("src", c_void_p), ("context_rgb", c_void_p), ("out", c_void_p),
+        ("src_pitch_n", c_int64), ("src_pitch_c", c_int64), ("src_pitch_row", c_int64), ("out_pitch_n", c_int64),
+        ("n", c_int32), ("h", c_int32), ("w", c_int32), ("src_c", c_int32),
+        ("rh", c_int32), ("rw", c_int32), ("ct", c_int32), ("cl", c_int32), ("H", c_int32), ("W", c_int32),
+        ("pad_value", c_float), ("out_mul", c_float), ("out_add", c_float),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/seva_hip.h
 SYMBOLS = {
     "seva_last_error": (c_char_p, []),
@@ -124,6 +134,9 @@ SYMBOLS = {
     "seva_scale_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
     "seva_plucker_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "seva_cond_concat_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "seva_image_area_crop_u8": (c_int, [POINTER(ImageDesc), c_void_p]),
+    "seva_image_area_crop_f32": (c_int, [POINTER(ImageDesc), c_void_p]),
+    "seva_rgb_to_u8": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "seva_set_knob": (c_int, [c_char_p, c_int32]),
     "seva_get_knob": (c_int, [c_char_p, POINTER(c_int32)]),
     "seva_graph_begin": (c_int, [c_void_p]),

@@ -13,7 +13,7 @@ import ctypes as C
 import torch
 
 from . import _native as nv
-from ._native import AttnDesc, GemmDesc, GroupNormDesc, check, ptr, require_cuda, stream_ptr
+from ._native import AttnDesc, GemmDesc, GroupNormDesc, ImageDesc, check, ptr, require_cuda, stream_ptr
 
 F16, F32 = torch.float16, torch.float32
 U8 = torch.uint8  # e4m3 bytes travel as uint8 tensors (bit pattern of torch.float8_e4m3fn)
@@ -804,6 +804,50 @@ def cond_concat(plucker_maps: torch.Tensor, mask_u8: torch.Tensor, c_concat: tor
     check(_lib().seva_cond_concat_f32(plucker_maps.data_ptr(), mask_u8.data_ptr(), c_concat.data_ptr(),
                                       uc_concat.data_ptr(), V, h, w, stream_ptr(plucker_maps.device)),
           "seva_cond_concat_f32")
+
+
+def image_area_crop(src: torch.Tensor, out: torch.Tensor, *, rh: int, rw: int, ct: int = 0, cl: int = 0, pad_value: float = 0.0,
+                    out_mul: float = 1.0, out_add: float = 0.0, context_rgb: torch.Tensor | None = None) -> None:
+    """Source conversion + alpha compositing + F.interpolate(mode="area") to (rh, rw) + the (H, W) window at (ct, cl) of the
+    resized image (signed; outside = pad_value) + v * out_mul + out_add, bit for bit the reference's CPU arithmetic
+    (seva_image_area_crop_u8 / _f32).  src: uint8 (n,h,w,3|4) or fp32 (n,3,h,w), rows dense; out: fp32 (n,3,H,W), planes
+    dense, any image pitch; context_rgb: fp32 (h,w,3) alpha background (RGBA sources), None = white."""
+    require_cuda(src, out, context_rgb)
+    assert out.dtype == F32 and out.dim() == 4 and out.shape[1] == 3
+    n, _, H, W = out.shape
+    assert out.stride(3) == 1 and out.stride(2) == W and out.stride(1) == H * W, "output planes must be dense"
+    d = ImageDesc()
+    if src.dtype == torch.uint8:
+        assert src.dim() == 4 and src.shape[0] == n and src.shape[3] in (3, 4)
+        h, w, c = src.shape[1:]
+        assert src.stride(3) == 1 and src.stride(2) == c, "source pixels must be dense in a row"
+        d.src_pitch_n, d.src_pitch_c, d.src_pitch_row = src.stride(0), 0, src.stride(1)
+        fn, name = _lib().seva_image_area_crop_u8, "seva_image_area_crop_u8"
+    else:
+        assert src.dtype == F32 and src.dim() == 4 and src.shape[0] == n and src.shape[1] == 3
+        h, w, c = src.shape[2], src.shape[3], 3
+        assert src.stride(3) == 1, "source rows must be dense"
+        d.src_pitch_n, d.src_pitch_c, d.src_pitch_row = src.stride(0), src.stride(1), src.stride(2)
+        fn, name = _lib().seva_image_area_crop_f32, "seva_image_area_crop_f32"
+    if context_rgb is not None:
+        assert context_rgb.dtype == F32 and context_rgb.shape == (h, w, 3) and context_rgb.is_contiguous()
+    d.src, d.context_rgb, d.out = src.data_ptr(), ptr(context_rgb), out.data_ptr()
+    d.out_pitch_n = out.stride(0)
+    d.n, d.h, d.w, d.src_c = n, h, w, c
+    d.rh, d.rw, d.ct, d.cl, d.H, d.W = int(rh), int(rw), int(ct), int(cl), H, W
+    d.pad_value, d.out_mul, d.out_add = float(pad_value), float(out_mul), float(out_add)
+    check(fn(C.byref(d), stream_ptr(out.device)), name)
+
+
+def rgb_to_u8(x: torch.Tensor, out: torch.Tensor) -> None:
+    """x: fp32 (n,3,H,W), planes dense, any image pitch -> out: uint8 (n,H,W,3) contiguous; (v + 1) / 2 * 255, clamped to
+    [0, 255], truncated; NaN -> 0 (seva_rgb_to_u8)."""
+    require_cuda(x, out)
+    assert x.dtype == F32 and x.dim() == 4 and x.shape[1] == 3 and out.dtype == torch.uint8
+    n, _, H, W = x.shape
+    assert x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W, "input planes must be dense"
+    assert out.shape == (n, H, W, 3) and out.is_contiguous()
+    check(_lib().seva_rgb_to_u8(x.data_ptr(), x.stride(0), out.data_ptr(), n, H, W, stream_ptr(x.device)), "seva_rgb_to_u8")
 
 
 # --- benchmark / debugging knobs (read from SEVA_* once at library load; see include/seva_hip.h) ---------

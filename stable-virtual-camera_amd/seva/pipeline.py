@@ -377,3 +377,36 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
         res["rgb"] = ae.decode(final)
         mark("decode")
     return res
+
+
+def run_scene(denoise_net: Callable, ae, images: Sequence, c2ws: torch.Tensor, Ks: torch.Tensor, input_ids: Sequence[int], *,
+              size=(576, 576), conditioner: Callable | None = None, clip_token: torch.Tensor | None = None,
+              **run_trajectory_kwargs) -> dict:
+    """Pictures + cameras in, uint8 frames out: `frames.load_img_and_K` per input picture (a path, a uint8 (h,w,3|4) array
+    or tensor; covered and cropped to `size` = (W, H)), `ae.encode`, `run_trajectory`, `ae.decode`, `frames.to_uint8`.
+    `Ks` (n,3,3) as `run_trajectory` takes them (normalised); the input views' rows are replaced by the intrinsics of the
+    cropped pictures.  With a `conditioner` the loaded pictures are its `input_rgb` and the hand-off goes through RGB, as
+    `run_trajectory` requires.  A composition only: on rank 0 the result of `run_trajectory` (with "rgb") plus "frames"
+    (n,H,W,3) uint8 and "Ks" (n_in,3,3), the adjusted intrinsics of the input views in pixels of the frames."""
+    from . import frames
+    device = torch.device(run_trajectory_kwargs.pop("device", None) or "cuda")
+    ids = [int(i) for i in input_ids]
+    assert len(images) == len(ids), "one picture per input view"
+    rgb, K_px = [], []
+    Ks = Ks.clone()
+    for img, fid in zip(images, ids):
+        x, K = frames.load_img_and_K(img, size, K=Ks[fid], device=device)
+        H, W = x.shape[-2:]
+        rgb.append(x)
+        K_px.append(K)
+        Ks[fid] = K / K.new_tensor([W, H, 1.0])[:, None]  # back to normalised intrinsics (eval.py:1400-1401)
+    input_rgb = torch.cat(rgb)
+    kw = dict(run_trajectory_kwargs)
+    if conditioner is not None:
+        kw.update(conditioner=conditioner, input_rgb=input_rgb)
+        kw.setdefault("handoff", "rgb")
+    res = run_trajectory(denoise_net, ae.encode(input_rgb), c2ws, Ks, ids, clip_token=clip_token, device=device, ae=ae, **kw)
+    if "rgb" in res:  # rank 0
+        res["frames"] = frames.to_uint8(res["rgb"])
+        res["Ks"] = torch.stack(K_px)
+    return res
