@@ -35,7 +35,6 @@
 #include "gemm_common.h"
 
 #include <atomic>
-#include <numeric>
 #include <type_traits>
 
 namespace {
@@ -49,7 +48,7 @@ struct ConvWinGeom {
   int32_t tiles_m, tiles_n;
   int32_t tpi;  // 0: M-tiles are consecutive BM-pixel ranges of the whole launch; > 0: tiles per image (a tile never leaves its image)
   int32_t n_lin;  // host only: images per launch of the linear tiles (31-bit offsets, exact multiply-high divisions); 0 = not even one
-};
+};  // filled from the plan (gemm_plan.h: WinGeom, WinTiling)
 
 // UP: the conv input is the nearest-2x upsampled image (reference layers.py:35-46: F.interpolate(scale_factor=2) then conv): the window
 // is staged from the SOURCE image and tap (ky, kx) of output pixel (y, x) reads source pixel ((y + ky - 1) >> 1, (x + kx - 1) >> 1)
@@ -525,76 +524,28 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
   }
 }
 
-uint32_t magic_u32(uint32_t d) { return (uint32_t)(0x100000000ull / d) + 1u; }
 
-template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP = false, int TW = 0, bool FP8 = false, bool O8 = false, bool S2 = false, bool PH = false>
-int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
+// Launches one row of the instantiation table (gemm_plan.h: SEVA_WIN_KERNELS) over the plan's ranges of whole images: outputs, residual,
+// row_add and statistics move by whole images (the plan keeps a range's first row on a row_add group boundary and on a 64-row block).
+template <int BM, int BN, int NW, int WCAP, bool DBW, bool STATS, bool UP, int TW, bool FP8, bool O8, bool S2, bool PH>
+int launch_win(const GemmArgs& a, const seva_plan::WinPlan& w, hipStream_t s) {
   constexpr int lds = (DBW ? 2 : 1) * WCAP * 128 + 2 * BN * 128;
   static_assert(lds <= 160 * 1024, "LDS per workgroup");
   static std::atomic<uint64_t> attr_devs{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t dev_bit = 1ull << (dev & 63);
-  if (!(attr_devs.load(std::memory_order_relaxed) & dev_bit)) {
-    (void)hipFuncSetAttribute((const void*)conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_devs.fetch_or(dev_bit, std::memory_order_relaxed);
-  }
-  ConvWinGeom g = g0;
-  g.tiles_n = (int)((a.N + BN - 1) / BN);
-  const auto go = [&](const GemmArgs& c, const ConvWinGeom& gc) {
-    const int64_t nb = (int64_t)gc.tiles_m * gc.tiles_n * (PH ? 4 : 1);  // PH: one workgroup per tile and phase
-    if (nb <= 0 || nb > 0x7fffffff) {
-      seva_set_error("conv_win: bad grid %lld", (long long)nb);
-      return SEVA_ERR_ARG;
-    }
-    hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH>), dim3((unsigned)nb), dim3(64 * NW), lds, s, c, gc);
-    return seva_check_launch("conv_win_kernel");
-  };
-  if constexpr (TW > 0) {
-    // 2-D tiles: whole tiles only, and (statistics) whole 64-pixel blocks per image
-    constexpr int TH = BM / 16;
-    if (a.ow % 16 != 0 || a.oh % TH != 0 || g.hw % 64 != 0) return 1;
-    g.tpi = (a.oh / TH) * (a.ow / 16);
-    g.tiles_m = a.n * g.tpi;
-    return go(a, g);
-  } else {
-  // Whether the linear tiles apply is decided from ONE image: the widest window of a tile of consecutive pixels of one image must fit
-  // the instantiation's capacity.  (Tiles over consecutive pixels of several images, which may straddle an image border, are never
-  // narrower than those of image 0 alone, so they cannot widen what applies.)  The output rows are the same bits however they are tiled.
-  if (g.n_lin <= 0 || g.Wp + 1 > WCAP) return 1;
-  const auto window_len = [&](int64_t ma, int64_t mb) {  // the kernel's WL (S2: window slots) for output rows [ma, mb]
-    const auto idx = [&](int64_t m, int64_t& x) {
-      const int64_t img = m / g.hw, rem = m % g.hw, y = rem / g.ow;
-      x = rem % g.ow;
-      if (S2) return img * g.Sp + 2 * y * g.Wp + 2 * x;
-      return img * g.Sp + ((UP ? y >> 1 : y) + 1) * g.Wp + (UP ? x >> 1 : x) + 1;
-    };
-    int64_t xa, xb;
-    const int64_t pa = idx(ma, xa), pb = idx(mb, xb);
-    if (S2) return ((pb - pa + 2 * g.Wp + 3 + 1) >> 1) * 2;
-    const int64_t q0 = (UP ? pa - (xa >> 1) : pa) - (g.Wp + 1);
-    return (UP ? pb - (xb >> 1) + a.iw - 1 : pb) - q0 + g.Wp + 2;
-  };
-  const auto fits = [&](int64_t rows, int tpi) {  // every tile's window <= WCAP; tpi > 0: tiles per image, else over `rows` consecutive rows
-    const int64_t tiles = tpi > 0 ? (int64_t)tpi : (rows + BM - 1) / BM;  // per-image tiling: every image has the same windows
-    const int64_t lim = tpi > 0 ? g.hw : rows;
-    for (int64_t t = 0; t < tiles; ++t) {
-      const int64_t ma = t * BM, mb = ma + BM < lim ? ma + BM : lim;
-      if (window_len(ma, mb - 1) > WCAP) return false;
-    }
-    return true;
-  };
-  const int tpi = (g.hw + BM - 1) / BM;
-  if (!fits(g.hw, tpi)) return 1;  // not applicable: the caller tries 2-D tiles, then falls back to the per-tap gather
-  // Launches of at most n_lin images (the 31-bit offsets and multiply-high divisions of the linear tiles hold over that range; n_lin
-  // comes from per-image dimensions): outputs, residual, row_add and statistics move by whole images.  n_lin keeps a range's first row
-  // on a row_add group boundary, and the statistics need hw % 64 == 0, so a range starts on a 64-row block.
-  for (int64_t i0 = 0; i0 < a.n; i0 += g.n_lin) {
-    const int nc = (int)(a.n - i0 < g.n_lin ? a.n - i0 : g.n_lin);
+  seva_max_dynamic_lds_once(attr_devs, lds, {(const void*)conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH>});
+  const seva_plan::WinGeom& pg = w.geom;
+  ConvWinGeom g{};
+  g.mul_hw = pg.mul_hw; g.mul_iw = pg.mul_iw; g.mul_sp = pg.mul_sp; g.mul_wp = pg.mul_wp;
+  g.Wp = pg.Wp; g.Sp = pg.Sp; g.hw = pg.hw; g.ow = pg.ow;
+  g.tiles_n = pg.tiles_n;
+  g.n_lin = pg.n_lin;
+  int64_t i0 = 0;  // first image of the range
+  for (int r = 0; r < w.n_ranges(); ++r) {
+    const seva_plan::WinTiling& t = w.range(r);
     const int64_t r0 = i0 * g.hw;
     GemmArgs c = a;
-    c.n = nc;
-    c.M = (int64_t)nc * g.hw;
+    c.n = t.n;
+    c.M = (int64_t)t.n * g.hw;
     c.a = a.a + i0 * a.ih * a.iw * a.cin;
     if (c.residual) c.residual += r0 * a.ldr;
     if (c.out_f32) c.out_f32 += r0 * (PH ? 4 : 1) * a.ldo32;  // (PH: r0 counts source pixels, four output rows each)
@@ -602,224 +553,36 @@ int launch_win(const GemmArgs& a, const ConvWinGeom& g0, hipStream_t s) {
     if (c.out_f8) c.out_f8 += r0 * a.ldo8;
     if (c.row_add) c.row_add += (r0 / a.rows_per_group) * a.ldra;
     if (c.ch_stats) c.ch_stats += (r0 / 64) * (PH ? 4 : 1) * 2 * a.N;
-    ConvWinGeom gc = g;
-    // consecutive pixels of the whole range where that fits (a tile may then straddle images: fewer, fuller tiles), else one image's
-    // (the scan is bounded: a window of BM pixels + two rows cannot fit once a row exceeds the capacity)
-    if (c.M / BM <= 65536 && fits(c.M, 0)) {
-      gc.tpi = 0;
-      gc.tiles_m = (int)((c.M + BM - 1) / BM);
-    } else {
-      gc.tpi = tpi;
-      gc.tiles_m = nc * tpi;
+    g.tpi = t.tpi;
+    g.tiles_m = t.tiles_m;
+    const int64_t nb = (int64_t)g.tiles_m * g.tiles_n * (PH ? 4 : 1);  // PH: one workgroup per tile and phase
+    if (nb <= 0 || nb > 0x7fffffff) {
+      seva_set_error("conv_win: bad grid %lld", (long long)nb);
+      return SEVA_ERR_ARG;
     }
-    const int rc = go(c, gc);
+    hipLaunchKernelGGL((conv_win_kernel<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH>), dim3((unsigned)nb), dim3(64 * NW), lds, s, c, g);
+    const int rc = seva_check_launch("conv_win_kernel");
     if (rc != 0) return rc;
+    i0 += t.n;
   }
   return 0;
-  }
 }
 
 }  // namespace
 
-namespace {
-// Geometry of a launch from its arguments (a.oh / a.ow: the image the kernel's M rows index; the phase mode passes the source image there).
-// 0 = ok, 1 = the window kernel does not apply
-int win_geometry(const GemmArgs& a, bool s2, ConvWinGeom& g) {
-  g = ConvWinGeom{};
-  g.Wp = a.iw + 1;             // padded SOURCE space (UP: the image before the nearest-2x upsample)
-  if (s2) g.Wp += g.Wp & 1;    // S2: frame columns on the right only, as many as make the row pitch even (parity of P = parity of x)
-  g.Sp = (a.ih + 1) * g.Wp;
-  g.hw = a.oh * a.ow;
-  g.ow = a.ow;
-  // GroupNorm statistics are 64-row blocks of the whole tensor: only where a block cannot straddle two images (the consumer refuses other
-  // statistics anyway), for every batch size
-  if (a.ch_stats != nullptr && g.hw % 64 != 0) return 1;
-  // 31-bit byte offsets into the image; exactness of the multiply-high divisions of the LINEAR tiles (2-D tiles divide by constants
-  // only): mulhi(x, floor(2^32 / d) + 1) == x / d for every x with x * e < 2^32, e = (floor(2^32 / d) + 1) * d - 2^32 in (0, d]
-  if ((uint64_t)a.ih * a.iw * a.cin * 2 >= (1ull << 31)) return 1;  // one image
-  const auto div_exact = [](uint64_t x_max, uint32_t d) {
-    const uint64_t e = (uint64_t)magic_u32(d) * d - (1ull << 32);
-    return x_max < (1ull << 32) && x_max * e < (1ull << 32);
-  };
-  // the terms that grow with the number of images hold up to some count n_lin: larger batches are launched as ranges of n_lin images
-  // (launch_win), so that whether the window kernel computes an image depends on per-image dimensions only
-  const auto lin_exact = [&](uint64_t nn) {
-    return nn * a.ih * a.iw * a.cin * 2 < (1ull << 31) && div_exact(nn * g.hw, (uint32_t)g.hw) && div_exact(nn * g.Sp + 1024, (uint32_t)g.Sp);
-  };
-  g.n_lin = 0;
-  if (div_exact((uint64_t)g.hw, (uint32_t)g.ow) && div_exact((uint64_t)g.Sp, (uint32_t)g.Wp) && lin_exact(1)) {
-    // largest count for which lin_exact holds -- NOT capped at n: n_lin must not depend on the batch
-    uint64_t lo = 1, hi = (1ull << 31) / ((uint64_t)a.ih * a.iw * a.cin * 2);
-    while (lo < hi) {
-      const uint64_t mid = (lo + hi + 1) / 2;
-      if (lin_exact(mid)) lo = mid; else hi = mid - 1;
-    }
-    // row_add: a range of n_lin images must end on a group boundary (groups of rows_per_group rows count from row 0 of the tensor)
-    const uint64_t rpg = a.row_add ? (uint64_t)a.rows_per_group : 1, step = rpg / std::gcd(rpg, (uint64_t)g.hw);
-    g.n_lin = (int32_t)(lo / step * step);  // (< 2^31: lo is)
-  }
-  g.mul_hw = magic_u32((uint32_t)g.hw);
-  g.mul_iw = magic_u32((uint32_t)g.ow);
-  g.mul_sp = magic_u32((uint32_t)g.Sp);
-  g.mul_wp = magic_u32((uint32_t)g.Wp);
-  return 0;
-}
-
-// Which of the two bitwise-equal 160-column families a launch of M rows x N columns (x `mult` workgroups per tile) takes, from how it
-// quantises: see seva_conv_win_launch.  rows4: tile height of the 4-wave family
-bool eight_waves_quantise_better(int64_t M, int64_t N, int rows4, int mult) {
-  const double tn = (double)((N + 159) / 160) * mult;
-  const double t8 = (double)((M + 255) / 256) * tn, t4 = (double)((M + rows4 - 1) / rows4) * tn;
-  const double r8 = t8 / 256.0, r4 = t4 / 512.0;
-  const double f4 = r4 - (double)(int64_t)r4;
-  const double tail4 = f4 > 0.0 ? (f4 <= 0.5 ? 0.55 : 0.55 + 0.9 * (f4 - 0.5)) : 0.0;  // a partly filled round of 4-wave workgroups runs one per CU
-  const double cost8 = 0.95 * (double)(int64_t)(r8 + 0.999999) / r8, cost4 = ((double)(int64_t)r4 + tail4) / r4;
-  return t8 >= 256.0 && cost8 < cost4;
-}
-}  // namespace
-
-// 0 = launched, 1 = not applicable (the caller uses the per-tap gather of gemm.hip), < 0 = error
-int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8) {
-  const int knob = g_seva_knobs.conv_win;
-  if (knob == 0) return 1;
-  // e4m3 stride 2 with bottom / right padding only (the VAE encoder's Downsample2D convs in its fp8 mode); the UNet's stride-2 convs (pad 1)
-  // and every f16 stride-2 conv keep the per-tap gather
-  const bool s2 = fp8 && a.stride == 2 && a.pad_lo == 0 && !a.upsample;
-  if (!s2 && (a.stride != 1 || a.pad_lo != 1)) return 1;
-  if (a.a2 != nullptr || a.sk_ws != nullptr) return 1;
-  const int up = a.upsample ? 2 : 1;
-  if (!s2 && (a.oh != up * a.ih || a.ow != up * a.iw)) return 1;  // (S2: oh = (ih - 2) / 2 + 1, checked by gemm.hip)
-  if (a.iw < 2 || a.ih < 2) return 1;
-  const bool narrow = a.N <= 32 && a.N % 4 == 0;  // the UNet's head (4 channels), the VAE's conv_out
-  if (a.cin % 64 != 0 || (a.N % 160 != 0 && a.N % 128 != 0 && !narrow) || a.K != 9LL * a.cin) return 1;
-  ConvWinGeom g;
-  if (win_geometry(a, s2, g) != 0) return 1;
-  const bool stats = a.ch_stats != nullptr;
-  if (fp8) {
-    // e4m3 operands (the C >= 640 levels in fp8 mode): 128-column tiles only (with 160 columns the 8-register operand tuples of the scaled
-    // MFMA no longer fit beside 100 accumulators: 2 KB of scratch; gemm.hip's e4m3 kernels found the same); cin counts 2-byte units
-    if (a.N % 128 != 0 || a.w_exp == nullptr) return 1;
-    const bool eight = knob == 2;  // two 4-wave workgroups per CU are faster on every e4m3 shape of a step (profiles/r04_kconvwin_fp8.log)
-    if (s2) {
-      // The VAE encoder's three Downsample2D convs (576 -> 288, 288 -> 144, 144 -> 72 px): the window of a stride-2 tile has about four times
-      // its output pixels, so one 4-wave workgroup per CU on 128-row tiles (no 8-wave variant).  Linear tiles where one image's windows fit
-      // 864 slots (output rows up to 72 px: a 128-pixel tile spans at most three of them, 846 slots at 72 px), else 2-D tiles of 16 x 8 output
-      // pixels (a 17 x 33 source window: 561 slots; 144 and 288 px output rows).
-      // Both are decided from one image's dimensions.  No e4m3 output epilogue here (the encoder's downsample output is the fp32 stream).
-      // Measured at 7 frames per pass, the family is SLOWER than the e4m3 per-tap gather on all three shapes (255 / 181 / 157 us against
-      // 184 / 133 / 110 us: one 4-wave workgroup per CU does not hide the barriers; profiles/r05_kvae_fp8_encode.log), so it runs only when
-      // the conv_win knob asks for it (1 or 2); by default these convs keep the gather, as the decoder's families follow the faster kernel.
-      if (knob != 1 && knob != 2) return 1;
-      if (a.out_f8) return 1;
-      int rc = launch_win<128, 128, 4, 864, false, true, false, 0, true, false, true>(a, g, s);
-      if (rc == 1) rc = launch_win<128, 128, 4, 568, false, true, false, 16, true, false, true>(a, g, s);
-      return rc;
-    }
-    // The VAE decoder's fp8 mode (128 / 256 / 512 channels, 72 .. 576 px rows) follows the f16 128-column family: linear tiles where the
-    // window fits, else 2-D tiles of 16 output columns.  Fused nearest-2x upsample and the e4m3 output epilogue (out_f8: the resnet that
-    // feeds an upsample conv writes its A operand) are instantiations of their own; the plain family keeps its linear chain unchanged.
-    int rc;
-    if (a.upsample) {
-      rc = eight ? launch_win<256, 128, 8, 416, true, true, true, 0, true>(a, g, s) : launch_win<128, 128, 4, 288, false, true, true, 0, true>(a, g, s);
-      if (rc == 1) rc = eight ? launch_win<256, 128, 8, 104, true, true, true, 16, true>(a, g, s) : launch_win<128, 128, 4, 64, false, true, true, 16, true>(a, g, s);
-      return rc;
-    }
-    if (a.out_f8) {
-      rc = eight ? launch_win<256, 128, 8, 416, true, true, false, 0, true, true>(a, g, s) : launch_win<128, 128, 4, 288, false, true, false, 0, true, true>(a, g, s);
-      if (rc == 1) rc = eight ? launch_win<256, 128, 8, 328, true, true, false, 16, true, true>(a, g, s) : launch_win<128, 128, 4, 184, false, true, false, 16, true, true>(a, g, s);
-      return rc;
-    }
-    rc = eight ? launch_win<256, 128, 8, 416, true, true, false, 0, true>(a, g, s) : launch_win<128, 128, 4, 288, false, true, false, 0, true>(a, g, s);
-    if (rc == 1) rc = eight ? launch_win<128, 128, 4, 288, false, true, false, 0, true>(a, g, s) : launch_win<256, 128, 8, 416, true, true, false, 0, true>(a, g, s);
-    if (rc == 1) rc = eight ? launch_win<256, 128, 8, 328, true, true, false, 16, true>(a, g, s) : launch_win<128, 128, 4, 184, false, true, false, 16, true>(a, g, s);
-    return rc;
-  }
-  if (narrow) {
-    // a conv with a handful of output channels is bound by reading its input: the per-tap gather reads it nine times (head conv of a step:
-    // 346 us), the window once.  32-column tile (one MFMA block per wave column; the upper wave column idles when N <= 16)
-    if (stats || a.upsample) return 1;
-    int rc = launch_win<160, 32, 4, 320, false, false>(a, g, s);
-    if (rc == 1) rc = launch_win<128, 32, 4, 184, false, false, false, 16>(a, g, s);
-    return rc;
-  }
-  if (a.N % 160 != 0) {
-    // 128-column family (the VAE's 128 / 256 / 512 channels): linear tiles where the window fits (72 px rows), else 2-D tiles of 16 output
-    // columns (144 .. 576 px rows).  Two 4-wave workgroups per CU on 128-row tiles: 2 - 11 % faster than the 8-wave 256-row tile on every
-    // decoder shape (profiles/r04_kconvwin_vae.log), which stays behind knob conv_win = 2.
-    const bool eight = knob == 2;
-    int rc;
-    if (a.upsample) {
-      rc = eight ? launch_win<256, 128, 8, 416, true, true, true>(a, g, s) : launch_win<128, 128, 4, 288, false, true, true>(a, g, s);
-      if (rc == 1) rc = eight ? launch_win<256, 128, 8, 104, true, true, true, 16>(a, g, s) : launch_win<128, 128, 4, 64, false, true, true, 16>(a, g, s);
-    } else {
-      rc = eight ? launch_win<256, 128, 8, 416, true, true>(a, g, s) : launch_win<128, 128, 4, 288, false, true>(a, g, s);
-      if (rc == 1) rc = eight ? launch_win<256, 128, 8, 328, true, true, false, 16>(a, g, s) : launch_win<128, 128, 4, 184, false, true, false, 16>(a, g, s);
-    }
-    return rc;
-  }
-  if (a.upsample) {
-    // fused nearest-2x upsample (the three Upsample convs of a step): the window over the SOURCE image is small (a quarter of the pixels),
-    // the 8-wave 256-row tile always fits; the 4-wave family serves launches too small to fill the CUs with 256-row tiles
-    const double t8 = (double)((a.M + 255) / 256) * (double)((a.N + 159) / 160);
-    const bool eight = knob == 2 || (knob != 1 && t8 >= 256.0);
-    int rc = eight ? launch_win<256, 160, 8, 416, true, true, true>(a, g, s) : launch_win<128, 160, 4, 288, false, true, true>(a, g, s);
-    if (rc == 1) rc = eight ? launch_win<128, 160, 4, 288, false, true, true>(a, g, s) : launch_win<256, 160, 8, 416, true, true, true>(a, g, s);
-    return rc;
-  }
-  // Two instantiation families, bitwise equal to each other (same reduction order): two 4-wave workgroups per CU on 160-row tiles
-  // (128 with statistics) or one 8-wave workgroup on a 256-row tile with the window double-buffered.  The 8-wave tile moves a third
-  // fewer LDS-DMA bytes per FLOP and is ~5 % faster where its tile count fills whole rounds of the 256 CUs; the choice is made from
-  // how the launch quantises (measured: 72x72 and 18x18 at batch 42 prefer 8 waves, 36x36 prefers 4: tools/kconvwin.py).  Which of
-  // the two RUNS may depend on the batch.  Whether the window kernel runs at all depends on per-sample dimensions only: a family applies
-  // when one image's tiles fit its window (launch_win), statistics need hw % 64 == 0 at every batch size, and a batch too large for the
-  // 32-bit index arithmetic of the linear tiles is launched as ranges of whole images (n_lin) instead of falling back to the gather.
-  const auto launch4 = [&]() { return stats ? launch_win<128, 160, 4, 288, false, true>(a, g, s) : launch_win<160, 160, 4, 320, false, false>(a, g, s); };
-  const auto launch8 = [&]() { return launch_win<256, 160, 8, 416, true, true>(a, g, s); };
-  bool eight;
-  if (knob == 1 || knob == 2) {
-    eight = knob == 2;
-  } else {
-    eight = eight_waves_quantise_better(a.M, a.N, stats ? 128 : 160, 1);
-  }
-  int rc = eight ? launch8() : launch4();
-  if (rc == 1) rc = eight ? launch4() : launch8();  // the other family may still fit (window capacity is per family)
-  return rc;
-}
-
-// seva_gemm_desc.upsample = 2 / 4: the nearest-2x upsample + 3x3 conv as four 2x2 phase convs on the source image (see PH above).  `a` holds
-// the conv as the caller states it (oh = 2 ih, ow = 2 iw, K = 4 cin, w = [4][N][4 cin]); gemm.hip has refused every epilogue but bias +
-// out_f32 (4: + ch_stats).
-// 0 = launched, 1 = the window kernel does not apply (an ERROR for the caller: no other kernel reads this weight layout), < 0 = error
-int seva_conv_win_phases_launch(const GemmArgs& a0, hipStream_t s) {
-  const int knob = g_seva_knobs.conv_win;
-  if (knob == 0) return 1;
-  if (a0.stride != 1 || a0.pad_lo != 1 || a0.oh != 2 * a0.ih || a0.ow != 2 * a0.iw || a0.iw < 2 || a0.ih < 2) return 1;
-  const bool vae = a0.upsample == 4;  // the 128-column family (2-D tiles, statistics); 2: the 160-column one
-  if (a0.cin % 64 != 0 || a0.N % (vae ? 128 : 160) != 0 || a0.K != 4LL * a0.cin) return 1;
-  GemmArgs a = a0;  // the kernel's view: a plain conv over the SOURCE image, one launch row per source pixel
-  a.oh = a0.ih;
-  a.ow = a0.iw;
-  a.M = (int64_t)a0.n * a0.ih * a0.iw;
-  ConvWinGeom g;
-  if (win_geometry(a, false, g) != 0) return 1;
-  if (vae) {
-    // As the plain 128-column family: two 4-wave workgroups per CU on 128-row tiles, linear where the window fits (72 px source rows), else
-    // 2-D; the 8-wave 256-row tiles behind knob 2.  No other kernel reads these weights, so where the 8-wave tiles do not apply (a 2-D
-    // tile of 16 source rows on an image of 8) knob 2 still takes the 4-wave ones: same reduction order, same bits.
-    int rc = 1;
-    if (knob == 2) {
-      rc = launch_win<256, 128, 8, 416, true, true, false, 0, false, false, false, true>(a, g, s);
-      if (rc == 1) rc = launch_win<256, 128, 8, 328, true, true, false, 16, false, false, false, true>(a, g, s);
-    }
-    if (rc == 1) rc = launch_win<128, 128, 4, 288, false, true, false, 0, false, false, false, true>(a, g, s);
-    if (rc == 1) rc = launch_win<128, 128, 4, 184, false, true, false, 16, false, false, false, true>(a, g, s);
-    return rc;
-  }
-  // the plain conv's two families, bitwise equal (same reduction order), chosen by the same quantisation rule with four workgroups per tile
-  const auto launch4 = [&]() { return launch_win<160, 160, 4, 320, false, false, false, 0, false, false, false, true>(a, g, s); };
-  const auto launch8 = [&]() { return launch_win<256, 160, 8, 416, true, false, false, 0, false, false, false, true>(a, g, s); };
-  const bool eight = knob == 1 || knob == 2 ? knob == 2 : eight_waves_quantise_better(a.M, a.N, 160, 4);
-  int rc = eight ? launch8() : launch4();
-  if (rc == 1) rc = eight ? launch4() : launch8();
-  return rc;
+int seva_conv_win_launch(const GemmArgs& a0, const seva_plan::WinPlan& w, hipStream_t s) {
+  const seva_plan::WinCfg none{};
+  const seva_plan::WinCfg& c = w.win >= 0 ? w.cand[w.win] : none;
+  GemmArgs a = a0;  // the kernel's view (the phase modes: a plain conv over the SOURCE image, one launch row per source pixel)
+  a.oh = w.problem.oh;
+  a.ow = w.problem.ow;
+  a.M = w.problem.M;
+#define SEVA_LAUNCH_ROW(NAME, BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH)                               \
+  if (seva_plan::same_kernel(c, seva_plan::WinCfg{BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH}))      \
+    return launch_win<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH>(a, w, s);
+  SEVA_WIN_KERNELS(SEVA_LAUNCH_ROW)
+#undef SEVA_LAUNCH_ROW
+  seva_set_error("conv_win: internal error: no conv_win_kernel<%d, %d, %d, %d> instantiation with dbw %d stats %d up %d tw %d fp8 %d o8 %d s2 %d "
+                 "ph %d (candidate %d of %d)", c.bm, c.bn, c.nw, c.wcap, c.dbw, c.stats, c.up, c.tw, c.fp8, c.o8, c.s2, c.ph, w.win, w.n_cand);
+  return SEVA_ERR_ARG;
 }

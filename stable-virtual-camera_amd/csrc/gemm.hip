@@ -826,106 +826,58 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
   }
 }
 
-template <int BM, int BN, int MODE, int EPI, bool PAIRED, bool ASTAT = false, bool FP8 = false, bool SPLITK = false, int NW = 4,
-          bool SPLIT16 = false>
-int launch_p(const GemmArgs& a, hipStream_t s) {
+
+// Launches one row of the instantiation table (gemm_plan.h: SEVA_GEMM_KERNELS) with the plan's schedule.
+template <int BM, int BN, int MODE, int EPI, bool PAIRED, bool ASTAT, bool FP8, bool SPLITK, int NW, bool SPLIT16>
+int launch_p(const GemmArgs& a, const seva_plan::Plan& p, hipStream_t s) {
   // + bias slots (ASYNC) + weight-scale slots (FP8 ASYNC)
   constexpr int lds = 2 * ((ASTAT ? 0 : BM) + BN) * 128 + (ASTAT ? 8192 : PAIRED ? 4096 : 0) + (FP8 && PAIRED ? 4096 : 0);
-  constexpr bool DBG_BUILD = !ASTAT && !FP8 && !SPLITK && NW == 4 && !SPLIT16;  // the ablation instantiation only exists for the staged-A f16 kernels
-  // the dynamic-LDS attribute is per device: one bit per device ordinal and instantiation (a second GPU in the
-  // same process would otherwise launch 72-80 KB kernels without it)
+  constexpr seva_plan::GemmCfg kRow{BM, BN, MODE, EPI, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16, false};
+  constexpr bool DBG_BUILD = seva_plan::has_dbgk(kRow);
   static std::atomic<uint64_t> attr_devs{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t dev_bit = 1ull << (dev & 63);
-  if (!(attr_devs.load(std::memory_order_relaxed) & dev_bit)) {
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, MODE, EPI, false, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if constexpr (DBG_BUILD)
-      (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, MODE, EPI, true, PAIRED, false>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_devs.fetch_or(dev_bit, std::memory_order_relaxed);
+  const void* const production = (const void*)gemm_kernel<BM, BN, MODE, EPI, false, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16>;
+  if constexpr (DBG_BUILD) {
+    seva_max_dynamic_lds_once(attr_devs, lds, {production, (const void*)gemm_kernel<BM, BN, MODE, EPI, true, PAIRED, false>});
+  } else {
+    seva_max_dynamic_lds_once(attr_devs, lds, {production});
   }
   GemmArgs args = a;
-  args.tiles_m = (int)((a.M + BM - 1) / BM);
-  args.tiles_n = (int)((a.N + BN - 1) / BN);
-  // Schedule: an M-tile's N-tiles are split over `chunks` sibling workgroups that are adjacent in the
-  // XCD-remapped order, i.e. co-resident on one XCD: they stream the same A row-panel through that
-  // XCD's L2 at the same time.  One workgroup walking ALL N-tiles (the former default for big M)
-  // re-reads an 80..320 KB panel per N-tile while 512 such panels (40..160 MB) compete for 32 MB of
-  // L2.  Measured over every shape of a step (tools/ksweep_chunks.py, profiles/r01_ksweep_chunks.log):
-  // narrow outputs (<= 5 N-tiles) want one tile per workgroup, wide ones ~4 tiles per workgroup, and
-  // the split must be even (2,1,1,1 tiles is 30 % slower than 1,1,1,1,1).
-  constexpr int kTargetBlocks = 1024;
-  const int base = (kTargetBlocks + args.tiles_m - 1) / args.tiles_m;  // >= two rounds of the chip
-  int chunks;
-  if (args.tiles_n <= 5) {
-    chunks = args.tiles_n;
-  } else {
-    int per = 0;
-    for (int t : {4, 5, 3, 2})
-      if (args.tiles_n % t == 0) { per = t; break; }
-    chunks = per ? args.tiles_n / per : (args.tiles_n + 3) / 4;
-  }
-  if (ASTAT) chunks = 1;  // the A panel sits in registers: re-loading it per sibling is pure cost (re-swept: c1 best)
-  if (chunks < base) {
-    chunks = base;
-    for (int c = base; c <= 2 * base && c <= args.tiles_n; ++c)  // nearest even split above `base`
-      if (args.tiles_n % c == 0) { chunks = c; break; }
-  }
-  // knob gemm_chunks (SEVA_GEMM_CHUNKS=n, benchmarking) overrides the heuristic
-  if (g_seva_knobs.gemm_chunks > 0) chunks = g_seva_knobs.gemm_chunks;
-  if (chunks < 1) chunks = 1;
-  if (chunks > args.tiles_n) chunks = args.tiles_n;
-  args.n_chunks = chunks;
-  args.dbg = g_seva_knobs.gemm_dbg > 0 ? g_seva_knobs.gemm_dbg : 0;
-  args.stagger = g_seva_knobs.gemm_stagger > 0 ? g_seva_knobs.gemm_stagger : 0;
-  int64_t nb = (int64_t)args.tiles_m * chunks;
-  if (SPLITK) nb *= 2;  // split-K: producers (upper half of K) in the first half of the grid, consumers in the second
-  if (nb <= 0 || nb > 0x7fffffff) {
-    seva_set_error("gemm: bad grid %lld", (long long)nb);
+  args.tiles_m = p.tiles_m;
+  args.tiles_n = p.tiles_n;
+  args.n_chunks = p.n_chunks;
+  args.dbg = p.dbg;
+  args.stagger = p.stagger;
+  if (p.grid <= 0 || p.grid > 0x7fffffff) {
+    seva_set_error("gemm: bad grid %lld", (long long)p.grid);
     return SEVA_ERR_ARG;
   }
   if constexpr (DBG_BUILD) {
-    if (args.dbg || args.stagger) {
-      hipLaunchKernelGGL((gemm_kernel<BM, BN, MODE, EPI, true, PAIRED, false>), dim3((unsigned)nb), dim3(256), lds, s, args);
+    if (p.gemm.dbgk) {
+      hipLaunchKernelGGL((gemm_kernel<BM, BN, MODE, EPI, true, PAIRED, false>), dim3((unsigned)p.grid), dim3(256), lds, s, args);
       return seva_check_launch("gemm_kernel");
     }
   }
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, MODE, EPI, false, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16>), dim3((unsigned)nb), dim3(64 * NW), lds, s, args);
+  hipLaunchKernelGGL((gemm_kernel<BM, BN, MODE, EPI, false, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16>), dim3((unsigned)p.grid), dim3(64 * NW), lds, s, args);
   return seva_check_launch("gemm_kernel");
 }
 
-template <int BM, int BN, int MODE, int EPI, bool FP8 = false>
-int launch(const GemmArgs& a, hipStream_t s) {
-  // knob gemm_astat = 0 (SEVA_GEMM_ASTAT=0) disables the A-in-registers variant (benchmarking)
-  const bool astat_on = g_seva_knobs.gemm_astat != 0;
-  const bool dbg_run = g_seva_knobs.gemm_dbg >= 0 || g_seva_knobs.gemm_stagger >= 0;
-  const bool half_out = a.out_f16 || (FP8 && a.out_f8);  // 2-byte (or e4m3) outputs only: ASYNC schedule
-  // (the A-in-registers variant is f16-only: with both k-steps' fragments live for one 128-deep MFMA it spills)
-  if constexpr (EPI == 1) {
-    if constexpr (BM == 128 && !FP8) {
-      if (astat_on && !dbg_run && a.K <= 320 && half_out && !a.out_f32) return launch_p<BM, BN, MODE, EPI, true, true, FP8>(a, s);
-    }
-    return launch_p<BM, BN, MODE, EPI, true, false, FP8>(a, s);
-  } else {
-    if constexpr (MODE == 0 && BN >= 128) {
-      if (a.out_f16 && !a.out_f32 && !a.residual) {
-        if constexpr (BM == 128 && !FP8) {
-          if (astat_on && !dbg_run && a.K <= 320) return launch_p<BM, BN, MODE, EPI, true, true, FP8>(a, s);
-        }
-        return launch_p<BM, BN, MODE, EPI, true, false, FP8>(a, s);
-      }
-    }
-    return launch_p<BM, BN, MODE, EPI, false, false, FP8>(a, s);
-  }
+// the plan's gemm_kernel configuration -> its row of the table
+int launch_gemm(const GemmArgs& a, const seva_plan::Plan& p, hipStream_t s) {
+#define SEVA_LAUNCH_ROW(NAME, BM, BN, MODE, EPI, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16)                                          \
+  if (seva_plan::same_kernel(p.gemm, seva_plan::GemmCfg{BM, BN, MODE, EPI, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16, false}))    \
+    return launch_p<BM, BN, MODE, EPI, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16>(a, p, s);
+  SEVA_GEMM_KERNELS(SEVA_LAUNCH_ROW)
+#undef SEVA_LAUNCH_ROW
+  const seva_plan::GemmCfg& c = p.gemm;
+  seva_set_error("gemm: internal error: no gemm_kernel<%d, %d, %d, %d> instantiation with dbgk %d paired %d astat %d fp8 %d splitk %d nw %d "
+                 "split16 %d", c.bm, c.bn, c.mode, c.epi, c.dbgk, c.paired, c.astat, c.fp8, c.splitk, c.nw, c.split16);
+  return SEVA_ERR_ARG;
 }
 
-}  // namespace
-
-namespace {
-template <bool FP8, bool SPLIT16 = false>
-int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
+// Everything a descriptor can be refused for before a kernel is chosen.  (What only the chosen kernel can refuse -- a window-only conv the
+// window kernel declines, a split-K workspace too small for the tiles -- follows the plan in gemm_entry.)
+template <bool FP8, bool SPLIT16>
+int validate(const seva_gemm_desc* d) {
   SEVA_REQUIRE(d != nullptr, "gemm: null desc");
   if constexpr (SPLIT16) {
     // what the split-precision output does not do is an error, never a fall-back to a plain f16 output
@@ -962,36 +914,16 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
   SEVA_REQUIRE((!d->residual || d->ldr % 4 == 0) && (!d->out_f32 || d->ldo32 % 4 == 0) &&
                    (!d->out_f16 || d->ldo16 % 4 == 0),
                "gemm: row pitches must be multiples of 4");
-  GemmArgs a{};
-  a.a = (const half_t*)d->a;
-  a.w = (const half_t*)d->w;
-  a.bias = d->bias;
-  a.row_add = d->row_add;
-  a.residual = d->residual;
-  a.out_f32 = d->out_f32;
-  a.out_f16 = (half_t*)d->out_f16;
-  a.out_f8 = (uint8_t*)d->out_f8;
-  a.w_exp = (const uint8_t*)d->w_exp;
-  a.ch_stats = d->ch_stats;
-  a.sk_ws = nullptr;
   SEVA_REQUIRE(!d->ch_stats || (d->out_f32 && d->epilogue == 0 && d->N >= 128 && (uintptr_t)d->ch_stats % 16 == 0 &&
                                 d->col_scale_n == 0),
                "gemm: ch_stats needs the plain epilogue with an fp32 output, N >= 128, no col_scale, a 16-byte aligned buffer");
-  a.M = d->M; a.N = d->N; a.K = d->K / KU;
-  a.lda = d->lda / KU; a.ldr = d->ldr; a.ldo32 = d->ldo32; a.ldo16 = d->ldo16; a.ldo8 = d->ldo8;
-  a.rows_per_group = d->rows_per_group > 0 ? d->rows_per_group : 1;
-  a.col_scale = d->col_scale;
-  a.col_scale_n = d->col_scale_n;
   SEVA_REQUIRE(d->col_scale_n >= 0 && d->col_scale_n % 4 == 0 && d->col_scale_n <= d->N,
                "gemm: col_scale_n=%d invalid", d->col_scale_n);
   SEVA_REQUIRE(d->col_scale_n == 0 || (d->mode == 0 && !d->residual && !d->row_add && d->epilogue == 0 && d->N > 32),
                "gemm: col_scale needs mode 0 (no convolution) and the plain epilogue without residual / row_add");
-  a.ldra = d->ld_row_add > 0 ? d->ld_row_add : d->N;
-  SEVA_REQUIRE(a.ldra % 4 == 0, "gemm: ld_row_add must be a multiple of 4");
-  // upsample = 2: the fused nearest-2x upsample as four 2x2 phase convs on the source image (conv_win.hip: PH); w = [4][N][4 cin]
-  // upsample = 4: the same on the 128-column family, with GroupNorm statistics (the VAE decoders' upsample convs)
+  SEVA_REQUIRE((d->ld_row_add > 0 ? d->ld_row_add : d->N) % 4 == 0, "gemm: ld_row_add must be a multiple of 4");
   const bool phases128 = d->mode == 1 && d->upsample == 4;
-  const bool phases = (d->mode == 1 && d->upsample == 2) || phases128;
+  const bool phases = seva_plan::is_phases(*d);
   SEVA_REQUIRE(d->mode != 1 || (d->upsample >= 0 && d->upsample <= 2) || d->upsample == 4, "conv: upsample=%d (0, 1, 2 or 4)", d->upsample);
   if (phases128) {
     // as for value 2: what the family does not do is an error, never a fall-back
@@ -1020,9 +952,6 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
                        (uintptr_t)d->a2 % 16 == 0 && d->N > 32 && d->out_f32,
                    "conv: the folded second operand a2 needs the f16 stride-any 3x3 conv without upsample, K2 %% 64 == 0, lda2 >= K2 "
                    "(multiple of 8), N > 32, an fp32 output");
-      a.a2 = (const half_t*)d->a2;
-      a.lda2 = d->lda2;
-      a.nk1 = (int)(9LL * d->cin / BK);
     }
     SEVA_REQUIRE(d->stride == 1 || d->stride == 2, "conv: stride %d", d->stride);
     SEVA_REQUIRE(!(d->upsample && d->stride != 1), "conv: upsample needs stride 1");
@@ -1032,157 +961,104 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
                  "conv: output %dx%d inconsistent with input %dx%d stride %d up %d pad_br_only %d", d->oh, d->ow,
                  d->ih, d->iw, d->stride, d->upsample, d->pad_br_only);
     SEVA_REQUIRE(d->M == (int64_t)d->n * d->oh * d->ow, "conv: M != n*oh*ow");
-    a.n = d->n; a.ih = d->ih; a.iw = d->iw; a.cin = d->cin / KU; a.oh = d->oh; a.ow = d->ow;
-    a.stride = d->stride; a.upsample = d->upsample;
-    a.pad_lo = d->pad_br_only ? 0 : 1;
   } else {
     SEVA_REQUIRE(d->lda >= d->K && d->lda % (8 * KU) == 0, "gemm: lda=%lld invalid", (long long)d->lda);
   }
-  hipStream_t s = (hipStream_t)stream;
   // (phases: the reference-equivalent reduction is the nine taps, longer than the executed four)
   SEVA_REQUIRE(d->alg_K >= 0 && d->alg_K <= (phases ? 9LL * d->cin : d->K), "gemm: alg_K=%lld outside [0, K]", (long long)d->alg_K);
-  const double flops = 2.0 * (double)d->M * (double)d->N * (double)(d->alg_K > 0 ? d->alg_K : d->K);  // reference-equivalent FLOP (seva_hip.h)
-  // algorithmic HBM bytes: A (conv: the NHWC image) and W read once, residual read once, each output written once
-  const double a_elems = (d->mode == 1 ? (double)d->n * d->ih * d->iw * d->cin : (double)d->M * (double)d->K);
-  const double a2_bytes = (d->mode == 1 && d->a2) ? 2.0 * (double)d->M * (double)d->K2 : 0.0;
-  const double n_out = d->epilogue == 1 ? (double)d->N / 2 : (double)d->N;
-  const double esz = FP8 ? 1.0 : 2.0;
-  const double alg_bytes = esz * a_elems + a2_bytes + esz * (double)d->N * (double)d->K * (phases ? 4.0 : 1.0) + (d->bias ? 4.0 * (double)d->N : 0.0) +
-                           (double)d->M * n_out * ((d->residual ? 4.0 : 0.0) + (d->out_f32 ? 4.0 : 0.0) +
-                                                   (d->out_f16 ? 2.0 : 0.0) + (d->out_f8 ? 1.0 : 0.0));
-  SevaProfScope prof(d->mode == 1 ? 1 : 0, flops, s, alg_bytes);
   if (phases) {
     SEVA_REQUIRE(d->epilogue == 0, "conv: the phase-decomposed upsample has the plain epilogue only");
-    const int rc = seva_conv_win_phases_launch(a, s);
-    SEVA_REQUIRE(rc != 1, "conv: the phase-decomposed upsample runs on the window kernel only, which declined it (image %dx%d, cin %d, N %lld: "
-                 "stride 1, pad 1, one image's tiles must fit the window -- upsample = 4: or iw %% 16 == 0 and ih %% 8 == 0 for the 2-D tiles; conv_win "
-                 "knob not 0)", d->ih, d->iw, d->cin, (long long)d->N);
-    return rc;
-  }
-  if (d->epilogue == 1) {
+  } else if (d->epilogue == 1) {
     SEVA_REQUIRE(d->N % 64 == 0, "geglu: N=%lld not a multiple of 64", (long long)d->N);
     SEVA_REQUIRE(d->mode == 0, "geglu: plain mode only");
     SEVA_REQUIRE(!d->out_f16 || d->ldo16 % 8 == 0, "geglu: f16 row pitch must be a multiple of 8");
   }
-  const bool narrow = d->N <= 32;
-  if constexpr (SPLIT16) {
-    // one tile shape per epilogue and width, whatever M: nothing about a row's result depends on the batch
-    if (d->epilogue == 1) return launch_p<128, 128, 0, 1, true, false, false, false, 4, true>(a, s);
-    if (d->N % 160 == 0) return launch_p<128, 160, 0, 0, false, false, false, false, 4, true>(a, s);
-    return launch_p<128, 128, 0, 0, false, false, false, false, 4, true>(a, s);
-  } else if constexpr (FP8) {
-    // e4m3 operands: the K >= 640 GEMMs / cin >= 640 convs of the ds2..ds8 levels.  Same tile-shape heuristics.
-    bool half_m8 = ((d->M + 127) / 128) * ((d->N + 159) / 160) < 320 && d->M > 64;
-    if (g_seva_knobs.gemm_bm > 0) half_m8 = g_seva_knobs.gemm_bm == 64;
-    if (d->ch_stats) half_m8 = false;  // statistics are emitted per wave-owned 64-row block: 128-row tiles only
-    bool wide8 = d->N % 160 == 0;
-    if (g_seva_knobs.gemm_bn > 0) wide8 = g_seva_knobs.gemm_bn == 160;
-    // (160-row GEGLU tiles, the f16 default, were measured here too: 255 registers with a small spill, no gain)
-    if (d->epilogue == 1) return half_m8 ? launch<64, 128, 0, 1, true>(a, s) : launch<128, 128, 0, 1, true>(a, s);
-    // 128-row tiles are 128 wide only: 128x160 with both k-steps' fragments live exceeds 256 VGPRs (spills)
-    if (d->mode == 0) {
-      if (half_m8) return wide8 ? launch<64, 160, 0, 0, true>(a, s) : launch<64, 128, 0, 0, true>(a, s);
-      return launch<128, 128, 0, 0, true>(a, s);
+  return 0;
+}
+
+// the kernels' view of a validated descriptor (the plan adds tiles, chunks and the split-K workspace)
+template <bool FP8>
+GemmArgs kernel_args(const seva_gemm_desc* d) {
+  constexpr int KU = FP8 ? 2 : 1;
+  GemmArgs a{};
+  a.a = (const half_t*)d->a;
+  a.w = (const half_t*)d->w;
+  a.bias = d->bias;
+  a.row_add = d->row_add;
+  a.residual = d->residual;
+  a.out_f32 = d->out_f32;
+  a.out_f16 = (half_t*)d->out_f16;
+  a.out_f8 = (uint8_t*)d->out_f8;
+  a.w_exp = (const uint8_t*)d->w_exp;
+  a.ch_stats = d->ch_stats;
+  a.sk_ws = nullptr;
+  a.M = d->M; a.N = d->N; a.K = d->K / KU;
+  a.lda = d->lda / KU; a.ldr = d->ldr; a.ldo32 = d->ldo32; a.ldo16 = d->ldo16; a.ldo8 = d->ldo8;
+  a.rows_per_group = d->rows_per_group > 0 ? d->rows_per_group : 1;
+  a.col_scale = d->col_scale;
+  a.col_scale_n = d->col_scale_n;
+  a.ldra = d->ld_row_add > 0 ? d->ld_row_add : d->N;
+  if (d->mode == 1) {
+    if (d->a2) {
+      a.a2 = (const half_t*)d->a2;
+      a.lda2 = d->lda2;
+      a.nk1 = (int)(9LL * d->cin / BK);
     }
-    // 3x3 / stride 1 / pad 1 convs and the stride-2 bottom / right-padded ones: the window-staged kernel (conv_win.hip, e4m3 instantiations)
-    const bool win_on = g_seva_knobs.conv_win != 0 && g_seva_knobs.gemm_dbg < 0 && g_seva_knobs.gemm_bm <= 0 && g_seva_knobs.gemm_bn <= 0 &&
-                        g_seva_knobs.gemm_chunks <= 0;
-    if (d->mode == 1 && d->a2 == nullptr && win_on) {
-      const int rc = seva_conv_win_launch(a, s, true);
-      if (rc <= 0) return rc;
-    }
-    // e4m3 stride 2 + pad_br_only (the VAE encoder's fp8 downsample convs): the per-tap gather by default (measured faster, conv_win.hip);
-    // where the conv_win knob asks for the stride-2 window family (1 or 2) and it declines, an error, not a silent fall-back to the gather
-    SEVA_REQUIRE(!(d->mode == 1 && win_on && (g_seva_knobs.conv_win == 1 || g_seva_knobs.conv_win == 2) && d->stride == 2 && d->pad_br_only &&
-                   d->N % 128 == 0),
-                 "gemm fp8: the stride-2 bottom/right-padded conv runs on the window kernel only, which declined it (image %dx%d -> %dx%d, "
-                 "cin %d: no e4m3 output, statistics need oh*ow %% 64 == 0, 2-D tiles need ow %% 16 == 0 and oh %% 8 == 0, linear tiles a "
-                 "window of at most 864 slots)", d->ih, d->iw, d->oh, d->ow, d->cin);
-    // the per-tap gather below has neither the fused upsample nor the e4m3 output in conv mode: only the window kernel runs those
-    SEVA_REQUIRE(!(d->mode == 1 && (d->upsample || d->out_f8)),
-                 "gemm fp8: a conv with %s runs on the window kernel only, which declined it (3x3 / stride 1 / pad 1, N %% 128 == 0, "
-                 "image tiles must fit its window; conv_win knob not 0)", d->upsample ? "the fused upsample" : "out_f8");
-    if (half_m8) return wide8 ? launch<64, 160, 1, 0, true>(a, s) : launch<64, 128, 1, 0, true>(a, s);
-    return launch<128, 128, 1, 0, true>(a, s);
-  } else {
-  // Small problems (the ds8 level: 27 x 8 tiles of 128 rows on 512 workgroup slots) get 64-row tiles: twice the
-  // workgroups, both slots of a CU busy.  SEVA_GEMM_BM=64|128 forces the height (benchmark knob).
-  bool half_m = ((d->M + 127) / 128) * ((d->N + 159) / 160) < 320 && d->M > 64;
-  if (g_seva_knobs.gemm_bm > 0) half_m = g_seva_knobs.gemm_bm == 64;
-  if (d->ch_stats) half_m = false;  // statistics are emitted per wave-owned 64-row block: 128-row tiles only
-  const bool two_src = d->mode == 1 && d->a2 != nullptr;  // MODE 3: instantiated for 128- and 160-row tiles, never split-K
-  if (two_src) half_m = false;
-  // Split-K = 2 for convolutions over SMALL IMAGES (<= 128 output pixels per sample: the ds8 level, 9 x 9) with a long
-  // reduction: 128-row tiles, two workgroups per tile, instead of 64-row tiles.  The choice looks at per-sample dimensions
-  // only, so a sample's result does not depend on the batch size.
-  if (d->splitk_ws && d->mode == 1 && !two_src && !d->upsample && !narrow && (int64_t)d->oh * d->ow <= 128 && d->K / BK >= 16 &&
-      (d->K / BK) % 2 == 0 && g_seva_knobs.gemm_bm <= 0 && g_seva_knobs.gemm_dbg < 0 && g_seva_knobs.gemm_stagger < 0) {
-    const int bn = (g_seva_knobs.gemm_bn > 0 ? g_seva_knobs.gemm_bn == 160 : d->N % 160 == 0) ? 160 : 128;
-    const int64_t tiles = ((d->M + 127) / 128) * ((d->N + bn - 1) / bn);
+    a.n = d->n; a.ih = d->ih; a.iw = d->iw; a.cin = d->cin / KU; a.oh = d->oh; a.ow = d->ow;
+    a.stride = d->stride; a.upsample = d->upsample;
+    a.pad_lo = d->pad_br_only ? 0 : 1;
+  }
+  return a;
+}
+
+// what the profiler credits a launch with (seva_hip.h)
+struct GemmWork { double flops, bytes; };
+GemmWork gemm_work(const seva_gemm_desc* d, bool fp8) {
+  const bool phases = seva_plan::is_phases(*d);
+  const double flops = 2.0 * (double)d->M * (double)d->N * (double)(d->alg_K > 0 ? d->alg_K : d->K);  // reference-equivalent FLOP
+  // algorithmic HBM bytes: A (conv: the NHWC image) and W read once, residual read once, each output written once
+  const double a_elems = (d->mode == 1 ? (double)d->n * d->ih * d->iw * d->cin : (double)d->M * (double)d->K);
+  const double a2_bytes = (d->mode == 1 && d->a2) ? 2.0 * (double)d->M * (double)d->K2 : 0.0;
+  const double n_out = d->epilogue == 1 ? (double)d->N / 2 : (double)d->N;
+  const double esz = fp8 ? 1.0 : 2.0;
+  const double bytes = esz * a_elems + a2_bytes + esz * (double)d->N * (double)d->K * (phases ? 4.0 : 1.0) + (d->bias ? 4.0 * (double)d->N : 0.0) +
+                       (double)d->M * n_out * ((d->residual ? 4.0 : 0.0) + (d->out_f32 ? 4.0 : 0.0) +
+                                               (d->out_f16 ? 2.0 : 0.0) + (d->out_f8 ? 1.0 : 0.0));
+  return {flops, bytes};
+}
+
+// validate -> account -> plan -> launch
+template <bool FP8, bool SPLIT16 = false>
+int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
+  if (const int rc = validate<FP8, SPLIT16>(d)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const GemmWork work = gemm_work(d, FP8);
+  SevaProfScope prof(d->mode == 1 ? 1 : 0, work.flops, s, work.bytes);
+  const seva_plan::Plan p = seva_plan::plan(*d, g_seva_knobs, SPLIT16 ? seva_plan::F16_SPLIT_OUT : FP8 ? seva_plan::FP8 : seva_plan::F16);
+  SEVA_REQUIRE(p.declined != seva_plan::DECLINED_PHASES,
+               "conv: the phase-decomposed upsample runs on the window kernel only, which declined it (image %dx%d, cin %d, N %lld: "
+               "stride 1, pad 1, one image's tiles must fit the window -- upsample = 4: or iw %% 16 == 0 and ih %% 8 == 0 for the 2-D tiles; conv_win "
+               "knob not 0)", d->ih, d->iw, d->cin, (long long)d->N);
+  SEVA_REQUIRE(p.declined != seva_plan::DECLINED_FP8_STRIDE2,
+               "gemm fp8: the stride-2 bottom/right-padded conv runs on the window kernel only, which declined it (image %dx%d -> %dx%d, "
+               "cin %d: no e4m3 output, statistics need oh*ow %% 64 == 0, 2-D tiles need ow %% 16 == 0 and oh %% 8 == 0, linear tiles a "
+               "window of at most 864 slots)", d->ih, d->iw, d->oh, d->ow, d->cin);
+  SEVA_REQUIRE(p.declined != seva_plan::DECLINED_FP8_WINDOW_ONLY,
+               "gemm fp8: a conv with %s runs on the window kernel only, which declined it (3x3 / stride 1 / pad 1, N %% 128 == 0, "
+               "image tiles must fit its window; conv_win knob not 0)", d->upsample ? "the fused upsample" : "out_f8");
+  GemmArgs a = kernel_args<FP8>(d);
+  if (p.kernel == seva_plan::WINDOW_KERNEL) return seva_conv_win_launch(a, p.window, s);
+  if (p.gemm.splitk) {
     SEVA_REQUIRE((uintptr_t)d->splitk_ws % 16 == 0, "gemm: splitk_ws must be 16-byte aligned");
     // A workspace that cannot hold this launch's tiles is an ERROR (it was a silent fall-back to the unsplit 64-row kernel in
     // round 3: the reduction order of a sample would then have depended on the batch it was launched in and on the size of the
     // caller's workspace -- the opposite of what the per-sample split rule promises).  Size it with the formula of seva_hip.h.
-    SEVA_REQUIRE(tiles < 16383 && d->splitk_ws_bytes >= (int64_t)(16384 + tiles * 128 * bn) * 4,
+    SEVA_REQUIRE(p.sk_tiles < 16383 && d->splitk_ws_bytes >= (int64_t)(16384 + p.sk_tiles * 128 * p.sk_bn) * 4,
                  "gemm: splitk_ws too small for this launch: %lld tiles of 128 x %d need %lld bytes (and fewer than 16383 tiles), got %lld",
-                 (long long)tiles, bn, (long long)((16384 + tiles * 128 * bn) * 4), (long long)d->splitk_ws_bytes);
+                 (long long)p.sk_tiles, p.sk_bn, (long long)((16384 + p.sk_tiles * 128 * p.sk_bn) * 4), (long long)d->splitk_ws_bytes);
     a.sk_ws = d->splitk_ws;
-    half_m = false;
   }
-  // 3x3 / stride 1 / pad 1 convs whose tile window fits LDS: the input window (+ halo) is staged once per 64-channel slab and the nine
-  // taps read it through shifted fragment addresses (conv_win.hip); everything else keeps the per-tap gather below
-  if (d->mode == 1 && !two_src && g_seva_knobs.gemm_dbg < 0 && g_seva_knobs.gemm_stagger < 0 && g_seva_knobs.gemm_bm <= 0 &&
-      g_seva_knobs.gemm_bn <= 0 && g_seva_knobs.gemm_chunks <= 0) {
-    const int rc = seva_conv_win_launch(a, s);
-    if (rc <= 0) return rc;
-  }
-  if (d->epilogue == 1) {
-    // GEGLU tiles are 128 wide (the epilogue pairs 64-row value / gate groups), so the cheaper operand stream comes from the
-    // other side: 160 x 128 tiles -- 10 % fewer LDS-DMA bytes per FLOP, 40 instead of 32 MFMAs per wave and barrier, 215
-    // registers, still two workgroups per CU.  Bitwise the same outputs; ds2 / ds4 -6 %, the 9x9 level -15 % against its 64-row
-    // tiles (tools/kgeglu_bm.py).  K <= 320 keeps the A-in-registers kernel (a 128-row design).
-    const bool dbg_run = g_seva_knobs.gemm_dbg >= 0 || g_seva_knobs.gemm_stagger >= 0;
-    const bool tall = g_seva_knobs.gemm_bm == 160 || (g_seva_knobs.gemm_bm <= 0 && !dbg_run && d->K > 320 && d->M >= 1024);
-    if (tall) return launch_p<160, 128, 0, 1, true>(a, s);
-    return half_m ? launch<64, 128, 0, 1>(a, s) : launch<128, 128, 0, 1>(a, s);
-  }
-  // 128x160 tiles: every channel count of the network (320 .. 10240) is a multiple of 160, so no MFMA
-  // column is idle (N = 320: 2 tiles instead of 3 with the last half empty), and a tile needs 10 %
-  // fewer LDS-DMA bytes and fragment reads per FLOP than 128x128.  (128x64 tiles, tried earlier, were
-  // 5-25 % slower: profiles/r01_kbench_bn64.log.)  SEVA_GEMM_BN=128|160 forces the width (benchmark knob).
-  bool wide = d->N % 160 == 0;
-  if (g_seva_knobs.gemm_bn > 0) wide = g_seva_knobs.gemm_bn == 160;
-  // 160 x 160 tiles for the fp32-output kernels (not the f16-only ASYNC ones: their bias slots would not fit): 0.0125 operand bytes
-  // per FLOP instead of 0.0141, 50 instead of 40 MFMAs per wave and barrier; two workgroups take EXACTLY the CU's 160 KiB of LDS
-  // and all 256 registers (no spill in GEMM mode, 7 dwords in conv mode).  Bitwise the same outputs; -3 ... -10 % on every shape
-  // measured, also where 160-row tiles quantise worse (tools/ktile160.py).  Launches that emit GroupNorm statistics keep 128
-  // rows (a wave must own a 64-row block), as do the small ones (64-row tiles / split-K) and the fused-upsample conv.
-  {
-    const bool dbg_run = g_seva_knobs.gemm_dbg >= 0 || g_seva_knobs.gemm_stagger >= 0;
-    const bool f16_only = d->mode == 0 && d->out_f16 && !d->out_f32 && !d->residual;
-    const bool big = g_seva_knobs.gemm_bm == 160 ||
-                     (g_seva_knobs.gemm_bm <= 0 && g_seva_knobs.gemm_bn <= 0 && g_seva_knobs.gemm_chunks <= 0 && !dbg_run && !half_m && d->M >= 2048);
-    if (big && wide && !narrow && !d->ch_stats && !d->upsample && !a.sk_ws && !f16_only) {
-      if (two_src) return launch_p<160, 160, 3, 0, false>(a, s);
-      return d->mode == 0 ? launch_p<160, 160, 0, 0, false>(a, s) : launch_p<160, 160, 1, 0, false>(a, s);
-    }
-  }
-  if (two_src) return wide ? launch<128, 160, 3, 0>(a, s) : launch<128, 128, 3, 0>(a, s);
-  if (d->mode == 0) {
-    if (narrow) return launch<128, 32, 0, 0>(a, s);
-    if (half_m) return wide ? launch<64, 160, 0, 0>(a, s) : launch<64, 128, 0, 0>(a, s);
-    return wide ? launch<128, 160, 0, 0>(a, s) : launch<128, 128, 0, 0>(a, s);
-  }
-  if (d->upsample) {  // the three Upsample convs of a step: general gather (MODE 2)
-    if (narrow) return launch<128, 32, 2, 0>(a, s);
-    if (half_m) return wide ? launch<64, 160, 2, 0>(a, s) : launch<64, 128, 2, 0>(a, s);
-    return wide ? launch<128, 160, 2, 0>(a, s) : launch<128, 128, 2, 0>(a, s);
-  }
-  if (narrow) return launch<128, 32, 1, 0>(a, s);
-  if (a.sk_ws) return wide ? launch_p<128, 160, 1, 0, false, false, false, true>(a, s) : launch_p<128, 128, 1, 0, false, false, false, true>(a, s);
-  if (half_m) return wide ? launch<64, 160, 1, 0>(a, s) : launch<64, 128, 1, 0>(a, s);
-  return wide ? launch<128, 160, 1, 0>(a, s) : launch<128, 128, 1, 0>(a, s);
-  }  // !FP8
+  return launch_gemm(a, p, s);
 }
 }  // namespace
 

@@ -1,5 +1,9 @@
-// Shared by gemm.hip (128x128 two-stage kernel) and gemm_ring.hip (8-wave multi-stage ring kernel).
+// Shared by gemm.hip (the staged GEMM / per-tap conv kernel) and conv_win.hip (the window-staged 3x3 conv kernel).
 #pragma once
+#include <atomic>
+#include <initializer_list>
+
+#include "gemm_plan.h"
 #include "seva_common.h"
 
 static __device__ uint4 g_zero_page[8];  // 128 B of zeros: source of padding taps (zero-initialised)
@@ -104,7 +108,6 @@ static __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
-// conv_win.hip: 3x3 / stride 1 / pad 1 conv with the tile's input window staged in LDS.  0 = launched, 1 = not applicable, < 0 = error
 // e4m3 x e4m3 -> fp32 on the block-scaled MFMA (gemm.hip: FP8); wscale = four packed E8M0 weight-scale bytes, OPSEL picks one
 typedef int v8i_t __attribute__((ext_vector_type(8)));
 template <int OPSEL>
@@ -127,6 +130,17 @@ static __device__ __forceinline__ f32x4 mfma_f8(int j, half8_t w_lo, half8_t w_h
 }
 
 
-int seva_conv_win_launch(const GemmArgs& a, hipStream_t s, bool fp8 = false);
-// seva_gemm_desc.upsample = 2 (four 2x2 phase convs on the source image; f16, bias + out_f32 only).  1 = declined: an error for the caller
-int seva_conv_win_phases_launch(const GemmArgs& a, hipStream_t s);
+// The dynamic-LDS attribute is per device: one bit per device ordinal in `devs`, which the caller keeps per kernel instantiation (a
+// second GPU in the same process would otherwise launch 72-80 KB kernels without it).
+inline void seva_max_dynamic_lds_once(std::atomic<uint64_t>& devs, int lds, std::initializer_list<const void*> kernels) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const uint64_t dev_bit = 1ull << (dev & 63);
+  if (devs.load(std::memory_order_relaxed) & dev_bit) return;
+  for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  devs.fetch_or(dev_bit, std::memory_order_relaxed);
+}
+
+// conv_win.hip: launches the winning candidate of a plan's window part (w.win >= 0) over its image ranges.  `a`: the conv as gemm.hip's
+// kernel_args() states it.  0 = launched, < 0 = error
+int seva_conv_win_launch(const GemmArgs& a, const seva_plan::WinPlan& w, hipStream_t s);

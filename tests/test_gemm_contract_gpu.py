@@ -10,8 +10,9 @@ B. Pitches and sentinels.  Every operand honours its row pitch (lda > K, ldr / l
    Integer data, exact against an fp64 reference.
 C. col_scale is a mode-0 feature: a convolution with col_scale_n > 0 is refused (the window kernel never applied it).
 
-Each case id names the kernel instantiation its shape steers to (csrc/gemm.hip gemm_entry / launch, csrc/conv_win.hip
-seva_conv_win_launch); a kernel trace of this file (rocprofv3 --kernel-trace --stats) lists them.
+Each case id names the kernel instantiation its shape steers to (csrc/gemm_plan.h: plan(), win_candidates(), the rows of
+SEVA_GEMM_KERNELS / SEVA_WIN_KERNELS); tests/test_gemm_plan_cpu.py asserts that the planner says the same, and a kernel trace of this
+file (rocprofv3 --kernel-trace --stats) lists them.
 """
 import ctypes as C
 
@@ -240,6 +241,35 @@ def test_conv_72x72_window_at_the_32bit_index_limit(dev, knobs):
             assert torch.equal(st[i * 81:(i + 1) * 81], s1), f"statistics of frame {i} (batch {nb})"
         del out, st, o16
     torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("groups", [False, True], ids=["n_lin3", "row_add_groups_n_lin2"])
+def test_conv_ranges_of_whole_images(dev, groups, knobs):
+    """1024 x 32 px x 64 -> 128 with statistics: hw = 2^15, so the multiply-high divisions of the linear window tiles are exact only while
+    n * hw^2 < 2^32 -- three images -- and a batch of 7 is launched as ranges of 3 + 3 + 1 whole images (csrc/gemm_plan.h: n_lin,
+    plan_tiling; csrc/conv_win.hip: launch_win).  With row_add groups of two images a range must end on a group boundary: 2 + 2 + 2 + 1.
+    Every image of the batch (input, row_add group, f32 output, statistics blocks moved by whole images) has the bits it has alone."""
+    from seva import ops
+    knobs(conv_win=-1, gemm_bm=-1, gemm_bn=-1)
+    n, ih, iw, cin, cout = 7, 1024, 32, 64, 128
+    hw, per = ih * iw, ih * iw // 64
+    x, w, _ = _conv_case(dev, n, ih, iw, cin, cout, seed=70)
+    bias = _randn((cout,), dev, 71, 0.3)
+    emb = _randn(((n + 1) // 2, cout), dev, 72, 0.3)
+
+    def run(xs, radd):
+        k = xs.shape[0]
+        out = torch.full((k, hw, cout), float("nan"), device=dev)
+        st = torch.full(ops.channel_stats_shape(k * hw, cout), float("nan"), device=dev)
+        ops.conv3x3(xs, w, bias=bias, row_add=radd, rows_per_group=2 * hw if groups else 0, out_f32=out, ch_stats=st)
+        return out, st
+
+    out, st = run(x, emb if groups else None)
+    for i in range(n):
+        o1, s1 = run(x[i:i + 1], emb[i // 2:i // 2 + 1] if groups else None)
+        assert torch.isfinite(o1).all()
+        assert torch.equal(out[i], o1[0]), f"image {i} of the batch differs from the image alone"
+        assert torch.equal(st[i * per:(i + 1) * per], s1), f"statistics of image {i}"
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
