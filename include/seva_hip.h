@@ -31,6 +31,10 @@ typedef void* seva_stream_t;
 #define SEVA_ERR_UNSUPPORTED (-3)
 
 const char* seva_last_error(void);
+/* Name of the instantiation-table row (csrc/gemm_plan.h: SEVA_GEMM_KERNELS / SEVA_WIN_KERNELS) of the last seva_gemm_f16 /
+ * seva_gemm_f16_split_out / seva_gemm_fp8 launch the calling thread planned; "" before any.  Thread-local, host only, a static
+ * string (never freed).  A call that failed before a row was chosen leaves the previous name.  (No ABI change: a new symbol only.) */
+const char* seva_last_plan(void);
 /* ABI version of this header; bumped on any signature change. */
 int seva_abi_version(void);
 /* Name of the code object's target, e.g. "gfx950". */

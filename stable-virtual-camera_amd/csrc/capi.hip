@@ -52,6 +52,8 @@ SevaKnobs knobs_from_env() {
 
 SevaKnobs g_seva_knobs = knobs_from_env();  // once, at library load
 
+thread_local const char* g_seva_last_plan = "";
+
 void seva_set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -88,6 +90,7 @@ SevaProfScope::~SevaProfScope() {
 extern "C" {
 
 const char* seva_last_error(void) { return g_err; }
+const char* seva_last_plan(void) { return g_seva_last_plan; }
 int seva_abi_version(void) { return 12; }
 const char* seva_target_arch(void) { return "gfx950"; }
 

@@ -578,8 +578,10 @@ int seva_conv_win_launch(const GemmArgs& a0, const seva_plan::WinPlan& w, hipStr
   a.ow = w.problem.ow;
   a.M = w.problem.M;
 #define SEVA_LAUNCH_ROW(NAME, BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH)                               \
-  if (seva_plan::same_kernel(c, seva_plan::WinCfg{BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH}))      \
-    return launch_win<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH>(a, w, s);
+  if (seva_plan::same_kernel(c, seva_plan::WinCfg{BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH})) {    \
+    g_seva_last_plan = NAME;                                                                                       \
+    return launch_win<BM, BN, NW, WCAP, DBW, STATS, UP, TW, FP8, O8, S2, PH>(a, w, s);                             \
+  }
   SEVA_WIN_KERNELS(SEVA_LAUNCH_ROW)
 #undef SEVA_LAUNCH_ROW
   seva_set_error("conv_win: internal error: no conv_win_kernel<%d, %d, %d, %d> instantiation with dbw %d stats %d up %d tw %d fp8 %d o8 %d s2 %d "

@@ -864,8 +864,10 @@ int launch_p(const GemmArgs& a, const seva_plan::Plan& p, hipStream_t s) {
 // the plan's gemm_kernel configuration -> its row of the table
 int launch_gemm(const GemmArgs& a, const seva_plan::Plan& p, hipStream_t s) {
 #define SEVA_LAUNCH_ROW(NAME, BM, BN, MODE, EPI, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16)                                          \
-  if (seva_plan::same_kernel(p.gemm, seva_plan::GemmCfg{BM, BN, MODE, EPI, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16, false}))    \
-    return launch_p<BM, BN, MODE, EPI, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16>(a, p, s);
+  if (seva_plan::same_kernel(p.gemm, seva_plan::GemmCfg{BM, BN, MODE, EPI, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16, false})) {  \
+    g_seva_last_plan = NAME;                                                                                                       \
+    return launch_p<BM, BN, MODE, EPI, PAIRED, ASTAT, FP8, SPLITK, NW, SPLIT16>(a, p, s);                                          \
+  }
   SEVA_GEMM_KERNELS(SEVA_LAUNCH_ROW)
 #undef SEVA_LAUNCH_ROW
   const seva_plan::GemmCfg& c = p.gemm;

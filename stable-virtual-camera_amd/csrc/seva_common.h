@@ -20,6 +20,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // host side ----------------------------------------------------------------------------------
 void seva_set_error(const char* fmt, ...);
 int seva_check_launch(const char* what);
+// table-row name (gemm_plan.h) of the last GEMM / conv launch this thread planned: seva_last_plan()
+extern thread_local const char* g_seva_last_plan;
 
 #define SEVA_REQUIRE(cond, ...)          \
   do {                                   \

@@ -92,6 +92,7 @@ class ImageDesc(C.Structure):
 # name -> (restype, argtypes); must list every symbol declared in include/seva_hip.h
 SYMBOLS = {
     "seva_last_error": (c_char_p, []),
+    "seva_last_plan": (c_char_p, []),
     "seva_abi_version": (c_int, []),
     "seva_target_arch": (c_char_p, []),
     "seva_gemm_f16": (c_int, [POINTER(GemmDesc), c_void_p]),

@@ -855,6 +855,11 @@ def set_knob(name: str, value: int) -> None:
     check(_lib().seva_set_knob(name.encode(), int(value)), "seva_set_knob")
 
 
+def last_plan() -> str:
+    """Table-row name (csrc/gemm_plan.h) of the last GEMM / conv launch this thread planned, "" before any (seva_last_plan)."""
+    return _lib().seva_last_plan().decode()
+
+
 def get_knob(name: str) -> int:
     v = C.c_int32()
     check(_lib().seva_get_knob(name.encode(), C.byref(v)), "seva_get_knob")

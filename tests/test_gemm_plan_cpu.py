@@ -11,15 +11,11 @@ and prints one plan line each.  Checked:
   bitwise equal on the device);
 * every benchmark knob gives the plan its comment describes.
 """
-import os
-import shutil
-import subprocess
-
 import pytest
 
 from conftest import PKG
+from kernel_cases import CXX, build_plan_dump, line
 
-CXX = shutil.which("g++")
 pytestmark = pytest.mark.skipif(CXX is None, reason="no g++")
 
 BATCHES = (1, 2, 3, 7, 42)
@@ -27,28 +23,8 @@ BATCHES = (1, 2, 3, 7, 42)
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    """plans(lines) -> list of dicts, one per descriptor line"""
-    exe = tmp_path_factory.mktemp("gemm_plan") / "gemm_plan_dump"
-    src = os.path.join(PKG, "csrc", "gemm_plan_dump.cpp")
-    # plain C++: no ROCm include path, no HIP
-    subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-Werror", "-o", str(exe), src], check=True)
-
-    def plans(lines):
-        r = subprocess.run([str(exe)], input="\n".join(lines) + "\n", capture_output=True, text=True, check=True)
-        out = [dict(t.split("=", 1) for t in ln.split("\t")) for ln in r.stdout.splitlines()]
-        assert len(out) == len(lines), (len(out), len(lines))
-        return out
-
-    def tables():
-        r = subprocess.run([str(exe)], input="tables\n", capture_output=True, text=True, check=True)
-        return [dict(t.split("=", 1) for t in ln.split("\t")) for ln in r.stdout.splitlines()]
-
-    plans.tables = tables
-    return plans
-
-
-def line(**kw):
-    return " ".join(f"{k}={v}" for k, v in kw.items())
+    """plans(lines) -> list of dicts, one per descriptor line (kernel_cases.build_plan_dump)"""
+    return build_plan_dump(tmp_path_factory.mktemp("gemm_plan"), PKG)
 
 
 def gemm(kind, M, N, K, **kw):
