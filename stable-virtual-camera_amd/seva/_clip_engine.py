@@ -20,28 +20,19 @@ import math
 import torch
 
 from . import ops
-from ._engine import _Arena, interleave_geglu
-from ._native import SevaNativeError, require_cuda
+from ._engine import _EngineBase, interleave_geglu
+from ._native import require_cuda
 
 F16, F32 = torch.float16, torch.float32
 
 
-class ClipEngine:
-    @staticmethod
-    def _resolve_device(weights) -> torch.device:
-        params = list(weights.parameters())
-        if not params or params[0].device.type != "cuda":
-            raise SevaNativeError("CLIPConditioner runs only on an AMD GPU (no CPU fallback): call .to('cuda')")
-        from . import _native
-
-        _native.load()
-        return params[0].device
+class ClipEngine(_EngineBase):
+    NEEDS_GPU = "CLIPConditioner runs only on an AMD GPU (no CPU fallback): call .to('cuda')"
 
     def __init__(self, weights, p, mean, std):
-        self.device = self._resolve_device(weights)
+        super().__init__(weights, group_norms=False)
         self.p = p
         self.mean, self.std = [float(v) for v in mean], [float(v) for v in std]
-        self.arena = _Arena(self.device)
         dev = self.device
         sd = {k: v.detach().to(dev) for k, v in weights.state_dict().items()}
         W = {}
@@ -69,9 +60,6 @@ class ClipEngine:
             W[o + ".fc1.w"], W[o + ".fc1.b"] = interleave_geglu(vg_w, vg_b)
             W[o + ".fc2.w"], W[o + ".fc2.b"] = sd[b + ".mlp.c_proj.weight"].to(F16).contiguous(), sd[b + ".mlp.c_proj.bias"].float().contiguous()
         self.W = W
-
-    def _buf(self, name, shape, dtype):
-        return self.arena.get(name, shape, dtype)
 
     def _patches(self, x):
         p = self.p

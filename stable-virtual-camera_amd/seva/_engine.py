@@ -107,7 +107,7 @@ def parse_split(spec, strict: bool = False) -> set:
 
 
 def dup_k(w: torch.Tensor) -> torch.Tensor:
-    """[N, K] -> [N, 2K] = [W | W]: the weights a split-precision [hi | lo] operand meets."""
+    """[N, K] -> [N, 2K] = [W | W]: the weights a split-precision [hi | lo] operand meets (a conv weight [cout, cin, 3, 3]: along cin)."""
     return torch.cat([w, w], 1).contiguous()
 
 
@@ -118,33 +118,90 @@ class _Arena:
         self.device = device
         self.bufs: dict = {}
 
-    def get(self, name: str, shape, dtype) -> torch.Tensor:
+    def get(self, name: str, shape, dtype, zero: bool = False) -> torch.Tensor:
+        """zero: zeroed once, when the buffer is made (pad columns that nothing writes again, flag areas)"""
         key = (name, tuple(int(s) for s in shape), dtype)
         t = self.bufs.get(key)
         if t is None:
-            t = torch.empty(key[1], dtype=dtype, device=self.device)
-            self.bufs[key] = t
+            t = self.bufs[key] = (torch.zeros if zero else torch.empty)(key[1], dtype=dtype, device=self.device)
         return t
 
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.bufs.values())
 
 
-class SevaEngine:
-    split: frozenset = frozenset()  # split-precision operand classes; set per instance in __init__ (an engine built without it: none)
+def env_flag(name: str, rule: str, default: bool = False) -> bool:
+    """Boolean switch `name`; unset: `default`.  rule "not0": on at anything but "0"; rule "is1": on at exactly "1"."""
+    v = os.environ.get(name)
+    return default if v is None else (v != "0" if rule == "not0" else v == "1")
+
+
+def env_int(name: str, default: int) -> int:
+    return int(os.environ.get(name, default))
+
+
+class _EngineBase:
+    """What the UNet, VAE and CLIP engines share: the device of the module they pack, the arena, and (engines with GroupNorms) the
+    hand-off of GroupNorm statistics from the producing kernel's epilogue."""
+
+    NEEDS_GPU = ""  # the error of a module that is not on a cuda device
 
     @staticmethod
-    def _resolve_device(model) -> torch.device:
-        params = [p for p in model.parameters()]
+    def _resolve_device(module):
+        """The module's cuda device (the library is loaded on the way), None if it is not on one.  (One argument: the tests' seam.)"""
+        params = list(module.parameters())
         if not params or params[0].device.type != "cuda":
-            raise SevaNativeError(
-                "Seva.forward runs only on an AMD GPU: move the module to a cuda device first "
-                "(there is no CPU fallback)."
-            )
-        from . import _native
-
+            return None
         _native.load()
         return params[0].device
+
+    def __init__(self, module, group_norms: bool = True):
+        self.device = self._resolve_device(module)
+        if self.device is None:
+            raise SevaNativeError(self.NEEDS_GPU)
+        self.arena = _Arena(self.device)
+        if group_norms:
+            # GroupNorm statistics from the producers' epilogues: 0 off (separate statistics pass everywhere, A/B runs),
+            # 1 where it pays (default), 2 wherever hw % 64 == 0, even on launches that would otherwise run 64-row tiles (tests)
+            self.gn_fused_stats = env_int("SEVA_GN_FUSED_STATS", 1)
+            self._stats: dict = {}
+
+    def _buf(self, name, shape, dtype, zero=False):
+        return self.arena.get(name, shape, dtype, zero)
+
+    # GroupNorm statistics emitted by the producing kernel's epilogue (seva_gemm_desc.ch_stats): a tensor that a GroupNorm will
+    # read gets a [rows / 64][2][c] side buffer filled by the conv / GEMM that writes it, and that GroupNorm then skips its
+    # statistics pass over the fp32 tensor.  Only where a 64-row block cannot straddle two samples (hw % 64 == 0: results stay
+    # bitwise independent of the batch composition) and where the launch keeps 128-row tiles anyway.
+    def _stats_buf(self, name, rows, hw, c):
+        if not self.gn_fused_stats or hw % ops.STATS_ROWS or c < 128 or c % 4:
+            return None
+        # small images keep the statistics pass: their launches run 64-row tiles, which have no statistics variant.  The rule
+        # looks at ONE sample (never at the batch size): a sample's result must not depend on what it is batched with
+        if self.gn_fused_stats < 2 and (hw // 128) * ((c + 159) // 160) < 16:
+            return None
+        return self._buf("st:" + name, ops.channel_stats_shape(rows, c), F32)
+
+    def _produced(self, out, st):
+        """Record (or forget) the statistics buffer that travels with fp32 tensor `out`."""
+        if st is None:
+            self._stats.pop(out.data_ptr(), None)
+        else:
+            self._stats[out.data_ptr()] = st
+
+    def _gn_stats(self, x1, x2=None):
+        """(stats1, stats2) for a GroupNorm over x1 (|| x2): the producers' buffers, or (None, None) unless every source has one."""
+        s1 = self._stats.get(x1.data_ptr())
+        s2 = None if x2 is None else self._stats.get(x2.data_ptr())
+        if s1 is None or (x2 is not None and s2 is None):
+            return None, None
+        return s1, s2
+
+
+class SevaEngine(_EngineBase):
+    NEEDS_GPU = "Seva.forward runs only on an AMD GPU: move the module to a cuda device first (there is no CPU fallback)."
+    split: frozenset = frozenset()  # split-precision operand classes; set per instance in __init__ (an engine built without it: none)
+    _resolve_device = staticmethod(_EngineBase._resolve_device)  # (an entry of its own: tests save and restore `__dict__["_resolve_device"]`)
 
     def __init__(self, model, precision: str | None = None, attention: str | None = None, ff: str | None = None, split=None):
         """precision "f16" (default; the parity mode, fp16 operands / fp32 accumulation) or "fp8" (BASELINE config 5:
@@ -152,50 +209,32 @@ class SevaEngine:
         convs whose reduction length is a multiple of 128 -- the C = 640 / 1280 levels; the C = 320 level (opt-in through
         zero-padding, SEVA_FP8_PAD=1: no gain, see below), attention, the small projections and the resampling convs stay f16).
         split (f16 only): the split-precision operand classes (`parse_split`); None leaves the choice to SEVA_SPLIT_PRECISION."""
-        import os as _os
-
-        self.device = self._resolve_device(model)
-        self.precision = precision or _os.environ.get("SEVA_PRECISION", "f16")
+        super().__init__(model)
+        self.precision = precision or os.environ.get("SEVA_PRECISION", "f16")
         if self.precision not in ("f16", "fp8"):
             raise ValueError(f"unknown precision {self.precision!r} (f16 | fp8)")
         self.fp8 = self.precision == "fp8"
         # fp8 mode's attention sub-option: "fp8" runs the long self-attention launches (lq >= ops.PV8_MIN_LQ, the ones
         # seva_attention_f16 gives attn16_kernel) with P and V in e4m3 (seva_attention_pv8).  Not given: SEVA_FP8_ATTENTION=0|1.
-        if attention is None:
-            attention = "fp8" if self.fp8 and _os.environ.get("SEVA_FP8_ATTENTION", "0") == "1" else "f16"
-        if attention not in ("f16", "fp8"):
-            raise ValueError(f"unknown attention {attention!r} (f16 | fp8)")
-        if attention == "fp8" and not self.fp8:
-            raise ValueError('attention="fp8" needs precision "fp8" (the f16 parity mode stays pure)')
-        self.attention = attention
-        self.pv8 = attention == "fp8"
+        self.attention = self._fp8_option("attention", attention, "SEVA_FP8_ATTENTION")
+        self.pv8 = self.attention == "fp8"
         # fp8 mode only: also take reductions that need zero-padding to a multiple of 128 (C = 320 -> 384, 960 -> 1024).  Off by
         # default -- measured (profiles/r02_bench_T21_fp8_pad320.json): the C = 320 level then leaves the fused f16 feed-forward
         # for the two-kernel fp8 path, the step stays at 86.1 ms and the error doubles (rel-L2 2.9e-2 -> 5.2e-2).
-        self.fp8_pad = _os.environ.get("SEVA_FP8_PAD", "0") == "1"
-        self.ff_fused = _os.environ.get("SEVA_FF_FUSED", "1") != "0"  # 0: two-kernel GEGLU + FF2 everywhere (A/B runs)
+        self.fp8_pad = env_flag("SEVA_FP8_PAD", "is1")
+        self.ff_fused = env_flag("SEVA_FF_FUSED", "not0", True)  # 0: two-kernel GEGLU + FF2 everywhere (A/B runs)
         # fp8 mode's feed-forward sub-option: "fp8" runs the feed-forwards that take the fused f16 kernel in fp8 mode (reduction
         # not a multiple of 128: the C = 320 level, the tiny net's C = 64) on its e4m3 sibling (seva_ff_fused_fp8); with
         # SEVA_FP8_PAD=1 it takes precedence over the padded two-kernel chain there.  Not given: SEVA_FP8_FF=0|1.
-        if ff is None:
-            ff = "fp8" if self.fp8 and _os.environ.get("SEVA_FP8_FF", "0") == "1" else "f16"
-        if ff not in ("f16", "fp8"):
-            raise ValueError(f"unknown ff {ff!r} (f16 | fp8)")
-        if ff == "fp8" and not self.fp8:
-            raise ValueError('ff="fp8" needs precision "fp8" (the f16 parity mode stays pure)')
-        self.ff = ff
-        self.ff8 = ff == "fp8"
-        # GroupNorm statistics from the producers' epilogues: 0 off (separate statistics pass everywhere, A/B runs),
-        # 1 where it pays (default), 2 wherever hw % 64 == 0, even on launches that would otherwise run 64-row tiles (tests)
-        self.gn_fused_stats = int(_os.environ.get("SEVA_GN_FUSED_STATS", "1"))
-        self._stats: dict = {}
-        self.conv_splitk = _os.environ.get("SEVA_CONV_SPLITK", "1") != "0"  # 0: 64-row tiles at the 9x9 level (A/B runs)
-        self.attn_split = _os.environ.get("SEVA_ATTN_SPLIT_KV", "1") != "0"  # 0: joint attention never K/V-split (A/B runs)
-        self.attn_split_max = max(2, min(4, int(_os.environ.get("SEVA_ATTN_SPLIT", "2"))))  # workspace slots (knob attn_split: 2..4)
+        self.ff = self._fp8_option("ff", ff, "SEVA_FP8_FF")
+        self.ff8 = self.ff == "fp8"
+        self.conv_splitk = env_flag("SEVA_CONV_SPLITK", "not0", True)  # 0: 64-row tiles at the 9x9 level (A/B runs)
+        self.attn_split = env_flag("SEVA_ATTN_SPLIT_KV", "not0", True)  # 0: joint attention never K/V-split (A/B runs)
+        self.attn_split_max = max(2, min(4, env_int("SEVA_ATTN_SPLIT", 2)))  # workspace slots (knob attn_split: 2..4)
         # 1: the ResBlock's 1x1 skip conv as extra K-tiles of its second 3x3 conv (one accumulation, no fp32 round trip of the skip
         # result, a launch fewer).  OFF by default -- measured neutral (profiles/r03_ab_fold_skip.log: 96.9 vs 96.5 ms per step over two
         # interleaved rounds, GEMM class -2.0 ms, conv class +1.2 ms).  Not at levels whose convs run split-K (images <= 128 px).
-        self.fold_skip = _os.environ.get("SEVA_FOLD_SKIP", "0") != "0" and not self.fp8
+        self.fold_skip = env_flag("SEVA_FOLD_SKIP", "not0") and not self.fp8
         # Split-precision operands (hi + lo f16 pairs against duplicated weights) for the three operand roundings that dominate the
         # network's error budget (tests/test_f16_floor_cpu.py: 1x1 skip convs 4.9e-4, stem 2.4e-4, head 2.3e-4 of 8.1e-4):
         # comma list of "stem", "head", "skip" / "skip_deep"; "none" = every operand plain fp16 (the round-2 numerics).
@@ -210,22 +249,29 @@ class SevaEngine:
                 raise ValueError('split precision needs precision "f16" (the fp8 mode has no split operands)')
             self.split = parse_split(split, strict=True)
         else:  # (fp8 mode: the environment variable is ignored)
-            self.split = parse_split(_os.environ.get("SEVA_SPLIT_PRECISION", SPLIT_DEFAULT)) if not self.fp8 else set()
+            self.split = parse_split(os.environ.get("SEVA_SPLIT_PRECISION", SPLIT_DEFAULT)) if not self.fp8 else set()
         self.p = model.params
         self.layout: Layout = model._layout
-        self.arena = _Arena(self.device)
         self._pack(model)
         # hipGraph replay of the whole network call (SEVA_HIPGRAPH=0 disables): one captured graph
         # per input signature, fed through static input buffers
-        import os
-
-        self.use_graph = os.environ.get("SEVA_HIPGRAPH", "1") != "0"
+        self.use_graph = env_flag("SEVA_HIPGRAPH", "not0", True)
         self._graphs: dict = {}
         # frame-sliced execution of the token-wise chains at the largest level (see _slice_rows); 0 frames = off (default:
         # measured end-to-end it does not pay, see _slice_rows)
-        self.slice_frames = int(os.environ.get("SEVA_SLICE_FRAMES", "0"))
+        self.slice_frames = env_int("SEVA_SLICE_FRAMES", 0)
         self.slice_min_bytes = int(float(os.environ.get("SEVA_SLICE_MIN_MB", "96")) * (1 << 20))
-        self.slice_attn = os.environ.get("SEVA_SLICE_ATTN", "0") == "1"  # also slice LN -> QKV -> attention -> out-proj
+        self.slice_attn = env_flag("SEVA_SLICE_ATTN", "is1")  # also slice LN -> QKV -> attention -> out-proj
+
+    def _fp8_option(self, name: str, value, switch: str) -> str:
+        """The `attention=` / `ff=` sub-option of the fp8 mode, "f16" | "fp8"; None leaves it to the environment `switch` (fp8 mode only)."""
+        if value is None:
+            value = "fp8" if self.fp8 and env_flag(switch, "is1") else "f16"
+        if value not in ("f16", "fp8"):
+            raise ValueError(f"unknown {name} {value!r} (f16 | fp8)")
+        if value == "fp8" and not self.fp8:
+            raise ValueError(f'{name}="fp8" needs precision "fp8" (the f16 parity mode stays pure)')
+        return value
 
     def _ff_fused_fp8(self, c: int) -> bool:
         """Does a feed-forward of width c run on seva_ff_fused_fp8?  Exactly those that reach the fused f16 kernel in fp8 mode
@@ -278,37 +324,40 @@ class SevaEngine:
         sp = self.split
 
         def pack_attn_self(pfx):
-            W[pfx + ".qkv"] = torch.cat(
-                [f16(pfx + ".to_q.weight"), f16(pfx + ".to_k.weight"), f16(pfx + ".to_v.weight")], 0
-            ).contiguous()
-            if "qkv" in sp:  # the LayerNorm output arrives as [hi | lo]
-                W[pfx + ".qkv"] = dup_k(W[pfx + ".qkv"])
-            q8(pfx + ".qkv", torch.cat([f32(pfx + ".to_q.weight"), f32(pfx + ".to_k.weight"), f32(pfx + ".to_v.weight")], 0))
+            def qkv(conv):
+                return torch.cat([conv(pfx + ".to_q.weight"), conv(pfx + ".to_k.weight"), conv(pfx + ".to_v.weight")], 0)
+
+            W[pfx + ".qkv"] = dup_k(qkv(f16)) if "qkv" in sp else qkv(f16)  # ("qkv": the LayerNorm output arrives as [hi | lo])
+            if self.fp8:
+                q8(pfx + ".qkv", qkv(f32))
             W[pfx + ".out.w"], W[pfx + ".out.b"] = f16(pfx + ".to_out.0.weight"), f32(pfx + ".to_out.0.bias")
 
         def pack_attn_cross(pfx):
             nonlocal ctx_total
-            wv, wo = f32(pfx + ".to_v.weight"), f32(pfx + ".to_out.0.weight")
+            wv, wo, bo = f32(pfx + ".to_v.weight"), f32(pfx + ".to_out.0.weight"), f32(pfx + ".to_out.0.bias")
             ctx_w.append((wo.double() @ wv.double()).to(F16))  # folded W_out @ W_v  [C, ctx]
-            ctx_b.append(f32(pfx + ".to_out.0.bias"))
+            ctx_b.append(bo)
             self.ctx_off[pfx] = ctx_total
             ctx_total += wo.shape[0]
             # general path (context length > 1)
             W[pfx + ".q"] = f16(pfx + ".to_q.weight")
             W[pfx + ".kv"] = torch.cat([f16(pfx + ".to_k.weight"), f16(pfx + ".to_v.weight")], 0).contiguous()
-            W[pfx + ".out.w"], W[pfx + ".out.b"] = f16(pfx + ".to_out.0.weight"), f32(pfx + ".to_out.0.bias")
+            W[pfx + ".out.w"], W[pfx + ".out.b"] = f16(pfx + ".to_out.0.weight"), bo
 
         def pack_ff(pfx):
-            wi, bi = interleave_geglu(f16(pfx + ".net.0.proj.weight"), f32(pfx + ".net.0.proj.bias"))
+            b1 = f32(pfx + ".net.0.proj.bias")
+            wi, bi = interleave_geglu(f16(pfx + ".net.0.proj.weight"), b1)
             W[pfx + ".w1"], W[pfx + ".b1"] = wi, bi
             W[pfx + ".w2"], W[pfx + ".b2"] = f16(pfx + ".net.2.weight"), f32(pfx + ".net.2.bias")
             if "ff" in sp:  # LayerNorm output and GEGLU hidden tensor arrive as [hi | lo]
                 W[pfx + ".w1"], W[pfx + ".w2"] = dup_k(W[pfx + ".w1"]), dup_k(W[pfx + ".w2"])
+            if not self.fp8:
+                return
+            wi32 = interleave_geglu(f32(pfx + ".net.0.proj.weight"), b1)[0]
             if self._ff_fused_fp8(wi.shape[1]):  # e4m3 copies for seva_ff_fused_fp8 (W1 zero-padded to KP, W2 column-permuted)
-                W[pfx + ".w1f8"], W[pfx + ".w1f8e"], W[pfx + ".w2f8"], W[pfx + ".w2f8e"] = ops.pack_ff_fp8(
-                    interleave_geglu(f32(pfx + ".net.0.proj.weight"), f32(pfx + ".net.0.proj.bias"))[0], f32(pfx + ".net.2.weight"))
-            elif self.fp8:  # both or neither: the hidden activations travel as e4m3
-                q8(pfx + ".w1", interleave_geglu(f32(pfx + ".net.0.proj.weight"), f32(pfx + ".net.0.proj.bias"))[0])
+                W[pfx + ".w1f8"], W[pfx + ".w1f8e"], W[pfx + ".w2f8"], W[pfx + ".w2f8e"] = ops.pack_ff_fp8(wi32, f32(pfx + ".net.2.weight"))
+            else:  # both or neither: the hidden activations travel as e4m3
+                q8(pfx + ".w1", wi32)
                 if pfx + ".w18" in W:
                     q8(pfx + ".w2", f32(pfx + ".net.2.weight"))
 
@@ -320,7 +369,7 @@ class SevaEngine:
             if spec.kind == "conv":
                 wc = f32(pfx + ".weight")
                 if "stem" in self.split and 2 * spec.cin <= CIN_PAD:  # [w | w]: the input arrives as [hi | lo] channels
-                    wc = torch.cat([wc, wc], 1)
+                    wc = dup_k(wc)
                 W[pfx + ".w"] = pack_conv3x3(wc, CIN_PAD * ((wc.shape[1] + CIN_PAD - 1) // CIN_PAD))
                 W[pfx + ".b"] = f32(pfx + ".bias")
             elif spec.kind == "res":
@@ -328,17 +377,16 @@ class SevaEngine:
                 pack_ln(pfx + ".in_layers.0")
                 pack_ln(pfx + ".out_layers.0")
                 wc1, wc2 = f32(pfx + ".in_layers.2.weight"), f32(pfx + ".out_layers.3.weight")
-                if "conv" in sp:  # [w | w] per tap: both GroupNorms write [hi | lo] channels
-                    wc1, wc2 = torch.cat([wc1, wc1], 1), torch.cat([wc2, wc2], 1)
-                W[pfx + ".conv1.w"] = pack_conv3x3(wc1)
+                # ("conv": [w | w] per tap, both GroupNorms write [hi | lo] channels)
+                W[pfx + ".conv1.w"] = pack_conv3x3(dup_k(wc1) if "conv" in sp else wc1)
                 W[pfx + ".conv1.b"] = f32(pfx + ".in_layers.2.bias")
-                W[pfx + ".conv2.w"] = pack_conv3x3(wc2)
+                W[pfx + ".conv2.w"] = pack_conv3x3(dup_k(wc2) if "conv" in sp else wc2)
                 W[pfx + ".conv2.b"] = f32(pfx + ".out_layers.3.bias")
                 if self.fp8:  # K = 9*cin_pad ordered (ky, kx, ci): a 128-deep K-tile must not straddle taps -> channels padded
-                    for tag, key, ch in (("conv1", "in_layers.2", spec.cin), ("conv2", "out_layers.3", spec.cout)):
+                    for tag, wc, ch in (("conv1", wc1, spec.cin), ("conv2", wc2, spec.cout)):
                         cp = _pad128(ch)
                         if cp == ch or (self.fp8_pad and cp * 4 <= ch * 5):
-                            q8(f"{pfx}.{tag}.w", pack_conv3x3(f32(f"{pfx}.{key}.weight"), cp).float())
+                            q8(f"{pfx}.{tag}.w", pack_conv3x3(wc, cp).float())
                 W[pfx + ".dense.w"] = f32(pfx + ".dense_emb_layers.0.weight").reshape(2 * spec.cin, -1).contiguous()
                 W[pfx + ".dense.b"] = f32(pfx + ".dense_emb_layers.0.bias")
                 emb_w.append(f16(pfx + ".emb_layers.1.weight"))
@@ -348,7 +396,7 @@ class SevaEngine:
                 if spec.cin != spec.cout:
                     ws = f16(pfx + ".skip_connection.weight").reshape(spec.cout, spec.cin)
                     # split precision: the raw input arrives as [hi | lo] (K = 2 cin), the weights are duplicated
-                    W[pfx + ".skip.w"] = (torch.cat([ws, ws], 1) if self._split_skip(spec.cout) else ws).contiguous()
+                    W[pfx + ".skip.w"] = dup_k(ws) if self._split_skip(spec.cout) else ws.contiguous()
                     W[pfx + ".skip.b"] = f32(pfx + ".skip_connection.bias")
                     if self.fold_skip:
                         # the skip conv folded into conv2 (seva_gemm_desc.a2): weights [w_conv2 | w_skip] per output row, biases summed
@@ -378,16 +426,16 @@ class SevaEngine:
                         pack_ln(f"{m}.{n}")
             elif spec.kind == "down":
                 wr = f32(pfx + ".op.weight")
-                W[pfx + ".w"], W[pfx + ".b"] = pack_conv3x3(torch.cat([wr, wr], 1) if "resample" in sp else wr), f32(pfx + ".op.bias")
+                W[pfx + ".w"], W[pfx + ".b"] = pack_conv3x3(dup_k(wr) if "resample" in sp else wr), f32(pfx + ".op.bias")
             elif spec.kind == "up":
                 wr = f32(pfx + ".conv.weight")
                 if "resample" in sp:  # duplicated along cin, also under the phase operator's taps
-                    wr = torch.cat([wr, wr], 1)
+                    wr = dup_k(wr)
                 W[pfx + ".w"], W[pfx + ".b"] = pack_conv3x3(wr), f32(pfx + ".conv.bias")
                 W[pfx + ".w4"] = combine_up_phases(wr)  # ops.conv3x3_up_phases (_resample)
         pack_ln("out.0")
         wh = f32("out.2.weight")
-        W["out.2.w"] = pack_conv3x3(torch.cat([wh, wh], 1) if "head" in self.split else wh)  # head input [hi | lo] per tap
+        W["out.2.w"] = pack_conv3x3(dup_k(wh) if "head" in self.split else wh)  # head input [hi | lo] per tap
         W["out.2.b"] = f32("out.2.bias")
         W["emb_all.w"], W["emb_all.b"] = torch.cat(emb_w, 0).contiguous(), torch.cat(emb_b, 0).contiguous()
         W["ctx_all.w"], W["ctx_all.b"] = torch.cat(ctx_w, 0).contiguous(), torch.cat(ctx_b, 0).contiguous()
@@ -395,27 +443,6 @@ class SevaEngine:
         self.W = W
 
     # ------------------------------------------------------------------ helpers
-    def _buf(self, name, shape, dtype, zero=False):
-        key = (name, tuple(int(v) for v in shape), dtype)
-        fresh = zero and key not in self.arena.bufs
-        t = self.arena.get(name, shape, dtype)
-        if fresh:
-            t.zero_()
-        return t
-
-    # GroupNorm statistics emitted by the producing kernel's epilogue (seva_gemm_desc.ch_stats): a tensor that a GroupNorm will
-    # read gets a [rows / 64][2][c] side buffer filled by the conv / GEMM that writes it, and that GroupNorm then skips its
-    # statistics pass over the fp32 tensor.  Only where a 64-row block cannot straddle two samples (hw % 64 == 0: results stay
-    # bitwise independent of the batch composition) and where the launch keeps 128-row tiles anyway.
-    def _stats_buf(self, name, rows, hw, c):
-        if not self.gn_fused_stats or hw % ops.STATS_ROWS or c < 128 or c % 4:
-            return None
-        # small images keep the statistics pass: their launches run 64-row tiles, which have no statistics variant.  The rule
-        # looks at ONE sample (never at the batch size): a sample's result must not depend on what it is batched with
-        if self.gn_fused_stats < 2 and (hw // 128) * ((c + 159) // 160) < 16:
-            return None
-        return self._buf("st:" + name, ops.channel_stats_shape(rows, c), F32)
-
     def _sk(self, rows=0, hw=0, c=0):
         """Workspace of seva_gemm_desc.splitk_ws (one per engine; its launches are serialised on one stream): lets the library run
         the convs of small images (the 9x9 level) as split-K.  16384 flags + one 128 x 160 fp32 slot per output tile (>= 512)."""
@@ -427,20 +454,6 @@ class SevaEngine:
         tiles = max(512, ((rows + 127) // 128) * ((c + 127) // 128)) if hw and hw <= 128 else 512
         tiles = min(tiles, 16382)
         return self._buf("sk_ws", (16384 + tiles * 128 * 160,), F32, zero=True)
-
-    def _produced(self, out, st):
-        """Record (or forget) the statistics buffer that travels with fp32 tensor `out`."""
-        if st is None:
-            self._stats.pop(out.data_ptr(), None)
-        else:
-            self._stats[out.data_ptr()] = st
-
-    def _gn_stats(self, x1, x2):
-        s1 = self._stats.get(x1.data_ptr())
-        s2 = None if x2 is None else self._stats.get(x2.data_ptr())
-        if s1 is None or (x2 is not None and s2 is None):
-            return None, None
-        return s1, s2
 
     def _ln(self, x, pfx, rows, c, fp8=False, split=False):
         if split:  # [hi | lo] for duplicated weights
@@ -496,9 +509,9 @@ class SevaEngine:
             a = self._ln(x32, ln_pfx, rows, c, split=sp_ff)
             hidden = self._buf("ffhs" if sp_ff else "ffh", (rows, (8 if sp_ff else 4) * c), F16)
             (ops.gemm_split_out if sp_ff else ops.gemm)(a, W[ff_pfx + ".w1"], bias=W[ff_pfx + ".b1"], out_f16=hidden, geglu=True,
-                                                      **({"alg_k": c} if sp_ff else {}))
+                                                      alg_k=c if sp_ff else 0)
             (ops.gemm_split_out if sp_o16 else ops.gemm)(hidden, W[ff_pfx + ".w2"], bias=W[ff_pfx + ".b2"], residual=residual,
-                                                       out_f32=out_f32, out_f16=out_f16, **({"alg_k": 4 * c} if sp_ff else {}))
+                                                       out_f32=out_f32, out_f16=out_f16, alg_k=4 * c if sp_ff else 0)
             return
         if self.ff_fused and c in ops.FF_FUSED_CHANNELS:
             # narrow levels (ds1: C = 320): GEGLU -> FF2 in ONE kernel, the 4C-wide hidden tensor never exists in HBM
@@ -537,7 +550,7 @@ class SevaEngine:
         s1, s2 = self._gn_stats(x1, x2)
         ops.groupnorm(x1, x2, W[pfx + ".in_layers.0.g"], W[pfx + ".in_layers.0.b"], a16, self.gn_ws,
                       eps=1e-5, silu=True, dense=dense, dense_w=W[pfx + ".dense.w"], dense_b=W[pfx + ".dense.b"],
-                      raw_f16=xs16, out_f8=a8, stats1=s1, stats2=s2, split_raw=sp_skip, **({"split_out": True} if sp_conv else {}))
+                      raw_f16=xs16, out_f8=a8, stats1=s1, stats2=s2, split_raw=sp_skip, split_out=sp_conv)
         hmid = self._buf("res_mid", (n, hw, cout), F32)
         st_mid = self._stats_buf("res_mid", n * hw, hw, cout)
         off = self.emb_off[pfx]
@@ -547,11 +560,11 @@ class SevaEngine:
         else:
             ops.conv3x3(a16.view(n, h, w, k1), W[pfx + ".conv1.w"], bias=W[pfx + ".conv1.b"],
                         row_add=emb_all[:, off:], rows_per_group=hw, ld_row_add=self.emb_total, out_f32=hmid, ch_stats=st_mid,
-                        splitk_ws=self._sk(n * hw, hw, cout), **({"alg_k": 9 * cin} if sp_conv else {}))
+                        splitk_ws=self._sk(n * hw, hw, cout), alg_k=9 * cin if sp_conv else 0)
         b16 = None if f8_2 else self._buf("gn16", (n, hw, k2), F16)
         b8 = self._buf("gn8", (n, hw, cout8), U8, zero=True) if f8_2 else None
         ops.groupnorm(hmid, None, W[pfx + ".out_layers.0.g"], W[pfx + ".out_layers.0.b"], b16, self.gn_ws,
-                      eps=1e-5, silu=True, out_f8=b8, stats1=st_mid, **({"split_out": True} if sp_conv else {}))
+                      eps=1e-5, silu=True, out_f8=b8, stats1=st_mid, split_out=sp_conv)
         fold = cin != cout and self.fold_skip and not f8_2 and (hw > 128 or not self.conv_splitk)
         if fold:
             res = None
@@ -572,7 +585,7 @@ class SevaEngine:
         else:
             ops.conv3x3(b16.view(n, h, w, k2), W[pfx + ".conv2.w"], bias=W[pfx + ".conv2.b"],
                         residual=res, out_f32=out, ch_stats=st_out, splitk_ws=self._sk(n * hw, hw, cout),
-                        **({"alg_k": 9 * cout} if sp_conv else {}))
+                        alg_k=9 * cout if sp_conv else 0)
         self._produced(out, st_out)
         return out
 
@@ -611,7 +624,7 @@ class SevaEngine:
             ops.gemm(a8, W[at_pfx + ".qkv8"], w_exp=W[at_pfx + ".qkv8e"], out_f16=qkv, col_scale=QK_SCALE_LOG2E, col_scale_n=c)
         else:
             a = self._ln(x32, ln_pfx, rows, c, split=sp_qkv)
-            ops.gemm(a, W[at_pfx + ".qkv"], out_f16=qkv, col_scale=QK_SCALE_LOG2E, col_scale_n=c, **({"alg_k": c} if sp_qkv else {}))
+            ops.gemm(a, W[at_pfx + ".qkv"], out_f16=qkv, col_scale=QK_SCALE_LOG2E, col_scale_n=c, alg_k=c if sp_qkv else 0)
         att = self._buf("att", (rows, c), F16)
         q, k, v = qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:]
         if regime == "frame":  # batch = frame, tokens = pixels
@@ -666,9 +679,9 @@ class SevaEngine:
         cs = 2 * c if sp_in else c
         g16 = self._buf("gn16", (n, hw, cs), F16)
         ops.groupnorm(x, None, W[pfx + ".norm.g"], W[pfx + ".norm.b"], g16, self.gn_ws, eps=1e-6, silu=False,
-                      stats1=self._gn_stats(x, None)[0], **({"split_out": True} if sp_in else {}))
+                      stats1=self._gn_stats(x)[0], split_out=sp_in)
         cur = self._buf("t_h", (rows, c), F32)
-        ops.gemm(g16.view(rows, cs), W[pfx + ".proj_in.w"], bias=W[pfx + ".proj_in.b"], out_f32=cur, **({"alg_k": c} if sp_in else {}))
+        ops.gemm(g16.view(rows, cs), W[pfx + ".proj_in.w"], bias=W[pfx + ".proj_in.b"], out_f32=cur, alg_k=c if sp_in else 0)
         collapse = lc == 1
         ldra_frame, ldra_scene = self.ctx_total, T * self.ctx_total
         last16 = None
@@ -724,7 +737,7 @@ class SevaEngine:
         out = self._buf("out:" + pfx, (n, hw, c), F32)
         st_out = self._stats_buf("out:" + pfx, rows, hw, c)
         ops.gemm(last16, W[pfx + ".proj_out.w"], bias=W[pfx + ".proj_out.b"], residual=x.view(rows, c),
-                 out_f32=out.view(rows, c), ch_stats=st_out, **({"alg_k": c} if sp_out else {}))
+                 out_f32=out.view(rows, c), ch_stats=st_out, alg_k=c if sp_out else 0)
         self._produced(out, st_out)
         return out
 
@@ -734,18 +747,18 @@ class SevaEngine:
         sp_rs = "resample" in self.split
         x16 = self._buf("rs16", (n, h, w, 2 * c if sp_rs else c), F16)
         (ops.cast_concat_f16_split if sp_rs else ops.cast_concat_f16)(x, None, x16)
-        ak = {"alg_k": 9 * c} if sp_rs else {}
+        alg_k = 9 * c if sp_rs else 0
         if spec.kind == "down":
             oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
             out = self._buf("out:" + spec.prefix, (n, oh * ow, c), F32)
             st_out = self._stats_buf("out:" + spec.prefix, n * oh * ow, oh * ow, c)
             ops.conv3x3(x16, self.W[spec.prefix + ".w"], stride=2, bias=self.W[spec.prefix + ".b"], out_f32=out, ch_stats=st_out,
-                        splitk_ws=self._sk(n * oh * ow, oh * ow, c), **ak)
+                        splitk_ws=self._sk(n * oh * ow, oh * ow, c), alg_k=alg_k)
         else:
             oh, ow = 2 * h, 2 * w
             out = self._buf("out:" + spec.prefix, (n, oh * ow, c), F32)
             phases = getattr(ops, "conv3x3_up_phases", None)
-            if phases is not None and c % 160 == 0 and os.environ.get("SEVA_UPSAMPLE_PHASES", "1") != "0":
+            if phases is not None and c % 160 == 0 and env_flag("SEVA_UPSAMPLE_PHASES", "not0", True):  # (read at every call)
                 # four 2x2 phase convs on the source image: 4/9 of the FLOPs.  The path emits no statistics (a 64-row block of one
                 # phase is not image-aligned), so the consuming GroupNorm runs its own pass over this tensor
                 st_out = None
@@ -753,7 +766,7 @@ class SevaEngine:
             else:
                 st_out = self._stats_buf("out:" + spec.prefix, n * oh * ow, oh * ow, c)
                 ops.conv3x3(x16, self.W[spec.prefix + ".w"], upsample=True, bias=self.W[spec.prefix + ".b"], out_f32=out,
-                            ch_stats=st_out, **ak)
+                            ch_stats=st_out, alg_k=alg_k)
         self._produced(out, st_out)
         return out, oh, ow
 
@@ -917,7 +930,7 @@ class SevaEngine:
         cf2 = (2 if sp_head else 1) * cfin
         g16 = self._buf("gn16", (n, ch * cw, cf2), F16)
         ops.groupnorm(cur, None, W["out.0.g"], W["out.0.b"], g16, self.gn_ws, eps=1e-5, silu=True,
-                      stats1=self._gn_stats(cur, None)[0], split_out=sp_head)
+                      stats1=self._gn_stats(cur)[0], split_out=sp_head)
         o_nhwc = self._buf("head", (n, ch * cw, p.out_channels), F32)
         ops.conv3x3(g16.view(n, ch, cw, cf2), W["out.2.w"], bias=W["out.2.b"], out_f32=o_nhwc, alg_k=9 * cfin)
         if out is None:

@@ -20,8 +20,8 @@ import os
 import torch
 
 from . import ops
-from ._engine import CIN_PAD, _Arena, combine_up_phases, pack_conv3x3
-from ._native import SevaNativeError, require_cuda
+from ._engine import CIN_PAD, _EngineBase, combine_up_phases, env_flag, pack_conv3x3
+from ._native import require_cuda
 
 F16, F32 = torch.float16, torch.float32
 U8 = torch.uint8  # e4m3 bytes (ops.py)
@@ -53,7 +53,7 @@ def check_vae_upsample(upsample: str) -> str:
 
 def vae_upsample_from_env() -> str:
     """SEVA_VAE_UPSAMPLE_PHASES=1: "phases" (unset or anything else: "taps"); used only where `AutoEncoder.set_upsample` was not called."""
-    return "phases" if os.environ.get("SEVA_VAE_UPSAMPLE_PHASES", "0") == "1" else "taps"
+    return "phases" if env_flag("SEVA_VAE_UPSAMPLE_PHASES", "is1") else "taps"
 
 
 def up_phases128_applies(ih: int, iw: int) -> bool:
@@ -74,12 +74,12 @@ def up_phases128_applies(ih: int, iw: int) -> bool:
 
 def fp8_downsample_from_env() -> bool:
     """SEVA_VAE_FP8_DOWNSAMPLE=1: the fp8 encode also runs the three downsample convs in e4m3 (off by default, see fp8_encoder_convs)."""
-    return os.environ.get("SEVA_VAE_FP8_DOWNSAMPLE", "0") == "1"
+    return env_flag("SEVA_VAE_FP8_DOWNSAMPLE", "is1")
 
 
 def fp8_upsample_from_env() -> bool:
     """SEVA_VAE_FP8_UPSAMPLE=1: the fp8 decode also runs the three upsample convs in e4m3 (off by default, see fp8_decoder_convs)."""
-    return os.environ.get("SEVA_VAE_FP8_UPSAMPLE", "0") == "1"
+    return env_flag("SEVA_VAE_FP8_UPSAMPLE", "is1")
 
 
 def fp8_decoder_convs(block_out, upsample: bool = False) -> list[str]:
@@ -165,31 +165,18 @@ def pack_fp8_convs(sd: dict, block_out, upsample: bool = False, names=None) -> d
     return W8
 
 
-class _VaeEngineBase:
+class _VaeEngineBase(_EngineBase):
+    NEEDS_GPU = "AutoEncoder runs only on an AMD GPU (no CPU fallback): call .to('cuda')"
     PREFIXES: tuple = ()       # state_dict key prefixes this half owns
     CONV_IN = CONV_OUT = ""    # first conv (input channels padded to 64) / last conv (handled by the subclass)
-
-    @staticmethod
-    def _resolve_device(weights) -> torch.device:
-        params = list(weights.parameters())
-        if not params or params[0].device.type != "cuda":
-            raise SevaNativeError("AutoEncoder runs only on an AMD GPU (no CPU fallback): call .to('cuda')")
-        from . import _native
-
-        _native.load()
-        return params[0].device
 
     _w8: dict = {}  # e4m3 conv weights of the running decode / encode (fp8 precision), else empty
 
     def __init__(self, weights):
-        self.device = self._resolve_device(weights)
+        super().__init__(weights)
         self.block_out = weights.block_out
         self.out_channels = weights.out_channels
         self.latent = weights.latent_channels
-        self.arena = _Arena(self.device)
-        import os as _os
-        self.gn_fused_stats = int(_os.environ.get("SEVA_GN_FUSED_STATS", "1"))  # seva/_engine.py: same switch
-        self._stats: dict = {}
         sd = {k: v.detach().to(self.device) for k, v in weights.state_dict().items() if k.startswith(self.PREFIXES)}
         W = {}
 
@@ -227,7 +214,7 @@ class _VaeEngineBase:
                 conv3(p)
         # channel-changing resnets: the 1x1 shortcut conv rides in the K loop of the second 3x3 conv (seva_gemm_desc.a2): one
         # accumulation, and the shortcut result (fp32, up to 576 x 576 x 128 per frame) is neither written nor read back
-        self.fold_shortcut = _os.environ.get("SEVA_VAE_FOLD_SHORTCUT", "1") != "0"
+        self.fold_shortcut = env_flag("SEVA_VAE_FOLD_SHORTCUT", "not0", True)
         for k in list(W):
             if k.endswith(".conv_shortcut.w") and W[k].shape[1] % 64 == 0:
                 p = k[: -len(".conv_shortcut.w")]
@@ -235,28 +222,6 @@ class _VaeEngineBase:
                 W[p + ".conv2.bf"] = (W[p + ".conv2.b"] + W[p + ".conv_shortcut.b"]).contiguous()
         self.W = W
         self._pack_ends(sd, conv3)
-
-    def _buf(self, name, shape, dtype, zero=False):
-        key = (name, tuple(int(s) for s in shape), dtype)
-        fresh = key not in self.arena.bufs
-        t = self.arena.get(name, shape, dtype)
-        if fresh and zero:
-            t.zero_()
-        return t
-
-    # GroupNorm statistics from the producing conv / GEMM epilogue (same scheme as seva/_engine.py:_stats_buf)
-    def _stats_buf(self, name, rows, hw, c):
-        if not self.gn_fused_stats or hw % ops.STATS_ROWS or c < 128 or c % 4:
-            return None
-        if self.gn_fused_stats < 2 and (hw // 128) * ((c + 159) // 160) < 16:  # per sample, never per batch
-            return None
-        return self._buf("st:" + name, ops.channel_stats_shape(rows, c), F32)
-
-    def _produced(self, out, st):
-        if st is None:
-            self._stats.pop(out.data_ptr(), None)
-        else:
-            self._stats[out.data_ptr()] = st
 
     def _resnet(self, p, x, n, h, w, cin, cout, f16_out=None, f8_out=None):
         """diffusers ResnetBlock2D (no time embedding): GN-SiLU-conv-GN-SiLU-conv + shortcut.
@@ -273,7 +238,7 @@ class _VaeEngineBase:
         a8 = self._buf("gn8", (n, hw, cin), U8) if f8_1 else None
         xs16 = self._buf("v_sk16", (n * hw, cin), F16) if cin != cout else None
         ops.groupnorm(x, None, W[p + ".norm1.g"], W[p + ".norm1.b"], a16, self.gn_ws, eps=1e-6, silu=True,
-                      stats1=self._stats.get(x.data_ptr()), raw_f16=None if xs16 is None else xs16.view(n, hw, cin), out_f8=a8)
+                      stats1=self._gn_stats(x)[0], raw_f16=None if xs16 is None else xs16.view(n, hw, cin), out_f8=a8)
         mid = self._buf("v_mid", (n, hw, cout), F32)
         st_mid = self._stats_buf("v_mid", n * hw, hw, cout)
         if f8_1:
@@ -285,34 +250,27 @@ class _VaeEngineBase:
         b8 = self._buf("gn8", (n, hw, cout), U8) if f8_2 else None
         ops.groupnorm(mid, None, W[p + ".norm2.g"], W[p + ".norm2.b"], b16, self.gn_ws, eps=1e-6, silu=True, stats1=st_mid,
                       out_f8=b8)
+        # conv2 + shortcut, in e4m3 or f16, into the one tensor its consumer reads
+        xb, w2, e2, b2, res, a2 = b16, W[p + ".conv2.w"], None, W[p + ".conv2.b"], x, None
         if f8_2:  # (never a channel-changing resnet: its folded shortcut is f16-only)
             assert cin == cout
-            w8, e8 = W8[p + ".conv2.w8"], W8[p + ".conv2.w8e"]
-            if f8_out is not None:
-                ops.conv3x3(b8.view(n, h, w, cout), w8, w_exp=e8, bias=W[p + ".conv2.b"], residual=x, out_f8=f8_out.view(n, hw, cout))
-                return f8_out
-            if f16_out is not None:
-                ops.conv3x3(b8.view(n, h, w, cout), w8, w_exp=e8, bias=W[p + ".conv2.b"], residual=x, out_f16=f16_out.view(n, hw, cout))
-                return f16_out
-            out = self._buf("out:" + p, (n, hw, cout), F32)
-            st_out = self._stats_buf("out:" + p, n * hw, hw, cout)
-            ops.conv3x3(b8.view(n, h, w, cout), w8, w_exp=e8, bias=W[p + ".conv2.b"], residual=x, out_f32=out, ch_stats=st_out)
-            self._produced(out, st_out)
-            return out
-        w2, b2, res, a2 = W[p + ".conv2.w"], W[p + ".conv2.b"], x, None
-        if cin != cout:
+            xb, w2, e2 = b8, W8[p + ".conv2.w8"], W8[p + ".conv2.w8e"]
+        elif cin != cout:
             if self.fold_shortcut and (p + ".conv2.wf") in W:
                 w2, b2, res, a2 = W[p + ".conv2.wf"], W[p + ".conv2.bf"], None, xs16
             else:
                 res = self._buf("v_sk32", (n * hw, cout), F32)
                 ops.gemm(xs16, W[p + ".conv_shortcut.w"], bias=W[p + ".conv_shortcut.b"], out_f32=res)
-        if f16_out is not None:
-            ops.conv3x3(b16.view(n, h, w, cout), w2, bias=b2, residual=res, a2=a2, out_f16=f16_out.view(n, hw, cout))
-            return f16_out
-        out = self._buf("out:" + p, (n, hw, cout), F32)
-        st_out = self._stats_buf("out:" + p, n * hw, hw, cout)
-        ops.conv3x3(b16.view(n, h, w, cout), w2, bias=b2, residual=res, a2=a2, out_f32=out, ch_stats=st_out)
-        self._produced(out, st_out)
+        if f8_out is not None:
+            out, dst = f8_out, {"out_f8": f8_out.view(n, hw, cout)}
+        elif f16_out is not None:
+            out, dst = f16_out, {"out_f16": f16_out.view(n, hw, cout)}
+        else:
+            out = self._buf("out:" + p, (n, hw, cout), F32)
+            st_out = self._stats_buf("out:" + p, n * hw, hw, cout)
+            dst = {"out_f32": out, "ch_stats": st_out}
+            self._produced(out, st_out)
+        ops.conv3x3(xb.view(n, h, w, cout), w2, w_exp=e2, bias=b2, residual=res, a2=a2, **dst)
         return out
 
     def _attention(self, p, x, n, h, w, c):
@@ -323,7 +281,7 @@ class _VaeEngineBase:
         hw_pad = 64 * ((hw + 63) // 64)
         g16 = self._buf("gn16", (n, hw, c), F16)
         ops.groupnorm(x, None, W[p + ".group_norm.g"], W[p + ".group_norm.b"], g16, self.gn_ws, eps=1e-6, silu=False,
-                      stats1=self._stats.get(x.data_ptr()))
+                      stats1=self._gn_stats(x)[0])
         q = self._buf("v_q", (n * hw, c), F16)
         k = self._buf("v_k", (n * hw, c), F16)
         ops.gemm(g16.view(n * hw, c), W[p + ".to_q.w"], bias=W[p + ".to_q.b"], out_f16=q)
@@ -344,7 +302,6 @@ class _VaeEngineBase:
                  out_f32=out.view(n * hw, c), ch_stats=st_out)
         self._produced(out, st_out)
         return out
-
 
 
 class VaeDecoderEngine(_VaeEngineBase):
@@ -446,7 +403,7 @@ class VaeDecoderEngine(_VaeEngineBase):
         c = rev[-1]
         g16 = self._buf("gn16", (n, h * w, c), F16)
         ops.groupnorm(x, None, W["decoder.conv_norm_out.g"], W["decoder.conv_norm_out.b"], g16, self.gn_ws,
-                      eps=1e-6, silu=True, stats1=self._stats.get(x.data_ptr()))
+                      eps=1e-6, silu=True, stats1=self._gn_stats(x)[0])
         o4 = self._buf("v_o4", (n, h * w, 4), F32)
         ops.conv3x3(g16.view(n, h, w, c), W["decoder.conv_out.w"], bias=W["decoder.conv_out.b"], out_f32=o4)
         out = torch.empty((n, self.out_channels, h, w), dtype=F32, device=self.device)
@@ -530,7 +487,7 @@ class VaeEncoderEngine(_VaeEngineBase):
         cur = self._resnet("encoder.mid_block.resnets.1", cur, n, h, w, top, top)
         g16 = self._buf("gn16", (n, h * w, top), F16)
         ops.groupnorm(cur, None, W["encoder.conv_norm_out.g"], W["encoder.conv_norm_out.b"], g16, self.gn_ws,
-                      eps=1e-6, silu=True, stats1=self._stats.get(cur.data_ptr()))
+                      eps=1e-6, silu=True, stats1=self._gn_stats(cur)[0])
         o4 = self._buf("v_m4", (n, h * w, self.latent), F32)
         ops.conv3x3(g16.view(n, h, w, top), W["enc_out.w"], bias=W["enc_out.b"], out_f32=o4)
         out = torch.empty((n, self.latent, h, w), dtype=F32, device=self.device)

@@ -61,28 +61,11 @@ def gemm(
     assert a.dim() == 2 and w.dim() == 2 and a.dtype == w.dtype == (U8 if fp8 else F16)
     M, K = a.shape
     N = w.shape[0]
-    d = GemmDesc()
-    d.a, d.w = ptr(a), w.data_ptr()
-    d.bias, d.row_add, d.residual = ptr(bias), ptr(row_add), ptr(residual)
-    d.out_f32, d.out_f16 = ptr(out_f32), ptr(out_f16)
-    d.M, d.N, d.K = M, N, K
-    d.alg_K = alg_k
-    d.lda = a.stride(0)
-    d.ldr = residual.stride(0) if residual is not None else 0
-    d.ldo32 = out_f32.stride(0) if out_f32 is not None else 0
-    d.ldo16 = out_f16.stride(0) if out_f16 is not None else 0
-    d.rows_per_group, d.ld_row_add = rows_per_group, ld_row_add
-    d.mode, d.epilogue = 0, 1 if geglu else 0
-    d.col_scale, d.col_scale_n = col_scale, col_scale_n
-    d.ch_stats = _stats_ptr(ch_stats, M, N, out_f32)
-    if splitk_ws is not None and not fp8:
-        assert splitk_ws.dtype == F32 and splitk_ws.is_contiguous()
-        d.splitk_ws, d.splitk_ws_bytes = splitk_ws.data_ptr(), splitk_ws.numel() * 4
-        _register_handoff_ws(splitk_ws)
+    d = _gemm_desc(a, w, (M, N, K), lda=a.stride(0), pitch_dim=0, fp8=fp8, geglu=geglu, col_scale=col_scale, col_scale_n=col_scale_n,
+                   bias=bias, row_add=row_add, rows_per_group=rows_per_group, ld_row_add=ld_row_add, residual=residual, out_f32=out_f32,
+                   out_f16=out_f16, w_exp=w_exp, out_f8=out_f8, ch_stats=ch_stats, splitk_ws=splitk_ws, alg_k=alg_k)
     if fp8:
         assert w_exp.dtype == U8 and w_exp.numel() == N and (out_f8 is None or out_f8.dtype == U8)
-        d.w_exp, d.out_f8 = w_exp.data_ptr(), ptr(out_f8)
-        d.ldo8 = out_f8.stride(0) if out_f8 is not None else 0
         check(_lib().seva_gemm_fp8(C.byref(d), stream_ptr(a.device)), "seva_gemm_fp8")
     elif split_out:
         assert out_f16.dtype == F16 and out_f16.stride(-1) == 1  # (a pitch below 2 NO is the library's error)
@@ -156,7 +139,57 @@ def _stats_ptr(ch_stats, M, N, out_f32):
     return ch_stats.data_ptr()
 
 
+def _pitch(t, dim: int) -> int:
+    return t.stride(dim) if t is not None else 0
+
+
+def _gemm_desc(a, w, mnk, *, lda, pitch_dim, conv=None, a2=None, fp8=False, geglu=False, col_scale=0.0, col_scale_n=0, bias=None,
+               row_add=None, rows_per_group=0, ld_row_add=0, residual=None, out_f32=None, out_f16=None, w_exp=None, out_f8=None,
+               ch_stats=None, splitk_ws=None, alg_k=0) -> GemmDesc:
+    """seva_gemm_desc of every GEMM / conv entry point.  mnk: (M, N, K), K including the K2 columns of a2; pitch_dim: the dimension of
+    residual / out_* whose stride is the row pitch (0: GEMM rows, -2: conv pixels); conv: (n, ih, iw, cin, oh, ow, stride, upsample
+    code, pad_br_only), None = plain GEMM.  A split-K workspace is handed on (and registered for `check_handoffs`) outside the fp8 mode."""
+    d = GemmDesc()
+    d.a, d.w = a.data_ptr(), w.data_ptr()
+    d.bias, d.row_add, d.residual = ptr(bias), ptr(row_add), ptr(residual)
+    d.out_f32, d.out_f16 = ptr(out_f32), ptr(out_f16)
+    d.M, d.N, d.K = mnk
+    d.alg_K = alg_k
+    d.lda = lda
+    d.ldr, d.ldo32, d.ldo16 = _pitch(residual, pitch_dim), _pitch(out_f32, pitch_dim), _pitch(out_f16, pitch_dim)
+    d.rows_per_group, d.ld_row_add = rows_per_group, ld_row_add
+    d.mode, d.epilogue = 0 if conv is None else 1, 1 if geglu else 0
+    d.col_scale, d.col_scale_n = col_scale, col_scale_n
+    if conv is not None:
+        d.n, d.ih, d.iw, d.cin, d.oh, d.ow, d.stride, d.upsample, d.pad_br_only = conv
+    if a2 is not None:
+        d.a2, d.lda2, d.K2 = a2.data_ptr(), a2.stride(0), a2.shape[1]
+    d.ch_stats = _stats_ptr(ch_stats, mnk[0], mnk[1], out_f32)
+    if splitk_ws is not None and not fp8:  # `splitk_workspace`: lets small-image convs run as split-K = 2 (seva_hip.h)
+        assert splitk_ws.dtype == F32 and splitk_ws.is_contiguous()
+        d.splitk_ws, d.splitk_ws_bytes = splitk_ws.data_ptr(), splitk_ws.numel() * 4
+        _register_handoff_ws(splitk_ws)
+    if fp8:
+        d.w_exp, d.out_f8, d.ldo8 = w_exp.data_ptr(), ptr(out_f8), _pitch(out_f8, pitch_dim)
+    return d
+
+
 FF_FUSED_CHANNELS = (64, 128, 256, 320)
+
+
+def _ff_desc(a, w1, b1, w2, b2, M, c, residual, out_f32, out_f16, ln_x, ln_gamma, ln_beta, ln_eps, w1_exp=None, w2_exp=None) -> nv.FfDesc:
+    """seva_ff_desc of both fused feed-forwards: the A operand is `a`, or with ln_x the LayerNorm prologue's (then d.a stays NULL)."""
+    d = nv.FfDesc()
+    d.w1, d.b1, d.w2, d.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
+    d.w1_exp, d.w2_exp = ptr(w1_exp), ptr(w2_exp)
+    if ln_x is not None:
+        d.ln_x, d.ln_gamma, d.ln_beta, d.ldx, d.ln_eps = ln_x.data_ptr(), ln_gamma.data_ptr(), ln_beta.data_ptr(), ln_x.stride(0), ln_eps
+    else:
+        d.a, d.lda = ptr(a), a.stride(0)
+    d.residual, d.out_f32, d.out_f16 = ptr(residual), ptr(out_f32), ptr(out_f16)
+    d.M, d.C = M, c
+    d.ldr, d.ldo32, d.ldo16 = _pitch(residual, 0), _pitch(out_f32, 0), _pitch(out_f16, 0)
+    return d
 
 
 def ff_fused(a: torch.Tensor | None, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, *,
@@ -172,15 +205,7 @@ def ff_fused(a: torch.Tensor | None, w1: torch.Tensor, b1: torch.Tensor, w2: tor
     assert (ln_x is not None and ln_x.dtype == F32 and ln_gamma is not None and ln_beta is not None) or a.dtype == F16
     assert w1.dtype == F16 and w2.dtype == F16 and w1.shape == (8 * c, c) and w2.shape == (c, 4 * c)
     assert w1.is_contiguous() and w2.is_contiguous() and c in FF_FUSED_CHANNELS
-    d = nv.FfDesc()
-    d.a, d.w1, d.b1, d.w2, d.b2 = ptr(a) if ln_x is None else None, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
-    if ln_x is not None:
-        d.ln_x, d.ln_gamma, d.ln_beta, d.ldx, d.ln_eps = ln_x.data_ptr(), ln_gamma.data_ptr(), ln_beta.data_ptr(), ln_x.stride(0), ln_eps
-    d.residual, d.out_f32, d.out_f16 = ptr(residual), ptr(out_f32), ptr(out_f16)
-    d.M, d.lda, d.C = M, (a.stride(0) if ln_x is None else 0), c
-    d.ldr = residual.stride(0) if residual is not None else 0
-    d.ldo32 = out_f32.stride(0) if out_f32 is not None else 0
-    d.ldo16 = out_f16.stride(0) if out_f16 is not None else 0
+    d = _ff_desc(a, w1, b1, w2, b2, M, c, residual, out_f32, out_f16, ln_x, ln_gamma, ln_beta, ln_eps)
     check(_lib().seva_ff_fused_f16(C.byref(d), stream_ptr(src.device)), "seva_ff_fused_f16")
 
 
@@ -224,16 +249,7 @@ def ff_fused_fp8(a: torch.Tensor | None, w1: torch.Tensor, w1_exp: torch.Tensor,
     assert w1.dtype == U8 and w2.dtype == U8 and w1.shape == (8 * c, kp) and w2.shape == (c, 4 * c)
     assert w1_exp.dtype == U8 and w2_exp.dtype == U8 and w1_exp.numel() == 8 * c and w2_exp.numel() == c
     assert w1.is_contiguous() and w2.is_contiguous() and c in FF_FUSED_CHANNELS
-    d = nv.FfDesc()
-    d.a, d.w1, d.b1, d.w2, d.b2 = ptr(a) if ln_x is None else None, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
-    d.w1_exp, d.w2_exp = w1_exp.data_ptr(), w2_exp.data_ptr()
-    if ln_x is not None:
-        d.ln_x, d.ln_gamma, d.ln_beta, d.ldx, d.ln_eps = ln_x.data_ptr(), ln_gamma.data_ptr(), ln_beta.data_ptr(), ln_x.stride(0), ln_eps
-    d.residual, d.out_f32, d.out_f16 = ptr(residual), ptr(out_f32), ptr(out_f16)
-    d.M, d.lda, d.C = M, (a.stride(0) if ln_x is None else 0), c
-    d.ldr = residual.stride(0) if residual is not None else 0
-    d.ldo32 = out_f32.stride(0) if out_f32 is not None else 0
-    d.ldo16 = out_f16.stride(0) if out_f16 is not None else 0
+    d = _ff_desc(a, w1, b1, w2, b2, M, c, residual, out_f32, out_f16, ln_x, ln_gamma, ln_beta, ln_eps, w1_exp, w2_exp)
     check(_lib().seva_ff_fused_fp8(C.byref(d), stream_ptr(src.device)), "seva_ff_fused_fp8")
 
 
@@ -274,42 +290,42 @@ def conv3x3(
     eh, ew = (2 * ih, 2 * iw) if upsample else (ih, iw)
     ps = 1 if pad_br_only else 2
     oh, ow = (eh + ps - 3) // stride + 1, (ew + ps - 3) // stride + 1
-    d = GemmDesc()
-    d.a, d.w = x.data_ptr(), w.data_ptr()
-    d.bias, d.row_add, d.residual = ptr(bias), ptr(row_add), ptr(residual)
-    d.out_f32, d.out_f16 = ptr(out_f32), ptr(out_f16)
-    d.M, d.N, d.K = n * oh * ow, w.shape[0], 9 * cin
+    M, N, K = n * oh * ow, w.shape[0], 9 * cin
     if a2 is not None:
-        assert not fp8 and not upsample and a2.dtype == F16 and a2.dim() == 2 and a2.stride(1) == 1 and a2.shape[0] == n * oh * ow
-        d.a2, d.lda2, d.K2 = a2.data_ptr(), a2.stride(0), a2.shape[1]
-        d.K = 9 * cin + a2.shape[1]
-    assert w.shape[1] == d.K
-    d.alg_K = alg_k
-    d.lda = cin
-    d.ldr = residual.stride(-2) if residual is not None else 0
-    d.ldo32 = out_f32.stride(-2) if out_f32 is not None else 0
-    d.ldo16 = out_f16.stride(-2) if out_f16 is not None else 0
-    d.rows_per_group, d.ld_row_add = rows_per_group, ld_row_add
-    d.mode, d.epilogue = 1, 0
-    d.n, d.ih, d.iw, d.cin, d.oh, d.ow = n, ih, iw, cin, oh, ow
-    d.stride, d.upsample = stride, 1 if upsample else 0
-    d.pad_br_only = 1 if pad_br_only else 0
-    d.ch_stats = _stats_ptr(ch_stats, n * oh * ow, w.shape[0], out_f32)
-    if splitk_ws is not None and not fp8:  # `splitk_workspace`: lets small-image convs run as split-K = 2 (seva_hip.h)
-        assert splitk_ws.dtype == F32 and splitk_ws.is_contiguous()
-        d.splitk_ws, d.splitk_ws_bytes = splitk_ws.data_ptr(), splitk_ws.numel() * 4
-        _register_handoff_ws(splitk_ws)
+        assert not fp8 and not upsample and a2.dtype == F16 and a2.dim() == 2 and a2.stride(1) == 1 and a2.shape[0] == M
+        K += a2.shape[1]
+    assert w.shape[1] == K
     if fp8:
-        assert w_exp.dtype == U8 and w_exp.numel() == w.shape[0]
-        d.w_exp = w_exp.data_ptr()
+        assert w_exp.dtype == U8 and w_exp.numel() == N
         if out_f8 is not None:
-            assert out_f8.dtype == U8 and out_f8.stride(-1) == 1 and out_f8.shape[-1] >= w.shape[0]
+            assert out_f8.dtype == U8 and out_f8.stride(-1) == 1 and out_f8.shape[-1] >= N
             assert not upsample, "out_f8 and the fused upsample are not available together"
-            d.out_f8, d.ldo8 = out_f8.data_ptr(), out_f8.stride(-2)
-        check(_lib().seva_gemm_fp8(C.byref(d), stream_ptr(x.device)), "seva_gemm_fp8(conv)")
     else:
         assert out_f8 is None, "out_f8 belongs to the fp8 conv (w_exp)"
+    d = _gemm_desc(x, w, (M, N, K), lda=cin, pitch_dim=-2, a2=a2, fp8=fp8, bias=bias, row_add=row_add, rows_per_group=rows_per_group,
+                   ld_row_add=ld_row_add, residual=residual, out_f32=out_f32, out_f16=out_f16, w_exp=w_exp, out_f8=out_f8,
+                   ch_stats=ch_stats, splitk_ws=splitk_ws, alg_k=alg_k,
+                   conv=(n, ih, iw, cin, oh, ow, stride, 1 if upsample else 0, 1 if pad_br_only else 0))
+    if fp8:
+        check(_lib().seva_gemm_fp8(C.byref(d), stream_ptr(x.device)), "seva_gemm_fp8(conv)")
+    else:
         check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), "seva_gemm_f16(conv)")
+
+
+def _up_phases(name: str, code: int, what: str, x, w4, bias, out_f32, ch_stats, alg_k) -> None:
+    """The two phase operators: seva_gemm_desc.upsample = `code` (2: 160-column tiles, no statistics; 4: 128-column tiles)."""
+    require_cuda(x, w4)
+    assert x.dtype == w4.dtype == F16 and x.dim() == 4 and x.is_contiguous() and w4.is_contiguous()
+    n, ih, iw, cin = x.shape
+    assert w4.dim() == 3 and w4.shape[0] == 4 and w4.shape[2] == 4 * cin, "w4: [4, cout, 4 * cin]"
+    if code == 2 and ch_stats is not None:
+        raise ValueError(f"{name} emits no GroupNorm statistics (ch_stats must be None)")
+    if out_f32 is None:
+        raise ValueError(f"{name} needs out_f32")
+    oh, ow = 2 * ih, 2 * iw
+    d = _gemm_desc(x, w4, (n * oh * ow, w4.shape[1], 4 * cin), lda=cin, pitch_dim=-2, conv=(n, ih, iw, cin, oh, ow, 1, code, 0),
+                   bias=bias, out_f32=out_f32, ch_stats=ch_stats, alg_k=alg_k)
+    check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), what)
 
 
 def conv3x3_up_phases(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tensor | None = None, out_f32: torch.Tensor | None = None,
@@ -320,24 +336,7 @@ def conv3x3_up_phases(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tensor |
     cout].  bias + out_f32 only, cout % 160 == 0.  The path emits no GroupNorm statistics: `ch_stats` must be None (the keyword
     names what the caller has to leave to the consumer's own statistics pass).  alg_k: reduction length the profiler credits
     (9 * cin: the reference operator).  Raises where the window kernel declines: no other kernel reads this weight layout."""
-    require_cuda(x, w4)
-    assert x.dtype == w4.dtype == F16 and x.dim() == 4 and x.is_contiguous() and w4.is_contiguous()
-    n, ih, iw, cin = x.shape
-    assert w4.dim() == 3 and w4.shape[0] == 4 and w4.shape[2] == 4 * cin, "w4: [4, cout, 4 * cin]"
-    if ch_stats is not None:
-        raise ValueError("conv3x3_up_phases emits no GroupNorm statistics (ch_stats must be None)")
-    if out_f32 is None:
-        raise ValueError("conv3x3_up_phases needs out_f32")
-    oh, ow = 2 * ih, 2 * iw
-    d = GemmDesc()
-    d.a, d.w, d.bias, d.out_f32 = x.data_ptr(), w4.data_ptr(), ptr(bias), out_f32.data_ptr()
-    d.M, d.N, d.K = n * oh * ow, w4.shape[1], 4 * cin
-    d.alg_K = alg_k
-    d.lda, d.ldo32 = cin, out_f32.stride(-2)
-    d.mode, d.epilogue = 1, 0
-    d.n, d.ih, d.iw, d.cin, d.oh, d.ow = n, ih, iw, cin, oh, ow
-    d.stride, d.upsample = 1, 2
-    check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), "seva_gemm_f16(conv, upsample phases)")
+    _up_phases("conv3x3_up_phases", 2, "seva_gemm_f16(conv, upsample phases)", x, w4, bias, out_f32, ch_stats, alg_k)
 
 
 def conv3x3_up_phases128(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tensor | None = None, out_f32: torch.Tensor | None = None,
@@ -347,23 +346,7 @@ def conv3x3_up_phases128(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tenso
     linear or 2-D tiles by one image's dimensions, and GroupNorm statistics: `ch_stats` (`channel_stats_shape(n * 4 ih iw, cout)`) gets
     one block per 64 output pixels of one phase, the blocks of an image adding up to that image; it needs ih * iw % 64 == 0.  Raises
     where the window kernel declines: no other kernel reads this weight layout."""
-    require_cuda(x, w4)
-    assert x.dtype == w4.dtype == F16 and x.dim() == 4 and x.is_contiguous() and w4.is_contiguous()
-    n, ih, iw, cin = x.shape
-    assert w4.dim() == 3 and w4.shape[0] == 4 and w4.shape[2] == 4 * cin, "w4: [4, cout, 4 * cin]"
-    if out_f32 is None:
-        raise ValueError("conv3x3_up_phases128 needs out_f32")
-    oh, ow = 2 * ih, 2 * iw
-    d = GemmDesc()
-    d.a, d.w, d.bias, d.out_f32 = x.data_ptr(), w4.data_ptr(), ptr(bias), out_f32.data_ptr()
-    d.M, d.N, d.K = n * oh * ow, w4.shape[1], 4 * cin
-    d.alg_K = alg_k
-    d.lda, d.ldo32 = cin, out_f32.stride(-2)
-    d.mode, d.epilogue = 1, 0
-    d.n, d.ih, d.iw, d.cin, d.oh, d.ow = n, ih, iw, cin, oh, ow
-    d.stride, d.upsample = 1, 4
-    d.ch_stats = _stats_ptr(ch_stats, n * oh * ow, w4.shape[1], out_f32)
-    check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), "seva_gemm_f16(conv, upsample phases, 128 columns)")
+    _up_phases("conv3x3_up_phases128", 4, "seva_gemm_f16(conv, upsample phases, 128 columns)", x, w4, bias, out_f32, ch_stats, alg_k)
 
 
 def attention(
@@ -390,16 +373,7 @@ def attention(
     q/k/v/out are f16 tensors (any views); strides are (batch-outer, batch-inner, token) in
     elements relative to the tensors' data pointers; head h sits at element offset 64*h."""
     require_cuda(q, k, v, out)
-    d = AttnDesc()
-    d.q, d.k, d.v, d.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    d.q_sb0, d.q_sb1, d.q_sl = q_strides
-    d.k_sb0, d.k_sb1, d.k_sl = k_strides
-    d.o_sb0, d.o_sb1, d.o_sl = o_strides
-    d.nb0, d.nb1, d.heads, d.lq, d.lk, d.scale = nb0, nb1, heads, lq, lk, scale
-    d.q_prescaled = 1 if q_prescaled else 0
-    if split_ws is not None:  # `attention_split_workspace`: lets long key sequences run K/V-split (seva_attn_desc.split_ws)
-        assert split_ws.dtype == F32 and split_ws.is_contiguous()
-        d.split_ws, d.split_ws_bytes = split_ws.data_ptr(), split_ws.numel() * 4
+    d = _attn_desc(q, k, v, out, nb0, nb1, heads, lq, lk, q_strides, k_strides, o_strides, split_ws, scale, q_prescaled)
     check(_lib().seva_attention_f16(C.byref(d), stream_ptr(q.device)), "seva_attention_f16")
 
 
@@ -432,15 +406,16 @@ def _v_fp8_ptrs(ws: torch.Tensor, batch: int, heads: int, lk: int) -> tuple[int,
     return ws.data_ptr(), ws.data_ptr() + v8
 
 
-def _attn_desc(q, k, v, out, nb0, nb1, heads, lq, lk, q_strides, k_strides, o_strides, split_ws) -> AttnDesc:
+def _attn_desc(q, k, v, out, nb0, nb1, heads, lq, lk, q_strides, k_strides, o_strides, split_ws, scale=0.0, q_prescaled=True) -> AttnDesc:
+    """seva_attn_desc of the three attention entry points (the fp8 pair: q pre-scaled, `scale` unused; the quantiser passes V alone)."""
     d = AttnDesc()
     d.q, d.k, d.v, d.out = ptr(q), ptr(k), ptr(v), ptr(out)
     d.q_sb0, d.q_sb1, d.q_sl = q_strides
     d.k_sb0, d.k_sb1, d.k_sl = k_strides
     d.o_sb0, d.o_sb1, d.o_sl = o_strides
-    d.nb0, d.nb1, d.heads, d.lq, d.lk = nb0, nb1, heads, lq, lk
-    d.q_prescaled = 1
-    if split_ws is not None:
+    d.nb0, d.nb1, d.heads, d.lq, d.lk, d.scale = nb0, nb1, heads, lq, lk, scale
+    d.q_prescaled = 1 if q_prescaled else 0
+    if split_ws is not None:  # `attention_split_workspace`: lets long key sequences run K/V-split (seva_attn_desc.split_ws)
         assert split_ws.dtype == F32 and split_ws.is_contiguous()
         d.split_ws, d.split_ws_bytes = split_ws.data_ptr(), split_ws.numel() * 4
     return d
