@@ -488,7 +488,53 @@ int seva_rgb_to_u8(const float* x, int64_t x_pitch_n, uint8_t* out, int32_t n, i
                    seva_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Benchmark / debugging knobs.  The library reads its SEVA_* environment variables ONCE, when it is loaded (nothing
+ * Image-space scores: per-frame squared error (-> MSE / PSNR) and SSIM of two batches of frames, on the uint8 values a
+ * user would save.  New symbols and one new struct; no existing struct changes (ABI version unchanged).
+ *
+ *   inputs     a, b: n frames H x W x 3 each, both of one kind.  kind 0: uint8 [n][H][W][3], rows and pixels dense,
+ *              images *_pitch_n BYTES apart.  kind 1: fp32 [n][3][H][W] in [-1, 1], planes and rows dense, images
+ *              *_pitch_n FLOATS apart; every value goes through the rule of seva_rgb_to_u8 as it is loaded
+ *              ((v + 1) / 2 * 255, clamp, truncate, NaN -> 0), so both kinds score the same integers.
+ *   sse        sse[i] = sum over the H*W*3 elements of (a - b)^2, exact, int64.
+ *   ssim       Wang et al. 2004, per channel: 11-tap Gaussian window, sigma 1.5, g[k] = exp(-(k-5)^2 / 4.5) normalised
+ *              to sum 1 in fp64 and rounded once to fp32, applied separably (along a row first, then down the column)
+ *              at "valid" positions only: (H-10) x (W-10) per channel.  All arithmetic is fp32, every operation rounded
+ *              on its own (no FMA), on x = float(a), y = float(b):
+ *                each pass:  acc = 0; for k = 0..10: acc = acc + g[k] * v[k]        (v = x, y, x*x, y*y, x*y in the row
+ *                            pass; the row pass's five results in the column pass)
+ *                moments:    mx, my, exx, eyy, exy;  mxx = mx*mx, myy = my*my, mxy = mx*my;
+ *                            sx = exx - mxx, sy = eyy - myy, sxy = exy - mxy                         (biased)
+ *                map:        ((2*mxy + C1) * (2*sxy + C2)) / (((mxx + myy) + C1) * ((sx + sy) + C2)), one correctly
+ *                            rounded division;  C1 = (0.01*255)^2 = 6.5025f, C2 = (0.03*255)^2 = 58.5225f
+ *              The two frames' expressions are the same operations in the same order: a frame against itself gives
+ *              exactly 1.0 at every position.  Each position's fp32 value is widened to fp64 and summed:
+ *              ssim_sum[i] = sum over 3 channels and all valid positions; the caller divides by 3 (H-10) (W-10).
+ *              ssim_map (optional): the fp32 values, [n][3][H-10][W-10] dense.
+ *   reduction  one workgroup per 32 x 32 tile of an image; the threads' partials are summed by a fixed binary tree, one
+ *              (fp64 SSIM sum, u32 squared error) pair per tile goes into the workspace, and a second kernel sums an
+ *              image's tiles in a fixed order.  No atomics: results repeat bit for bit and depend on nothing but the
+ *              image itself -- not on n, on the pitches, on what else runs or on what surrounds the outputs.
+ * ssim != 0 needs ssim_sum and H, W >= 11 (error otherwise); ssim == 0 computes sse only, for any H, W >= 1, and
+ * ssim_sum / ssim_map must then be NULL.  seva_frame_metrics_size: bytes of `workspace` (8-byte aligned). */
+typedef struct seva_metrics_desc {
+  const void* a;            /* generated frames */
+  const void* b;            /* target frames, same kind and shape */
+  int64_t* sse;             /* [n] */
+  double* ssim_sum;         /* [n]; NULL when ssim == 0 */
+  float* ssim_map;          /* optional [n][3][H-10][W-10] */
+  void* workspace;          /* seva_frame_metrics_size bytes; contents need not be kept between calls */
+  int64_t a_pitch_n;        /* kind 0: bytes, kind 1: floats; >= 3*H*W */
+  int64_t b_pitch_n;
+  int64_t workspace_bytes;
+  int32_t n, H, W;
+  int32_t kind;             /* 0: uint8 NHWC, 1: fp32 NCHW */
+  int32_t ssim;             /* 0: sse only */
+} seva_metrics_desc;
+int seva_frame_metrics_size(int32_t n, int32_t H, int32_t W, int64_t* workspace_bytes);
+int seva_frame_metrics(const seva_metrics_desc* d, seva_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Benchmark / debugging knobs. The library reads its SEVA_* environment variables ONCE, when it is loaded (nothing
  * on the launch path calls getenv); a host changes a knob at run time with seva_set_knob (tests, tools).  Names:
  * gemm_chunks, gemm_dbg, gemm_stagger, gemm_bm, gemm_bn, gemm_astat, attn_dbg, attn_no_tr, attn_two, attn_split,
  * gn_min_iter, conv_win (0: per-tap conv gather everywhere; 1 / 2: force the 4-wave / 8-wave family of the window-staged conv kernel)

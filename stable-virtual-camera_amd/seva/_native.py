@@ -89,6 +89,15 @@ class ImageDesc(C.Structure):
     ]
 
 
+class MetricsDesc(C.Structure):
+    _fields_ = [
+        ("a", c_void_p), ("b", c_void_p), ("sse", c_void_p), ("ssim_sum", c_void_p), ("ssim_map", c_void_p),
+        ("workspace", c_void_p),
+        ("a_pitch_n", c_int64), ("b_pitch_n", c_int64), ("workspace_bytes", c_int64),
+        ("n", c_int32), ("H", c_int32), ("W", c_int32), ("kind", c_int32), ("ssim", c_int32),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/seva_hip.h
 SYMBOLS = {
     "seva_last_error": (c_char_p, []),
@@ -138,6 +147,8 @@ SYMBOLS = {
     "seva_image_area_crop_u8": (c_int, [POINTER(ImageDesc), c_void_p]),
     "seva_image_area_crop_f32": (c_int, [POINTER(ImageDesc), c_void_p]),
     "seva_rgb_to_u8": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "seva_frame_metrics_size": (c_int, [c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "seva_frame_metrics": (c_int, [POINTER(MetricsDesc), c_void_p]),
     "seva_set_knob": (c_int, [c_char_p, c_int32]),
     "seva_get_knob": (c_int, [c_char_p, POINTER(c_int32)]),
     "seva_graph_begin": (c_int, [c_void_p]),

@@ -13,7 +13,7 @@ import ctypes as C
 import torch
 
 from . import _native as nv
-from ._native import AttnDesc, GemmDesc, GroupNormDesc, ImageDesc, check, ptr, require_cuda, stream_ptr
+from ._native import AttnDesc, GemmDesc, GroupNormDesc, ImageDesc, MetricsDesc, check, ptr, require_cuda, stream_ptr
 
 F16, F32 = torch.float16, torch.float32
 U8 = torch.uint8  # e4m3 bytes travel as uint8 tensors (bit pattern of torch.float8_e4m3fn)
@@ -823,6 +823,50 @@ def rgb_to_u8(x: torch.Tensor, out: torch.Tensor) -> None:
     assert x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W, "input planes must be dense"
     assert out.shape == (n, H, W, 3) and out.is_contiguous()
     check(_lib().seva_rgb_to_u8(x.data_ptr(), x.stride(0), out.data_ptr(), n, H, W, stream_ptr(x.device)), "seva_rgb_to_u8")
+
+
+def frame_metrics_workspace_numel(n: int, H: int, W: int) -> int:
+    """uint8 elements of `frame_metrics(workspace=...)`: one (fp64, u32) partial per 32 x 32 tile of every image."""
+    size = C.c_int64()
+    check(_lib().seva_frame_metrics_size(int(n), int(H), int(W), C.byref(size)), "seva_frame_metrics_size")
+    return size.value
+
+
+def frame_metrics(a: torch.Tensor, b: torch.Tensor, sse: torch.Tensor, ssim_sum: torch.Tensor | None = None,
+                  ssim_map: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> None:
+    """Per-frame squared error and SSIM sums of two batches of frames on their uint8 values (seva_frame_metrics; the contract
+    is in include/seva_hip.h).  a, b: both uint8 (n,H,W,3), images dense, any image pitch -- or both fp32 (n,3,H,W) in [-1, 1],
+    planes dense, any image pitch (scored through the uint8 rule of `rgb_to_u8`).  sse: int64 (n).  ssim_sum: fp64 (n), the
+    sum of the SSIM map over 3 (H-10) (W-10) positions (None: squared error only); ssim_map: optional fp32 (n,3,H-10,W-10).
+    workspace: uint8, `frame_metrics_workspace_numel` elements (None: allocated here)."""
+    require_cuda(a, b, sse, ssim_sum, ssim_map, workspace)
+    assert a.dim() == 4 and a.shape == b.shape and a.dtype == b.dtype and a.dtype in (U8, F32)
+    d = MetricsDesc()
+    if a.dtype == U8:
+        n, H, W, c = a.shape
+        assert c == 3
+        for x in (a, b):
+            assert x.stride(3) == 1 and x.stride(2) == 3 and x.stride(1) == 3 * W, "uint8 frames: (n,H,W,3) with dense images"
+        d.kind = 0
+    else:
+        n, c, H, W = a.shape
+        assert c == 3
+        for x in (a, b):
+            assert x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W, "fp32 frames: (n,3,H,W) with dense planes"
+        d.kind = 1
+    assert sse.dtype == torch.int64 and sse.shape == (n,) and sse.is_contiguous()
+    assert ssim_sum is None or (ssim_sum.dtype == torch.float64 and ssim_sum.shape == (n,) and ssim_sum.is_contiguous())
+    assert ssim_map is None or (ssim_sum is not None and ssim_map.dtype == F32 and ssim_map.is_contiguous()
+                                and ssim_map.shape == (n, 3, H - 10, W - 10))
+    need = frame_metrics_workspace_numel(n, H, W)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=U8, device=a.device)
+    assert workspace.dtype == U8 and workspace.is_contiguous() and workspace.numel() >= need, "frame_metrics workspace too small"
+    d.a, d.b, d.sse, d.ssim_sum, d.ssim_map, d.workspace = a.data_ptr(), b.data_ptr(), sse.data_ptr(), ptr(ssim_sum), ptr(ssim_map), \
+        workspace.data_ptr()
+    d.a_pitch_n, d.b_pitch_n, d.workspace_bytes = a.stride(0), b.stride(0), workspace.numel()
+    d.n, d.H, d.W, d.ssim = n, H, W, int(ssim_sum is not None)
+    check(_lib().seva_frame_metrics(C.byref(d), stream_ptr(a.device)), "seva_frame_metrics")
 
 
 # --- benchmark / debugging knobs (read from SEVA_* once at library load; see include/seva_hip.h) ---------

@@ -31,6 +31,10 @@ CLIP token: `clip_token` (one 1024-d token for every window), `clip_fn(window_so
 own rule (eval.py:1248: mean CLIP embedding of the window's conditioning views) -- `conditioner=` + `input_rgb=` with
 `handoff="rgb"` and an `ae`: the anchors are then decoded once after pass 1, every window's token is
 `conditioner(rgb of its conditioning frames).mean(0)` and the anchors re-enter pass 2 through `ae.encode`, as in the reference.
+
+One pass (`plan_views` / `run_views`, `run_scene(use_traj_prior=False)`): the reference's evaluation mode (eval.py:1472-1629,
+tasks `img2img` / `img2vid`) -- the first-pass half of the plan over EVERY non-input frame, no second pass; the same driver
+runs it.  `run_scene(targets=...)` scores the generated frames against held-out pictures (`seva.metrics`: PSNR / SSIM).
 """
 
 from __future__ import annotations
@@ -92,6 +96,34 @@ def _windows(pass_id, base, T, chunks, src_pool, tgt_pool, padding_mode="last"):
     return out
 
 
+def _input_conditioned_windows(c2ws, ins, targets, T, opts, task, strategy):
+    """Windows that generate the frames `targets` from the input views `ins` (the two-pass mode's first pass over the
+    anchors, the one-pass mode's only pass over every non-input frame) -> (windows, serial)."""
+    p1 = planner.chunk_input_and_test(T, c2ws[ins], c2ws[targets], [float(i) for i in ins], [float(a) for a in targets],
+                                      opts, task=task, chunk_strategy=strategy, gt_input_inds=list(range(len(ins))))
+    serial = strategy in DEPENDENT_FIRST_PASS
+    # source pool: the inputs, then (dependent strategies) the targets in the order they are generated
+    pool1 = list(ins)
+    if serial:
+        for ti in p1[3]:
+            pool1.extend(targets[j] for j in ti)
+    return _windows(1, 0, T, p1, pool1, targets, opts.get("t_padding_mode", "last")), serial
+
+
+def plan_views(c2ws: torch.Tensor, input_ids: Sequence[int], T: int = 21, chunk_strategy: str = "gt",
+               options: dict | None = None, task: str = "img2img") -> TrajectoryPlan:
+    """One-pass plan (the reference's `use_traj_prior=False` branch, eval.py:1472-1629, the mode of its evaluation tasks
+    `img2img` / `img2vid`): every non-input frame is a target of ONE pass of windows conditioned on the input views
+    (`chunk_strategy`, default "gt"; dependent strategies also read earlier windows' outputs, in generation order).  In
+    the plan's terms every non-input frame stands in the anchors' place and `pass2` is empty, which `run_trajectory`
+    drives as it is: independent windows sharded round-robin over the ranks, dependent ones serial on rank 0."""
+    ins = [int(i) for i in input_ids]
+    opts = {"sampler_verbose": False, **(options or {}), "chunk_strategy": chunk_strategy}
+    targets = [i for i in range(c2ws.shape[0]) if i not in set(ins)]
+    w1, serial = _input_conditioned_windows(c2ws, ins, targets, T, opts, task, chunk_strategy)
+    return TrajectoryPlan(T, ins, targets, w1, [], serial)
+
+
 def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int = 21, chunk_strategy: str = "interp",
                     first_pass_strategy: str = "gt-nearest", options: dict | None = None,
                     task: str = "img2trajvid", refine_anchors: bool = True) -> TrajectoryPlan:
@@ -111,16 +143,7 @@ def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int = 21, c
     T1, T2 = vd["T"] if isinstance(vd["T"], (list, tuple)) else (T, T)
     assert T1 == T2 == T, "different window lengths per pass are not driven by this pipeline"
     anchors = [int(v) for v in planner.infer_prior_inds(c2ws, n_prior, ins, opts)]
-    p1 = planner.chunk_input_and_test(T, c2ws[ins], c2ws[anchors], [float(i) for i in ins], [float(a) for a in anchors],
-                                      opts, task=task, chunk_strategy=first_pass_strategy,
-                                      gt_input_inds=list(range(len(ins))))
-    serial = first_pass_strategy in DEPENDENT_FIRST_PASS
-    # pass-1 source pool: the inputs, then (dependent strategies) the anchors in the order they are generated
-    pool1 = list(ins)
-    if serial:
-        for ti in p1[3]:
-            pool1.extend(anchors[j] for j in ti)
-    w1 = _windows(1, 0, T, p1, pool1, anchors, opts.get("t_padding_mode", "last"))
+    w1, serial = _input_conditioned_windows(c2ws, ins, anchors, T, opts, task, first_pass_strategy)
     order = np.argsort(ins + anchors).tolist()
     pool2 = [(ins + anchors)[o] for o in order]
     skip = set(ins) if refine_anchors else set(ins) | set(anchors)
@@ -292,7 +315,10 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
         mine1 = list(range(len(plan.pass1))) if world == 1 else (
             ([i for i in range(len(plan.pass1))] if rank == 0 else []) if plan.pass1_serial
             else shard_windows(len(plan.pass1), rank, world))
-    got_ids, got_lat = [], []
+    # one pass + RGB hand-off: a frame's OUTPUT is its own sample (the reference decodes it directly, `decode_output`); only later
+    # windows see the re-encoded latent.  (Two passes keep the handed-off latent for anchors the second pass does not regenerate.)
+    keep_own = handoff == "rgb" and ae is not None and not plan.pass2
+    got_ids, got_lat, got_own = [], [], []
     for i in mine1:
         win = plan.pass1[i]
         t_w = _now(device) if timers is not None else 0.0
@@ -301,11 +327,13 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
         if timers is not None:
             timers.setdefault("windows", []).append((1, i, _now(device) - t_w))
         zt = handoff_latent(z[win.target_slots], win.target_ids)
-        for fid, lat in zip(win.target_ids, zt):
+        for fid, lat, own in zip(win.target_ids, zt, z[win.target_slots]):
             latents_of[fid] = lat  # a dependent strategy's next window on this rank may read it
             if not (split1 and rank == 1):  # (rank 1 of the pair holds the same bits; rank 0 is the owner that publishes them)
                 got_ids.append(fid)
                 got_lat.append(lat)
+                if keep_own:
+                    got_own.append(own)
     mark("pass1")
     # ------------------------------------------------------------------ exchange: one all-gather of the anchors
     counts = [0] * world
@@ -320,7 +348,12 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
     for r in range(world):
         for j, fid in enumerate(owner_ids[r]):
             latents_of[fid] = parts[r][j]
-    if conditioner is not None:  # ranks that did not generate an anchor need its RGB for the CLIP token: decode locally (1.66 MB of
+    own_of = {}
+    if keep_own:
+        local = torch.stack(got_own) if got_own else torch.zeros((0, 4, h, w), device=device)
+        parts = _all_gather_padded(local.to(device=device, dtype=torch.float32), counts[rank], max(max(counts), 1), group)
+        own_of = {fid: parts[r][j] for r in range(world) for j, fid in enumerate(owner_ids[r])}
+    if conditioner is not None and plan.pass2:  # ranks that did not generate an anchor need its RGB for the CLIP token: decode locally (1.66 MB of
         for fid in plan.anchor_ids:  # latents travelled, not 40 MB of RGB)
             if fid not in rgb_of:
                 rgb_of[fid] = ae.decode(latents_of[fid][None])[0]
@@ -362,7 +395,7 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
     final = torch.zeros((n, 4, h, w), device=device)
     filled = torch.zeros(n, dtype=torch.bool)
     for fid in plan.input_ids + plan.anchor_ids:  # (anchors: first-pass samples, overwritten below when pass 2 regenerates them)
-        final[fid] = latents_of[fid]
+        final[fid] = own_of.get(fid, latents_of[fid])
         filled[fid] = True
     for i, win in enumerate(plan.pass2):
         z = collected[i]
@@ -379,15 +412,28 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
     return res
 
 
+def run_views(denoise_net: Callable, input_latents: torch.Tensor, c2ws: torch.Tensor, Ks: torch.Tensor,
+              input_ids: Sequence[int], *, T: int = 21, chunk_strategy: str = "gt", options: dict | None = None,
+              task: str = "img2img", **run_trajectory_kwargs) -> dict:
+    """One-pass generation of every non-input frame: `run_trajectory` over `plan_views(...)`; every other argument and the
+    result are `run_trajectory`'s ("anchor_latents": every generated frame as later windows saw it)."""
+    plan = plan_views(c2ws, input_ids, T, chunk_strategy, options, task)
+    return run_trajectory(denoise_net, input_latents, c2ws, Ks, input_ids, T=T, plan=plan, **run_trajectory_kwargs)
+
+
 def run_scene(denoise_net: Callable, ae, images: Sequence, c2ws: torch.Tensor, Ks: torch.Tensor, input_ids: Sequence[int], *,
               size=(576, 576), conditioner: Callable | None = None, clip_token: torch.Tensor | None = None,
-              **run_trajectory_kwargs) -> dict:
+              use_traj_prior: bool = True, targets: dict | None = None, **run_trajectory_kwargs) -> dict:
     """Pictures + cameras in, uint8 frames out: `frames.load_img_and_K` per input picture (a path, a uint8 (h,w,3|4) array
     or tensor; covered and cropped to `size` = (W, H)), `ae.encode`, `run_trajectory`, `ae.decode`, `frames.to_uint8`.
     `Ks` (n,3,3) as `run_trajectory` takes them (normalised); the input views' rows are replaced by the intrinsics of the
     cropped pictures.  With a `conditioner` the loaded pictures are its `input_rgb` and the hand-off goes through RGB, as
     `run_trajectory` requires.  A composition only: on rank 0 the result of `run_trajectory` (with "rgb") plus "frames"
-    (n,H,W,3) uint8 and "Ks" (n_in,3,3), the adjusted intrinsics of the input views in pixels of the frames."""
+    (n,H,W,3) uint8 and "Ks" (n_in,3,3), the adjusted intrinsics of the input views in pixels of the frames.
+    `use_traj_prior=False`: the reference's one-pass evaluation mode (`run_views`; `chunk_strategy` then defaults to "gt",
+    `options` / `task` go to `plan_views`).  `targets` = {frame id: picture}: held-out pictures, loaded exactly like the inputs
+    and scored against the generated frames of those ids (`metrics.compare` on the uint8 frames) -> on rank 0
+    "metrics" = {"frame_ids", "sse", "psnr", "ssim"}; in either mode."""
     from . import frames
     device = torch.device(run_trajectory_kwargs.pop("device", None) or "cuda")
     ids = [int(i) for i in input_ids]
@@ -405,8 +451,15 @@ def run_scene(denoise_net: Callable, ae, images: Sequence, c2ws: torch.Tensor, K
     if conditioner is not None:
         kw.update(conditioner=conditioner, input_rgb=input_rgb)
         kw.setdefault("handoff", "rgb")
-    res = run_trajectory(denoise_net, ae.encode(input_rgb), c2ws, Ks, ids, clip_token=clip_token, device=device, ae=ae, **kw)
+    run = run_trajectory if use_traj_prior else run_views
+    res = run(denoise_net, ae.encode(input_rgb), c2ws, Ks, ids, clip_token=clip_token, device=device, ae=ae, **kw)
     if "rgb" in res:  # rank 0
         res["frames"] = frames.to_uint8(res["rgb"])
         res["Ks"] = torch.stack(K_px)
+        if targets:
+            from . import metrics
+            tids = sorted(int(f) for f in targets)
+            want = torch.cat([frames.to_uint8(frames.load_img_and_K(targets[f], size, device=device)[0]) for f in tids])
+            m = metrics.compare(res["frames"][tids], want)
+            res["metrics"] = {"frame_ids": tids, "sse": m["sse"], "psnr": m["psnr"], "ssim": m["ssim"]}
     return res
