@@ -15,12 +15,9 @@
 // Regimes: per-frame / joint attention use 4 waves x 64-key tiles; the temporal
 // regime (L = num_frames <= 32, batch = pixels) uses one wave per (pixel, head) with a 32-key
 // tile and reads its tokens through the token stride, so no (b t) s c <-> (b s) t c transpose exists.
-#include "seva_common.h"
-#include "attn_pv8.h"
+#include "attn_common.h"
 
 #include <stdlib.h>
-
-#include <type_traits>
 
 namespace {
 // Two softmax probabilities -> one f16 pair, round to nearest even (v_cvt_pk_f16_f32, one instruction like the round-toward-zero pack
@@ -33,40 +30,9 @@ __device__ __forceinline__ p16x2_t pack_p(float e0, float e1) {
   return __builtin_bit_cast(p16x2_t, __builtin_convertvector(f32x2{e0, e1}, half2_t));
 }
 
-struct AttnArgs {
-  const half_t* q;
-  const half_t* k;
-  const half_t* v;
-  half_t* out;
-  int64_t q_sb0, q_sb1, q_sl;
-  int64_t k_sb0, k_sb1, k_sl;
-  int64_t o_sb0, o_sb1, o_sl;
-  int32_t nb1, heads, lq, lk, qblocks;
-  float scale_log2;  // softmax scale * log2(e)  (unused when q is pre-scaled)
-  int32_t dbg;       // ablation bits (SEVA_ATTN_DBG; timing only): 1 no K/V reloads, 2 no softmax, 4 no P*V, 8 no Q*K
-  // K/V split (attn2_kernel<.., true> + attn_combine_kernel): every (batch, head, query block) is computed by `nsplit` workgroups,
-  // each over a contiguous range of whole K/V tiles, which leave their UN-normalised fp32 O rows and (m, l) in the workspace
-  float* part_o;     // [nsplit][batch * heads * lq][64]
-  float* part_ml;    // [nsplit][batch * heads * lq][2]
-  int32_t nsplit;
-};
+struct AttnArgs : AttnBase {};  // (its own type: the kernels' names carry it)
 
 typedef short short8_t __attribute__((ext_vector_type(8)));
-
-// LDS-DMA from inline asm (see gemm_common.h: hipcc would otherwise drain it with vmcnt(0) before
-// every ds_read); ordered only by the counted waits + barriers below.
-__device__ __forceinline__ void glds16_raw(const void* gsrc, unsigned lds_wave_base) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_wave_base)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 __device__ __forceinline__ half8_t tr_read_pair(const char* a0, const char* a1) {
   short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)a0);
@@ -76,7 +42,6 @@ __device__ __forceinline__ half8_t tr_read_pair(const char* a0, const char* a1) 
 }
 
 __device__ __forceinline__ int v_chunk_swz(int row, int chunk) { return chunk ^ (((row >> 1) & 1) << 2); }
-__device__ __forceinline__ int k_chunk_swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
 // DBGK: the ablation instantiation reads p.dbg at run time; the production one has no such branches
 // (they split the tile body into dozens of basic blocks and stop the scheduler interleaving
@@ -99,36 +64,22 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_kernel(AttnArgs p) {
   constexpr int KB = KT / 32;               // 32-key blocks per tile
   const int dbg = DBGK ? p.dbg : 0;
 
-  // 3-deep ring of K/V tiles filled by LDS-DMA two tiles ahead: [buf][K tile | V tile]
-  __shared__ __attribute__((aligned(16))) char smem[3 * 2 * KT * 128];
+  __shared__ __attribute__((aligned(16))) char smem[3 * 2 * KT * 128];  // the K/V ring: [buf][K tile | V tile]
   constexpr int BUF_BYTES = 2 * KT * 128;
-  constexpr int IP = KT / 8 / NW;  // 8-row LDS-DMA instructions per wave per operand per tile
-  constexpr int G = 2 * IP;        // ... per wave per tile (K and V)
-  static_assert(KT % (8 * NW) == 0, "tile rows must split over the waves");
+  typedef AttnRing<KT, NW, BUF_BYTES, v_chunk_swz> Ring;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int qi = lane & 31, hh = lane >> 5;
 
-  // logical id = ((batch * heads) + head) * qblocks + qblock.  Hardware deals blocks b, b+8, ... to
-  // one XCD; the bijective remap gives every XCD one contiguous run of logical ids, so the q-blocks
-  // of a (batch, head) pair -- which all stream the same K/V -- share one L2.
-  int bid;
-  {
-    const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = blockIdx.x & 7;
-    bid = ((x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (blockIdx.x >> 3);
-  }
-  const int qb = bid % p.qblocks;
-  bid /= p.qblocks;
-  const int head = bid % p.heads;
-  const int batch = bid / p.heads;
-  const int b0 = batch / p.nb1, b1 = batch - b0 * p.nb1;
-
-  const half_t* const qbase = p.q + b0 * p.q_sb0 + b1 * p.q_sb1 + head * 64;
-  const half_t* const kbase = p.k + b0 * p.k_sb0 + b1 * p.k_sb1 + head * 64;
-  const half_t* const vbase = p.v + b0 * p.k_sb0 + b1 * p.k_sb1 + head * 64;
-  half_t* const obase = p.out + b0 * p.o_sb0 + b1 * p.o_sb1 + head * 64;
+  AttnWg w;
+  attn_decode<false>(p, KT, w);
+  const int qb = w.qb;
+  const half_t* const qbase = attn_q_base(p, w);
+  const half_t* const kbase = attn_kv_base(p, w, p.k);
+  const half_t* const vbase = attn_kv_base(p, w, p.v);
+  half_t* const obase = attn_o_base(p, w);
 
   const int qrow = qb * (32 * NW) + wave * 32 + qi;
   const int qrow_c = qrow < p.lq ? qrow : p.lq - 1;
@@ -155,61 +106,16 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_kernel(AttnArgs p) {
   const float c = p.scale_log2;
 
   const int nt = (p.lk + KT - 1) / KT;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  const unsigned smem_base =
-      __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-  // lane (r = lane>>3, physical chunk = lane&7) of each 8-row wave-instruction; the swizzle is applied
-  // on the SOURCE chunk (the LDS image of an LDS-DMA is lane-linear)
-  const int sr = lane >> 3, sp = lane & 7;
-  // Tiles are issued strictly in order 0, 1, 2, ...: the per-lane source pointers of the NEXT tile to issue are
-  // running state, advanced by the workgroup-uniform tile stride (the 64-bit key * stride products cost four
-  // quarter-rate v_mul_lo_u32 / two v_mad_u64_u32 per tile in a VALU-bound kernel).  Only a partial last tile
-  // recomputes its addresses, to clamp the rows past lk onto the last key.
-  const half_t* kp[IP];
-  const half_t* vp[IP];
-#pragma unroll
-  for (int i = 0; i < IP; ++i) {
-    const int row = 8 * (wave_u * IP + i) + sr;
-    const int key = row < p.lk ? row : p.lk - 1;
-    kp[i] = kbase + (int64_t)key * p.k_sl + k_chunk_swz(row, sp) * 8;
-    vp[i] = vbase + (int64_t)key * p.k_sl + v_chunk_swz(row, sp) * 8;
-  }
-  const int64_t tile_stride = (int64_t)KT * p.k_sl;
-  const bool ragged = (p.lk % KT) != 0;
-  auto issue_tile = [&](int kt, int buf) {
-    const bool clamp = ragged && kt == nt - 1 && kt > 0;  // (tile 0 was clamped when the pointers were built)
-#pragma unroll
-    for (int i = 0; i < IP; ++i) {
-      const unsigned dst = smem_base + buf * BUF_BYTES + 8 * (wave_u * IP + i) * 128;
-      if (clamp) {
-        const int row = 8 * (wave_u * IP + i) + sr;
-        int key = kt * KT + row;
-        if (key >= p.lk) key = p.lk - 1;
-        const int64_t roff = (int64_t)key * p.k_sl;
-        glds16_raw(kbase + roff + k_chunk_swz(row, sp) * 8, dst);
-        glds16_raw(vbase + roff + v_chunk_swz(row, sp) * 8, dst + KT * 128);
-      } else {
-        glds16_raw(kp[i], dst);
-        glds16_raw(vp[i], dst + KT * 128);
-      }
-      kp[i] += tile_stride;
-      vp[i] += tile_stride;
-    }
-  };
+  Ring ring(kbase, vbase, p.k_sl, p.lk, smem, lane, wave);
 
   const int g16 = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, p4 = i16 & 3;
 
-  // One K/V tile.  MASKED (tail tile) is compile-time so that the tail mask costs nothing on full tiles.  The LDS buffer
-  // index is a RUN-TIME (wave-uniform) value: with the three buffers as three unrolled copies of this body hipcc gave the
-  // loop-carried O accumulators different registers in different copies and moved all 32 of them (16 v_mov_b64 behind two
-  // `s_nop 11` MFMA-result hazards) in every tile, and rebuilt the 16-register splat of -m_run; one body has one assignment.
+  // one K/V tile (the ring driver: attn_common.h)
   auto tile = [&](int buf, auto masked_c, int kt) {
     constexpr bool MASKED = decltype(masked_c)::value;
     const char* const lds_k = smem + buf * BUF_BYTES;
     const char* const lds_v = lds_k + KT * 128;
-    // tile kt+2 -> buffer (kt+2)%3, last read in iteration kt-1 (every wave passed that barrier)
-    const bool more2 = kt + 2 < nt && !(dbg & 1);
-    if (more2) issue_tile(kt + 2, buf == 0 ? 2 : buf - 1);  // (buf + 2) % 3
+    const bool more2 = attn_ring_prefetch(kt, nt, buf, !(dbg & 1), ring);
 
     // ---- S^T = K Q^T ----
     f32x16 sc[KB];
@@ -363,27 +269,9 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_kernel(AttnArgs p) {
       }
     }
     __builtin_amdgcn_s_setprio(0);
-    // ---- stage tile kt+1 into the other buffer (its last readers passed the previous barrier) ----
-    // tile kt+1 (issued one iteration ago) must have landed; tile kt+2's G instructions may fly on
-    if (more2) wait_vm<G>();
-    else wait_vm<0>();
-    __syncthreads();
+    attn_ring_arrive<Ring::G>(more2);
   };
-
-  issue_tile(0, 0);
-  if (nt > 1) {
-    issue_tile(1, 1);
-    wait_vm<G>();
-  } else {
-    wait_vm<0>();
-  }
-  // Retire the Q loads HERE as far as hipcc's wait-count bookkeeping is concerned.  Otherwise they are
-  // "possibly pending" at the loop header (merged over the back-edge), the compiler guards the first
-  // use of qf[0..3] in EVERY tile with s_waitcnt vmcnt(3)..vmcnt(0), and that vmcnt(0) drains the
-  // LDS-DMA ring (which it cannot see: the DMAs are issued from inline asm) once per tile.
-#pragma unroll
-  for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(qf[s]));
-  __syncthreads();
+  attn_ring_start<Ring::G>(nt, ring, qf);
   const int nfull = p.lk / KT;  // tiles that need no mask (the ragged tail tile, if any, is the last one)
   int buf = 0;                  // buffer index == tile % 3
   for (int kt = 0; kt < nfull; ++kt) {
@@ -394,34 +282,10 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_kernel(AttnArgs p) {
 
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_tot;
-  // ---- epilogue: O through LDS so that every global store is a full 128-byte row ----
-  // (per-lane 8-byte stores at a row stride touch 32 lines per instruction and amplify HBM writes;
-  // profiles/r01_traffic.json).  Each wave owns a 32-row x 128-byte image in the (now idle) K/V
-  // buffers; 16-byte chunk c of row r sits at c ^ (r & 7).
   __syncthreads();  // every wave is done reading K/V tiles
   char* const ow = smem + wave * (32 * 128);
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      half4_t h;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) h[r] = (half_t)(acc_o[db][4 * t + r] * inv);
-      const int d0 = 32 * db + 8 * t + 4 * hh;          // first of 4 consecutive head dims
-      const int chunk = d0 >> 3, piece = (d0 >> 2) & 1;  // 16-byte chunk, 8-byte half
-      *(half4_t*)(ow + qi * 128 + ((chunk ^ (qi & 7)) << 4) + (piece << 3)) = h;
-    }
-  // same wave reads back its own image: no workgroup barrier needed, only the LDS round trip
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  const int q0 = qb * (32 * NW) + wave * 32;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = 8 * i + (lane >> 3), pchunk = lane & 7;
-    const uint4 v = *(const uint4*)(ow + row * 128 + (pchunk << 4));
-    const int lchunk = pchunk ^ (row & 7);
-    if (q0 + row < p.lq) *(uint4*)(obase + (int64_t)(q0 + row) * p.o_sl + lchunk * 8) = v;
-  }
+  attn_stage_o32(ow, qi, hh, acc_o, inv);
+  attn_store_rows<4>(ow, obase, p.o_sl, qb * (32 * NW) + wave * 32, p.lq, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -431,8 +295,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_kernel(AttnArgs p) {
 // Per query that is half the LDS fragment reads, half the K/V LDS-DMA bytes and instructions (a workgroup's tile serves 256
 // queries) and half the per-tile bookkeeping of attn_kernel -- the components whose costs ADD UP there (ablations of
 // the pipelined kernel).  Same LDS ring, operand layouts, online-softmax arithmetic and rounding as
-// attn_kernel<4, 64, true, false, true>; one loop body with a run-time buffer index, running source pointers, half-wave maximum
-// by v_permlane32_swap (as there).
+// attn_kernel<4, 64, true, false, true> (ring and driver: attn_common.h); half-wave maximum by v_permlane32_swap (as there).
 template <int KT, bool SPLIT = false>
 __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
   constexpr int NW = 4, QB = 2, KB = KT / 32;
@@ -440,42 +303,20 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
   // Workgroups of one (batch, head, split) are adjacent in the launch order (they stream the same K/V range through one L2).
   __shared__ __attribute__((aligned(16))) char smem[3 * 2 * KT * 128];
   constexpr int BUF_BYTES = 2 * KT * 128;
-  constexpr int IP = KT / 8 / NW;
-  constexpr int G = 2 * IP;
+  typedef AttnRing<KT, NW, BUF_BYTES, v_chunk_swz> Ring;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int qi = lane & 31, hh = lane >> 5;
 
-  int bid;
-  {
-    const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = blockIdx.x & 7;
-    bid = ((x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (blockIdx.x >> 3);
-  }
-  const int qb = bid % p.qblocks;
-  bid /= p.qblocks;
-  int ksp = 0;
-  if (SPLIT) {
-    ksp = bid % p.nsplit;
-    bid /= p.nsplit;
-  }
-  const int head = bid % p.heads;
-  const int batch = bid / p.heads;
-  const int b0 = batch / p.nb1, b1 = batch - b0 * p.nb1;
-  // this workgroup's key range [key0, key0 + lk): the whole sequence, or the split's run of whole tiles
-  int key0 = 0, lk = p.lk;
-  if (SPLIT) {
-    const int nt_all = (p.lk + KT - 1) / KT, tps = (nt_all + p.nsplit - 1) / p.nsplit;
-    key0 = ksp * tps * KT;
-    const int key1 = (ksp + 1) * tps * KT < p.lk ? (ksp + 1) * tps * KT : p.lk;
-    lk = key1 - key0;  // > 0: the host only splits when every split gets at least one tile
-  }
-
-  const half_t* const qbase = p.q + b0 * p.q_sb0 + b1 * p.q_sb1 + head * 64;
-  const half_t* const kbase = p.k + b0 * p.k_sb0 + b1 * p.k_sb1 + head * 64 + (int64_t)key0 * p.k_sl;
-  const half_t* const vbase = p.v + b0 * p.k_sb0 + b1 * p.k_sb1 + head * 64 + (int64_t)key0 * p.k_sl;
-  half_t* const obase = p.out + b0 * p.o_sb0 + b1 * p.o_sb1 + head * 64;
+  AttnWg w;
+  attn_decode<SPLIT>(p, KT, w);
+  const int qb = w.qb, lk = w.lk;
+  const half_t* const qbase = attn_q_base(p, w);
+  const half_t* const kbase = attn_kv_base(p, w, p.k);
+  const half_t* const vbase = attn_kv_base(p, w, p.v);
+  half_t* const obase = attn_o_base(p, w);
 
   half8_t qf[QB][4];
 #pragma unroll
@@ -509,41 +350,7 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
   constexpr float P_SUM_BOUND = 16384.0f;  // a lane's partial row sum at or above 2^14: look at the maximum, rescale (see the tile body)
 
   const int nt = (lk + KT - 1) / KT;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  const unsigned smem_base =
-      __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-  const int sr = lane >> 3, sp = lane & 7;
-  const half_t* kp[IP];
-  const half_t* vp[IP];
-#pragma unroll
-  for (int i = 0; i < IP; ++i) {
-    const int row = 8 * (wave_u * IP + i) + sr;
-    const int key = row < lk ? row : lk - 1;
-    kp[i] = kbase + (int64_t)key * p.k_sl + k_chunk_swz(row, sp) * 8;
-    vp[i] = vbase + (int64_t)key * p.k_sl + v_chunk_swz(row, sp) * 8;
-  }
-  const int64_t tile_stride = (int64_t)KT * p.k_sl;
-  const bool ragged = (lk % KT) != 0;
-  auto issue_tile = [&](int kt, int buf) {  // tiles are issued strictly in order 0, 1, 2, ...
-    const bool clamp = ragged && kt == nt - 1 && kt > 0;
-#pragma unroll
-    for (int i = 0; i < IP; ++i) {
-      const unsigned dst = smem_base + buf * BUF_BYTES + 8 * (wave_u * IP + i) * 128;
-      if (clamp) {
-        const int row = 8 * (wave_u * IP + i) + sr;
-        int key = kt * KT + row;
-        if (key >= lk) key = lk - 1;
-        const int64_t roff = (int64_t)key * p.k_sl;
-        glds16_raw(kbase + roff + k_chunk_swz(row, sp) * 8, dst);
-        glds16_raw(vbase + roff + v_chunk_swz(row, sp) * 8, dst + KT * 128);
-      } else {
-        glds16_raw(kp[i], dst);
-        glds16_raw(vp[i], dst + KT * 128);
-      }
-      kp[i] += tile_stride;
-      vp[i] += tile_stride;
-    }
-  };
+  Ring ring(kbase, vbase, p.k_sl, lk, smem, lane, wave);
   const int g16 = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, p4 = i16 & 3;
   typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
   const fp16x2_t ones2 = {(__fp16)1.0f, (__fp16)1.0f};
@@ -552,8 +359,7 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
     constexpr bool MASKED = decltype(masked_c)::value;
     const char* const lds_k = smem + buf * BUF_BYTES;
     const char* const lds_v = lds_k + KT * 128;
-    const bool more2 = kt + 2 < nt;
-    if (more2) issue_tile(kt + 2, buf == 0 ? 2 : buf - 1);  // (buf + 2) % 3
+    const bool more2 = attn_ring_prefetch(kt, nt, buf, true, ring);
 
     if (active) {
     // ---- S^T = K Q^T for both query blocks off ONE K fragment; accumulators start at -m_run (q carries scale*log2e) ----
@@ -686,23 +492,9 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
         }
     __builtin_amdgcn_s_setprio(0);
     }  // active
-    if (more2) wait_vm<G>();
-    else wait_vm<0>();
-    __syncthreads();
+    attn_ring_arrive<Ring::G>(more2);
   };
-
-  issue_tile(0, 0);
-  if (nt > 1) {
-    issue_tile(1, 1);
-    wait_vm<G>();
-  } else {
-    wait_vm<0>();
-  }
-#pragma unroll
-  for (int c = 0; c < QB; ++c)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(qf[c][s]));  // retire the Q loads (see attn_kernel)
-  __syncthreads();
+  attn_ring_start<Ring::G>(nt, ring, qf);
   const int nfull = lk / KT;
   int buf = 0;
   for (int kt = 0; kt < nfull; ++kt) {
@@ -713,14 +505,13 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
 
   if constexpr (SPLIT) {
     // partial result: un-normalised O (relative to m_run) as fp32, 16 bytes per lane and (db, t), and (m_run, l) per query row
-    const int64_t rows_all = (int64_t)gridDim.x / (p.qblocks * p.nsplit) * p.lq;  // batch * heads * lq
-    const int64_t row_bh = ((int64_t)batch * p.heads + head) * p.lq;
+    const int64_t row0 = attn_part_row0(p, w);
 #pragma unroll
     for (int c = 0; c < QB; ++c) {
       const int qrow = qb * (32 * QB * NW) + wave * (32 * QB) + 32 * c + qi;
       const float l_tot = l_run[c] + __shfl_xor(l_run[c], 32, 64);
       if (qrow < p.lq) {
-        float* const po = p.part_o + ((int64_t)ksp * rows_all + row_bh + qrow) * 64;
+        float* const po = p.part_o + (row0 + qrow) * 64;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -728,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
             *(f32x4*)(po + 32 * db + 8 * t + 4 * hh) =
                 f32x4{acc_o[c][db][4 * t], acc_o[c][db][4 * t + 1], acc_o[c][db][4 * t + 2], acc_o[c][db][4 * t + 3]};
         if (hh == 0) {
-          float* const pm = p.part_ml + ((int64_t)ksp * rows_all + row_bh + qrow) * 2;
+          float* const pm = p.part_ml + (row0 + qrow) * 2;
           pm[0] = m_run[c];
           pm[1] = l_tot;
         }
@@ -737,37 +528,13 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
     return;
   }
   __syncthreads();  // every wave is done reading K/V tiles
+  char* const ow = smem + wave * QB * (32 * 128);  // the QB blocks' images are consecutive: 64 rows
 #pragma unroll
   for (int c = 0; c < QB; ++c) {
     const float l_tot = l_run[c] + __shfl_xor(l_run[c], 32, 64);
-    const float inv = 1.0f / l_tot;
-    char* const ow = smem + (wave * QB + c) * (32 * 128);
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        half4_t h;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) h[r] = (half_t)(acc_o[c][db][4 * t + r] * inv);
-        const int d0 = 32 * db + 8 * t + 4 * hh;
-        const int chunk = d0 >> 3, piece = (d0 >> 2) & 1;
-        *(half4_t*)(ow + qi * 128 + ((chunk ^ (qi & 7)) << 4) + (piece << 3)) = h;
-      }
+    attn_stage_o32(ow + c * (32 * 128), qi, hh, acc_o[c], 1.0f / l_tot);
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int c = 0; c < QB; ++c) {
-    const char* const ow = smem + (wave * QB + c) * (32 * 128);
-    const int q0 = qb * (32 * QB * NW) + wave * (32 * QB) + 32 * c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = 8 * i + (lane >> 3), pchunk = lane & 7;
-      const uint4 v = *(const uint4*)(ow + row * 128 + (pchunk << 4));
-      const int lchunk = pchunk ^ (row & 7);
-      if (q0 + row < p.lq) *(uint4*)(obase + (int64_t)(q0 + row) * p.o_sl + lchunk * 8) = v;
-    }
-  }
+  attn_store_rows<4 * QB>(ow, obase, p.o_sl, qb * (32 * QB * NW) + wave * (32 * QB), p.lq, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -791,8 +558,7 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
   constexpr int NW = 4, NQ = 4, NKB = KT / 16, NJ = KT / 32;
   __shared__ __attribute__((aligned(16))) char smem[3 * 2 * KT * 128];
   constexpr int BUF_BYTES = 2 * KT * 128;
-  constexpr int IP = KT / 8 / NW;
-  constexpr int G = 2 * IP;
+  typedef AttnRing<KT, NW, BUF_BYTES, v16_chunk_swz> Ring;
   static_assert(3 * BUF_BYTES >= NW * 64 * 128, "the output staging re-uses the ring");
 
   const int tid = threadIdx.x;
@@ -800,33 +566,13 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
   const int wave = tid >> 6;
   const int i16 = lane & 15, g = lane >> 4;
 
-  int bid;
-  {
-    const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = blockIdx.x & 7;
-    bid = ((x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (blockIdx.x >> 3);
-  }
-  const int qb = bid % p.qblocks;
-  bid /= p.qblocks;
-  int ksp = 0;
-  if (SPLIT) {
-    ksp = bid % p.nsplit;
-    bid /= p.nsplit;
-  }
-  const int head = bid % p.heads;
-  const int batch = bid / p.heads;
-  const int b0 = batch / p.nb1, b1 = batch - b0 * p.nb1;
-  int key0 = 0, lk = p.lk;
-  if (SPLIT) {
-    const int nt_all = (p.lk + KT - 1) / KT, tps = (nt_all + p.nsplit - 1) / p.nsplit;
-    key0 = ksp * tps * KT;
-    const int key1 = (ksp + 1) * tps * KT < p.lk ? (ksp + 1) * tps * KT : p.lk;
-    lk = key1 - key0;  // > 0: the host only splits when every split gets at least one tile
-  }
-
-  const half_t* const qbase = p.q + b0 * p.q_sb0 + b1 * p.q_sb1 + head * 64;
-  const half_t* const kbase = p.k + b0 * p.k_sb0 + b1 * p.k_sb1 + head * 64 + (int64_t)key0 * p.k_sl;
-  const half_t* const vbase = p.v + b0 * p.k_sb0 + b1 * p.k_sb1 + head * 64 + (int64_t)key0 * p.k_sl;
-  half_t* const obase = p.out + b0 * p.o_sb0 + b1 * p.o_sb1 + head * 64;
+  AttnWg w;
+  attn_decode<SPLIT>(p, KT, w);
+  const int qb = w.qb, lk = w.lk;
+  const half_t* const qbase = attn_q_base(p, w);
+  const half_t* const kbase = attn_kv_base(p, w, p.k);
+  const half_t* const vbase = attn_kv_base(p, w, p.v);
+  half_t* const obase = attn_o_base(p, w);
 
   const int wq0 = qb * (64 * NW) + wave * 64;  // first query row of this wave
   half8_t qf[NQ][2];
@@ -853,41 +599,7 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
   constexpr float P_SUM_BOUND = 16384.0f;  // a lane's partial row sum at or above 2^14: look at the maximum, rescale (as attn2_kernel)
 
   const int nt = (lk + KT - 1) / KT;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  const unsigned smem_base =
-      __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-  const int sr = lane >> 3, sp = lane & 7;
-  const half_t* kp[IP];
-  const half_t* vp[IP];
-#pragma unroll
-  for (int i = 0; i < IP; ++i) {
-    const int row = 8 * (wave_u * IP + i) + sr;
-    const int key = row < lk ? row : lk - 1;
-    kp[i] = kbase + (int64_t)key * p.k_sl + k_chunk_swz(row, sp) * 8;
-    vp[i] = vbase + (int64_t)key * p.k_sl + v16_chunk_swz(row, sp) * 8;
-  }
-  const int64_t tile_stride = (int64_t)KT * p.k_sl;
-  const bool ragged = (lk % KT) != 0;
-  auto issue_tile = [&](int kt, int buf) {  // tiles are issued strictly in order 0, 1, 2, ...
-    const bool clamp = ragged && kt == nt - 1 && kt > 0;
-#pragma unroll
-    for (int i = 0; i < IP; ++i) {
-      const unsigned dst = smem_base + buf * BUF_BYTES + 8 * (wave_u * IP + i) * 128;
-      if (clamp) {
-        const int row = 8 * (wave_u * IP + i) + sr;
-        int key = kt * KT + row;
-        if (key >= lk) key = lk - 1;
-        const int64_t roff = (int64_t)key * p.k_sl;
-        glds16_raw(kbase + roff + k_chunk_swz(row, sp) * 8, dst);
-        glds16_raw(vbase + roff + v16_chunk_swz(row, sp) * 8, dst + KT * 128);
-      } else {
-        glds16_raw(kp[i], dst);
-        glds16_raw(vp[i], dst + KT * 128);
-      }
-      kp[i] += tile_stride;
-      vp[i] += tile_stride;
-    }
-  };
+  Ring ring(kbase, vbase, p.k_sl, lk, smem, lane, wave);
   const int q4 = i16 >> 2, p4 = i16 & 3;
   typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
   const fp16x2_t ones2 = {(__fp16)1.0f, (__fp16)1.0f};
@@ -896,8 +608,7 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
     constexpr bool MASKED = decltype(masked_c)::value;
     const char* const lds_k = smem + buf * BUF_BYTES;
     const char* const lds_v = lds_k + KT * 128;
-    const bool more2 = kt + 2 < nt;
-    if (more2) issue_tile(kt + 2, buf == 0 ? 2 : buf - 1);  // (buf + 2) % 3
+    const bool more2 = attn_ring_prefetch(kt, nt, buf, true, ring);
 
     if (active) {
       // ---- S^T = K Q^T for the four query blocks off ONE K fragment; accumulators start at -m_run (q carries scale*log2e) ----
@@ -994,23 +705,9 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
 #pragma unroll
           for (int c = 0; c < NQ; ++c) acc_o[c][db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vfa[db][j], pf[c][j], acc_o[c][db], 0, 0, 0);
     }  // active
-    if (more2) wait_vm<G>();
-    else wait_vm<0>();
-    __syncthreads();
+    attn_ring_arrive<Ring::G>(more2);
   };
-
-  issue_tile(0, 0);
-  if (nt > 1) {
-    issue_tile(1, 1);
-    wait_vm<G>();
-  } else {
-    wait_vm<0>();
-  }
-#pragma unroll
-  for (int c = 0; c < NQ; ++c)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) asm volatile("" : "+v"(qf[c][ks]));  // retire the Q loads (see attn_kernel)
-  __syncthreads();
+  attn_ring_start<Ring::G>(nt, ring, qf);
   const int nfull = lk / KT;
   int buf = 0;
   for (int kt = 0; kt < nfull; ++kt) {
@@ -1028,51 +725,10 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
     l_tot[c] = l;
   }
   if constexpr (SPLIT) {
-    // partial result: un-normalised O (relative to m_run) as fp32, 16 bytes per lane and 16-dim block, and (m_run, l) per query row
-    const int64_t rows_all = (int64_t)gridDim.x / (p.qblocks * p.nsplit) * p.lq;  // batch * heads * lq
-    const int64_t row_bh = ((int64_t)batch * p.heads + head) * p.lq;
-#pragma unroll
-    for (int c = 0; c < NQ; ++c) {
-      const int qrow = wq0 + 16 * c + i16;
-      if (qrow < p.lq) {
-        float* const po = p.part_o + ((int64_t)ksp * rows_all + row_bh + qrow) * 64;
-#pragma unroll
-        for (int db = 0; db < 4; ++db) *(f32x4*)(po + 16 * db + 4 * g) = acc_o[c][db];
-        if (g == 0) {
-          float* const pm = p.part_ml + ((int64_t)ksp * rows_all + row_bh + qrow) * 2;
-          pm[0] = m_run[c];
-          pm[1] = l_tot[c];
-        }
-      }
-    }
+    attn_write_partial16(p, w, wq0, acc_o, m_run, l_tot, i16, g);
     return;
   }
-  __syncthreads();  // every wave is done reading K/V tiles
-  char* const ow = smem + wave * (64 * 128);
-#pragma unroll
-  for (int c = 0; c < NQ; ++c) {
-    const float inv = 1.0f / l_tot[c];
-    const int row = 16 * c + i16;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      half4_t h;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) h[r] = (half_t)(acc_o[c][db][r] * inv);
-      const int d0 = 16 * db + 4 * g;
-      const int chunk = d0 >> 3, piece = (d0 >> 2) & 1;
-      *(half4_t*)(ow + row * 128 + ((chunk ^ (row & 7)) << 4) + (piece << 3)) = h;
-    }
-  }
-  // same wave reads back its own image: no workgroup barrier needed, only the LDS round trip
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int row = 8 * i + (lane >> 3), pchunk = lane & 7;
-    const uint4 v = *(const uint4*)(ow + row * 128 + (pchunk << 4));
-    const int lchunk = pchunk ^ (row & 7);
-    if (wq0 + row < p.lq) *(uint4*)(obase + (int64_t)(wq0 + row) * p.o_sl + lchunk * 8) = v;
-  }
+  attn_store_o16(smem, obase, p.o_sl, wq0, p.lq, acc_o, l_tot, lane, wave, i16, g);
 }
 
 // Combine of the K/V-split partials: out = sum_i 2^(m_i - m*) O_i / sum_i 2^(m_i - m*) l_i, one thread per (row, 8 columns).
@@ -1124,10 +780,7 @@ int launch(const AttnArgs& a, int64_t batch, hipStream_t s, bool use_tr, bool pr
   AttnArgs args = a;
   args.qblocks = (a.lq + 32 * NW - 1) / (32 * NW);
   const int64_t nb = batch * a.heads * args.qblocks;
-  if (nb <= 0 || nb > 0x7fffffff) {
-    seva_set_error("attention: bad grid %lld", (long long)nb);
-    return SEVA_ERR_ARG;
-  }
+  if (int rc = attn_check_grid("attention", nb)) return rc;
   const dim3 grid((unsigned)nb), block(NW * 64);
   if (args.dbg && !pre)
     hipLaunchKernelGGL((attn_kernel<NW, KT, true, true, false>), grid, block, 0, s, args);
@@ -1142,7 +795,7 @@ int launch(const AttnArgs& a, int64_t batch, hipStream_t s, bool use_tr, bool pr
 
 }  // namespace
 
-// attn_combine_kernel for the K/V-split fp8 P.V kernel (attention_fp8.hip: same partial layout as attn16_kernel<64, true>)
+// attn_combine_kernel for the K/V-split fp8 P.V kernel (attention_fp8.hip: attn_write_partial16's layout, as attn16_kernel<64, true>)
 int seva_attn_combine_launch(const float* part_o, const float* part_ml, int nsplit, void* out, int64_t o_sb0, int64_t o_sb1,
                              int64_t o_sl, int nb1, int heads, int lq, int64_t rows_all, hipStream_t s) {
   AttnArgs a{};
@@ -1155,23 +808,11 @@ int seva_attn_combine_launch(const float* part_o, const float* part_ml, int nspl
 }
 
 extern "C" int seva_attention_f16(const seva_attn_desc* d, seva_stream_t stream) {
-  SEVA_REQUIRE(d != nullptr, "attention: null desc");
-  SEVA_REQUIRE(d->q && d->k && d->v && d->out, "attention: null pointer");
-  SEVA_REQUIRE(d->lq > 0 && d->lk > 0 && d->heads > 0 && d->nb0 > 0 && d->nb1 > 0,
-               "attention: empty problem lq=%d lk=%d heads=%d nb=%dx%d", d->lq, d->lk, d->heads,
-               d->nb0, d->nb1);
-  SEVA_REQUIRE(((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v | (uintptr_t)d->out) % 16 == 0,
-               "attention: pointers must be 16-byte aligned");
-  SEVA_REQUIRE((d->q_sb0 | d->q_sb1 | d->q_sl | d->k_sb0 | d->k_sb1 | d->k_sl | d->o_sb0 |
-                d->o_sb1 | d->o_sl) % 8 == 0,
-               "attention: strides must be multiples of 8 elements");
+  if (int rc = attn_check_desc(d, "attention", true)) return rc;
+  if (int rc = attn_check_ptrs("attention", {d->q, d->k, d->v, d->out})) return rc;
   AttnArgs a{};
-  a.q = (const half_t*)d->q; a.k = (const half_t*)d->k; a.v = (const half_t*)d->v;
-  a.out = (half_t*)d->out;
-  a.q_sb0 = d->q_sb0; a.q_sb1 = d->q_sb1; a.q_sl = d->q_sl;
-  a.k_sb0 = d->k_sb0; a.k_sb1 = d->k_sb1; a.k_sl = d->k_sl;
-  a.o_sb0 = d->o_sb0; a.o_sb1 = d->o_sb1; a.o_sl = d->o_sl;
-  a.nb1 = d->nb1; a.heads = d->heads; a.lq = d->lq; a.lk = d->lk;
+  attn_fill_base(a, d);
+  a.v = (const half_t*)d->v;
   a.scale_log2 = d->scale * 1.44269504088896340736f;
   a.dbg = g_seva_knobs.attn_dbg > 0 ? g_seva_knobs.attn_dbg : 0;
   const int64_t batch = (int64_t)d->nb0 * d->nb1;
@@ -1194,10 +835,7 @@ extern "C" int seva_attention_f16(const seva_attn_desc* d, seva_stream_t stream)
     AttnArgs args = a;
     args.qblocks = (a.lq + qrows - 1) / qrows;
     const int64_t nb = batch * a.heads * args.qblocks;
-    if (nb <= 0 || nb > 0x7fffffff) {
-      seva_set_error("attention: bad grid %lld", (long long)nb);
-      return SEVA_ERR_ARG;
-    }
+    if (int rc = attn_check_grid("attention", nb)) return rc;
     // K/V split (seva_attn_desc.split_ws): two workgroups per query block for long key sequences.  The factor is a function of
     // lk alone (never of the batch); knob attn_split: 0 = never, 2..4 = that factor wherever a workspace is given.
     int nsplit = d->lk >= 6144 ? 2 : 1;
@@ -1206,13 +844,7 @@ extern "C" int seva_attention_f16(const seva_attn_desc* d, seva_stream_t stream)
     while (nsplit >= 2 && (nt_all + nsplit - 1) / nsplit * (nsplit - 1) >= nt_all) --nsplit;  // every split gets >= 1 tile
     if (nsplit >= 2 && d->split_ws != nullptr) {
       const int64_t rows_all = batch * a.heads * (int64_t)a.lq;
-      SEVA_REQUIRE(d->split_ws_bytes >= nsplit * rows_all * 66 * 4 && (uintptr_t)d->split_ws % 16 == 0,
-                   "attention: split_ws too small (%lld bytes, need %lld) or misaligned", (long long)d->split_ws_bytes,
-                   (long long)(nsplit * rows_all * 66 * 4));
-      SEVA_REQUIRE(nb * nsplit <= 0x7fffffff && rows_all * 8 / 256 + 1 <= 0x7fffffff, "attention: split grid too large");
-      args.nsplit = nsplit;
-      args.part_o = d->split_ws;
-      args.part_ml = d->split_ws + (int64_t)nsplit * rows_all * 64;
+      if (int rc = attn_split_setup(args, d, "attention", nsplit, rows_all, nb)) return rc;
       if (k16) hipLaunchKernelGGL((attn16_kernel<64, true>), dim3((unsigned)(nb * nsplit)), dim3(256), 0, s, args);
       else hipLaunchKernelGGL((attn2_kernel<64, true>), dim3((unsigned)(nb * nsplit)), dim3(256), 0, s, args);
       int rc = seva_check_launch("attn16_kernel / attn2_kernel <split>");

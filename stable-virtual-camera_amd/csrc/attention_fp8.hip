@@ -18,8 +18,7 @@
 // the normal range; tests/test_attention_fp8_cpu.py: pv8_reference).  A rescale in a later part of a tile first accumulates the
 // earlier parts' packed P (a second, rare, set of MFMAs) -- they were packed against the old reference.
 // Every tiling decision is a function of lk and per-sample sizes only (K/V split from lk >= 6144, as seva_attention_f16).
-#include <type_traits>
-
+#include "attn_common.h"
 #include "attn_pv8.h"
 
 namespace {
@@ -69,41 +68,11 @@ __global__ __launch_bounds__(256) void quant_v_fp8_kernel(QuantArgs p) {
   p.v8s[id * PV8_SCALE_BYTES + pv8_scale_index(d, b)] = (uint8_t)(127 + e);
 }
 
-struct Pv8Args {
-  const half_t* q;
-  const half_t* k;
+struct Pv8Args : AttnBase {
   const uint8_t* v8;
   const uint8_t* v8s;
-  half_t* out;
-  int64_t q_sb0, q_sb1, q_sl;
-  int64_t k_sb0, k_sb1, k_sl;
-  int64_t o_sb0, o_sb1, o_sl;
-  int32_t nb1, heads, lq, lk, qblocks, nsteps;
-  float* part_o;   // K/V split: [nsplit][batch * heads * lq][64]   (attn16_kernel's layout, read by attn_combine_kernel)
-  float* part_ml;  //            [nsplit][batch * heads * lq][2]
-  int32_t nsplit;
+  int32_t nsteps;
 };
-
-// LDS-DMA from inline asm, ordered only by the counted waits and barriers (as attention.hip)
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_wave_base) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_wave_base)
-               : "memory");
-}
-__device__ __forceinline__ void glds4(const void* gsrc, unsigned lds_wave_base) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_wave_base)
-               : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ int k_swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }  // attn16_kernel's K tile swizzle
 
 // O^T block (16 dims x 16 queries) += V^T (16 dims x 128 keys, e4m3, E8M0 byte SEL of vscale) * P^T (128 keys x 16 queries, e4m3, unit scale)
 template <int SEL>
@@ -117,9 +86,9 @@ __global__ __launch_bounds__(256, 2) void pv8_kernel(Pv8Args p) {
   constexpr int K_BYTES = KT * 128, V_BYTES = PV8_VALUE_BYTES, S_BYTES = NW * PV8_SCALE_BYTES;  // every wave stages its own scale copy
   constexpr int BUF_BYTES = K_BYTES + V_BYTES + S_BYTES;
   __shared__ __attribute__((aligned(16))) char smem[3 * BUF_BYTES];
-  constexpr int IPK = KT / 8 / NW;            // 8-row K instructions per wave per tile
+  typedef AttnRing<KT, NW, BUF_BYTES, nullptr> KRing;  // the K rows; this kernel copies its own V image and scales
   constexpr int IPV = V_BYTES / 1024 / NW;    // 1 KB V instructions per wave per tile
-  constexpr int G = IPK + IPV + 1;            // LDS-DMA instructions per wave per tile (+ the scale dwords)
+  constexpr int G = KRing::G + IPV + 1;       // LDS-DMA instructions per wave per tile (+ the scale dwords)
   constexpr float RESCALE_THR = 8.0f;         // P <= 2^8 < 448
   // scores are computed, tested and packed in NPART parts of the tile (the registers of all 128 scores of four query blocks do not fit)
   constexpr int NPART = 4, KBP = KT / 16 / NPART;
@@ -130,35 +99,15 @@ __global__ __launch_bounds__(256, 2) void pv8_kernel(Pv8Args p) {
   const int wave = tid >> 6;
   const int i16 = lane & 15, g = lane >> 4;
 
-  int bid;
-  {
-    const int nb = gridDim.x, q = nb >> 3, r = nb & 7, x = blockIdx.x & 7;
-    bid = ((x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (blockIdx.x >> 3);
-  }
-  const int qb = bid % p.qblocks;
-  bid /= p.qblocks;
-  int ksp = 0;
-  if (SPLIT) {
-    ksp = bid % p.nsplit;
-    bid /= p.nsplit;
-  }
-  const int head = bid % p.heads;
-  const int batch = bid / p.heads;
-  const int b0 = batch / p.nb1, b1 = batch - b0 * p.nb1;
-  int key0 = 0, lk = p.lk;
-  if (SPLIT) {
-    const int nt_all = (p.lk + KT - 1) / KT, tps = (nt_all + p.nsplit - 1) / p.nsplit;
-    key0 = ksp * tps * KT;
-    const int key1 = (ksp + 1) * tps * KT < p.lk ? (ksp + 1) * tps * KT : p.lk;
-    lk = key1 - key0;  // > 0: the host only splits when every split gets at least one tile
-  }
-
-  const half_t* const qbase = p.q + b0 * p.q_sb0 + b1 * p.q_sb1 + head * 64;
-  const half_t* const kbase = p.k + b0 * p.k_sb0 + b1 * p.k_sb1 + head * 64 + (int64_t)key0 * p.k_sl;
-  const int64_t step0 = ((int64_t)batch * p.heads + head) * p.nsteps + key0 / KT;
+  AttnWg w;
+  attn_decode<SPLIT>(p, KT, w);
+  const int qb = w.qb, lk = w.lk;
+  const half_t* const qbase = attn_q_base(p, w);
+  const half_t* const kbase = attn_kv_base(p, w, p.k);
+  const int64_t step0 = ((int64_t)w.batch * p.heads + w.head) * p.nsteps + w.key0 / KT;
   const uint8_t* vp = p.v8 + step0 * V_BYTES + (wave * IPV) * 1024 + lane * 16;
   const uint8_t* sp8 = p.v8s + step0 * PV8_SCALE_BYTES + lane * 4;
-  half_t* const obase = p.out + b0 * p.o_sb0 + b1 * p.o_sb1 + head * 64;
+  half_t* const obase = attn_o_base(p, w);
 
   const int wq0 = qb * (64 * NW) + wave * 64;
   half8_t qf[NQ][2];
@@ -183,38 +132,13 @@ __global__ __launch_bounds__(256, 2) void pv8_kernel(Pv8Args p) {
   }
 
   const int nt = (lk + KT - 1) / KT;
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  const unsigned smem_base =
-      __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
-  const int sr = lane >> 3, sc8 = lane & 7;
-  const half_t* kp[IPK];
-#pragma unroll
-  for (int i = 0; i < IPK; ++i) {
-    const int row = 8 * (wave_u * IPK + i) + sr;
-    const int key = row < lk ? row : lk - 1;
-    kp[i] = kbase + (int64_t)key * p.k_sl + k_swz(row, sc8) * 8;
-  }
-  const int64_t tile_stride = (int64_t)KT * p.k_sl;
-  const bool ragged = (lk % KT) != 0;
+  KRing kring(kbase, nullptr, p.k_sl, lk, smem, lane, wave);
   auto issue_tile = [&](int kt, int buf) {  // tiles are issued strictly in order 0, 1, 2, ...
-    const bool clamp = ragged && kt == nt - 1 && kt > 0;
-    const unsigned base = smem_base + buf * BUF_BYTES;
+    kring(kt, buf);  // (rows past lk read the last key: their scores are masked; their V positions are zero in the image)
+    const unsigned base = kring.smem_base + buf * BUF_BYTES;
 #pragma unroll
-    for (int i = 0; i < IPK; ++i) {
-      const unsigned dst = base + 8 * (wave_u * IPK + i) * 128;
-      if (clamp) {  // rows past lk read the last key (their scores are masked; their V positions are zero in the image)
-        const int row = 8 * (wave_u * IPK + i) + sr;
-        int key = kt * KT + row;
-        if (key >= lk) key = lk - 1;
-        glds16(kbase + (int64_t)key * p.k_sl + k_swz(row, sc8) * 8, dst);
-      } else {
-        glds16(kp[i], dst);
-      }
-      kp[i] += tile_stride;
-    }
-#pragma unroll
-    for (int i = 0; i < IPV; ++i) glds16(vp + i * 1024, base + K_BYTES + (wave_u * IPV + i) * 1024);
-    glds4(sp8, base + K_BYTES + V_BYTES + wave_u * PV8_SCALE_BYTES);
+    for (int i = 0; i < IPV; ++i) glds16_raw(vp + i * 1024, base + K_BYTES + (kring.wave_u * IPV + i) * 1024);
+    glds4(sp8, base + K_BYTES + V_BYTES + kring.wave_u * PV8_SCALE_BYTES);
     vp += V_BYTES;
     sp8 += PV8_SCALE_BYTES;
   };
@@ -224,8 +148,7 @@ __global__ __launch_bounds__(256, 2) void pv8_kernel(Pv8Args p) {
     constexpr bool MASKED = decltype(masked_c)::value;
     const char* const lds_k = smem + buf * BUF_BYTES;
     const char* const lds_v = lds_k + K_BYTES;
-    const bool more2 = kt + 2 < nt;
-    if (more2) issue_tile(kt + 2, buf == 0 ? 2 : buf - 1);  // (buf + 2) % 3
+    const bool more2 = attn_ring_prefetch(kt, nt, buf, true, issue_tile);
 
     if (active) {
       // this lane's V^T row 16 db + i16, positions [32 g, 32 g + 32): two b128 reads
@@ -254,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void pv8_kernel(Pv8Args p) {
           const int krow = 16 * (KBP * h + kk) + i16;
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
-            const half8_t kf = *(const half8_t*)(lds_k + krow * 128 + (k_swz(krow, 4 * ks + g) << 4));
+            const half8_t kf = *(const half8_t*)(lds_k + krow * 128 + (k_chunk_swz(krow, 4 * ks + g) << 4));
 #pragma unroll
             for (int c = 0; c < NQ; ++c)
               sc[c][kk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[c][ks], ks == 0 ? neg_m[c] : sc[c][kk], 0, 0, 0);
@@ -322,11 +245,9 @@ __global__ __launch_bounds__(256, 2) void pv8_kernel(Pv8Args p) {
 #pragma unroll
       for (int c = 0; c < NQ; ++c) pv(c, vf, pf[c], vs);
     }  // active
-    if (more2) wait_vm<G>();
-    else wait_vm<0>();
-    __syncthreads();
+    attn_ring_arrive<G>(more2);
   };
-
+  // (attn_ring_start written out: through the function hipcc allocates this kernel three SGPRs fewer, and its registers are to stay)
   issue_tile(0, 0);
   if (nt > 1) {
     issue_tile(1, 1);
@@ -334,10 +255,7 @@ __global__ __launch_bounds__(256, 2) void pv8_kernel(Pv8Args p) {
   } else {
     wait_vm<0>();
   }
-#pragma unroll
-  for (int c = 0; c < NQ; ++c)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) asm volatile("" : "+v"(qf[c][ks]));  // retire the Q loads (see attention.hip)
+  attn_retire_loads(qf);
   __syncthreads();
   const int nfull = lk / KT;
   int buf = 0;
@@ -348,58 +266,14 @@ __global__ __launch_bounds__(256, 2) void pv8_kernel(Pv8Args p) {
   if (nfull < nt) tile(buf, std::true_type{}, nfull);
 
   // the ones-MFMA leaves the full row sum of query i16 in every register of every lane of it
+  float l_tot[NQ];
+#pragma unroll
+  for (int c = 0; c < NQ; ++c) l_tot[c] = acc_l[c][0];
   if constexpr (SPLIT) {
-    const int64_t rows_all = (int64_t)gridDim.x / (p.qblocks * p.nsplit) * p.lq;  // batch * heads * lq
-    const int64_t row_bh = ((int64_t)batch * p.heads + head) * p.lq;
-#pragma unroll
-    for (int c = 0; c < NQ; ++c) {
-      const int qrow = wq0 + 16 * c + i16;
-      if (qrow < p.lq) {
-        float* const po = p.part_o + ((int64_t)ksp * rows_all + row_bh + qrow) * 64;
-#pragma unroll
-        for (int db = 0; db < 4; ++db) *(f32x4*)(po + 16 * db + 4 * g) = acc_o[c][db];
-        if (g == 0) {
-          float* const pm = p.part_ml + ((int64_t)ksp * rows_all + row_bh + qrow) * 2;
-          pm[0] = m_run[c];
-          pm[1] = acc_l[c][0];
-        }
-      }
-    }
+    attn_write_partial16(p, w, wq0, acc_o, m_run, l_tot, i16, g);
     return;
   }
-  __syncthreads();  // every wave is done reading K/V tiles
-  char* const ow = smem + wave * (64 * 128);
-#pragma unroll
-  for (int c = 0; c < NQ; ++c) {
-    const float inv = 1.0f / acc_l[c][0];
-    const int row = 16 * c + i16;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      half4_t hv;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) hv[r] = (half_t)(acc_o[c][db][r] * inv);
-      const int d0 = 16 * db + 4 * g;
-      const int chunk = d0 >> 3, piece = (d0 >> 2) & 1;
-      *(half4_t*)(ow + row * 128 + ((chunk ^ (row & 7)) << 4) + (piece << 3)) = hv;
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): same wave reads back its own image
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int row = 8 * i + (lane >> 3), pchunk = lane & 7;
-    const uint4 v = *(const uint4*)(ow + row * 128 + (pchunk << 4));
-    const int lchunk = pchunk ^ (row & 7);
-    if (wq0 + row < p.lq) *(uint4*)(obase + (int64_t)(wq0 + row) * p.o_sl + lchunk * 8) = v;
-  }
-}
-
-int check_desc(const seva_attn_desc* d, const char* what) {
-  SEVA_REQUIRE(d != nullptr, "%s: null desc", what);
-  SEVA_REQUIRE(d->lq > 0 && d->lk > 0 && d->heads > 0 && d->nb0 > 0 && d->nb1 > 0,
-               "%s: empty problem lq=%d lk=%d heads=%d nb=%dx%d", what, d->lq, d->lk, d->heads, d->nb0, d->nb1);
-  SEVA_REQUIRE((d->k_sb0 | d->k_sb1 | d->k_sl) % 8 == 0, "%s: strides must be multiples of 8 elements", what);
-  return SEVA_OK;
+  attn_store_o16(smem, obase, p.o_sl, wq0, p.lq, acc_o, l_tot, lane, wave, i16, g);
 }
 
 }  // namespace
@@ -414,12 +288,11 @@ extern "C" int seva_attn_v_fp8_size(int32_t batch, int32_t heads, int32_t lk, in
 }
 
 extern "C" int seva_attn_quant_v_fp8(const seva_attn_desc* d, void* v8, uint8_t* v8_scale, seva_stream_t stream) {
-  if (int rc = check_desc(d, "attn_quant_v_fp8")) return rc;
-  SEVA_REQUIRE(d->v && v8 && v8_scale, "attn_quant_v_fp8: null pointer");
-  SEVA_REQUIRE(((uintptr_t)d->v | (uintptr_t)v8 | (uintptr_t)v8_scale) % 16 == 0, "attn_quant_v_fp8: pointers must be 16-byte aligned");
+  if (int rc = attn_check_desc(d, "attn_quant_v_fp8", false)) return rc;
+  if (int rc = attn_check_ptrs("attn_quant_v_fp8", {d->v, v8, v8_scale})) return rc;
   const int64_t batch = (int64_t)d->nb0 * d->nb1, nsteps = pv8_steps(d->lk);
   const int64_t nb = batch * d->heads * nsteps;
-  SEVA_REQUIRE(nb <= 0x7fffffff, "attn_quant_v_fp8: bad grid %lld", (long long)nb);
+  if (int rc = attn_check_grid("attn_quant_v_fp8", nb)) return rc;
   QuantArgs a{};
   a.v = (const half_t*)d->v;
   a.v8 = (uint8_t*)v8;
@@ -433,26 +306,17 @@ extern "C" int seva_attn_quant_v_fp8(const seva_attn_desc* d, void* v8, uint8_t*
 }
 
 extern "C" int seva_attention_pv8(const seva_attn_desc* d, const void* v8, const uint8_t* v8_scale, seva_stream_t stream) {
-  if (int rc = check_desc(d, "attention_pv8")) return rc;
-  SEVA_REQUIRE(d->q && d->k && v8 && v8_scale && d->out, "attention_pv8: null pointer");
-  SEVA_REQUIRE(((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)v8 | (uintptr_t)v8_scale | (uintptr_t)d->out) % 16 == 0,
-               "attention_pv8: pointers must be 16-byte aligned");
-  SEVA_REQUIRE((d->q_sb0 | d->q_sb1 | d->q_sl | d->o_sb0 | d->o_sb1 | d->o_sl) % 8 == 0,
-               "attention_pv8: strides must be multiples of 8 elements");
+  if (int rc = attn_check_desc(d, "attention_pv8", true)) return rc;
+  if (int rc = attn_check_ptrs("attention_pv8", {d->q, d->k, v8, v8_scale, d->out})) return rc;
   SEVA_REQUIRE(d->q_prescaled != 0, "attention_pv8: q must be pre-scaled by scale * log2(e) (q_prescaled)");
   const int64_t batch = (int64_t)d->nb0 * d->nb1;
   Pv8Args a{};
-  a.q = (const half_t*)d->q; a.k = (const half_t*)d->k;
+  attn_fill_base(a, d);
   a.v8 = (const uint8_t*)v8; a.v8s = v8_scale;
-  a.out = (half_t*)d->out;
-  a.q_sb0 = d->q_sb0; a.q_sb1 = d->q_sb1; a.q_sl = d->q_sl;
-  a.k_sb0 = d->k_sb0; a.k_sb1 = d->k_sb1; a.k_sl = d->k_sl;
-  a.o_sb0 = d->o_sb0; a.o_sb1 = d->o_sb1; a.o_sl = d->o_sl;
-  a.nb1 = d->nb1; a.heads = d->heads; a.lq = d->lq; a.lk = d->lk;
   a.qblocks = (d->lq + 255) / 256;
   a.nsteps = pv8_steps(d->lk);
   const int64_t nb = batch * d->heads * a.qblocks;
-  SEVA_REQUIRE(nb > 0 && nb <= 0x7fffffff, "attention_pv8: bad grid %lld", (long long)nb);
+  if (int rc = attn_check_grid("attention_pv8", nb)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const double flops = 4.0 * (double)batch * d->heads * (double)d->lq * (double)d->lk * 64.0;
   const double alg_bytes = (double)batch * d->heads * 64.0 * (2.0 * 2.0 * (double)d->lq + 3.0 * (double)d->lk);  // q, out f16; k f16, v e4m3
@@ -463,13 +327,7 @@ extern "C" int seva_attention_pv8(const seva_attn_desc* d, const void* v8, const
   while (nsplit >= 2 && (nt_all + nsplit - 1) / nsplit * (nsplit - 1) >= nt_all) --nsplit;  // every split gets >= 1 tile
   if (nsplit >= 2 && d->split_ws != nullptr) {
     const int64_t rows_all = batch * d->heads * (int64_t)d->lq;
-    SEVA_REQUIRE(d->split_ws_bytes >= nsplit * rows_all * 66 * 4 && (uintptr_t)d->split_ws % 16 == 0,
-                 "attention_pv8: split_ws too small (%lld bytes, need %lld) or misaligned", (long long)d->split_ws_bytes,
-                 (long long)(nsplit * rows_all * 66 * 4));
-    SEVA_REQUIRE(nb * nsplit <= 0x7fffffff && rows_all * 8 / 256 + 1 <= 0x7fffffff, "attention_pv8: split grid too large");
-    a.nsplit = nsplit;
-    a.part_o = d->split_ws;
-    a.part_ml = d->split_ws + (int64_t)nsplit * rows_all * 64;
+    if (int rc = attn_split_setup(a, d, "attention_pv8", nsplit, rows_all, nb)) return rc;
     hipLaunchKernelGGL((pv8_kernel<true>), dim3((unsigned)(nb * nsplit)), dim3(256), 0, s, a);
     if (int rc = seva_check_launch("pv8_kernel <split>")) return rc;
     return seva_attn_combine_launch(a.part_o, a.part_ml, nsplit, d->out, d->o_sb0, d->o_sb1, d->o_sl, d->nb1, d->heads, d->lq,

@@ -34,7 +34,3 @@ __host__ __device__ __forceinline__ int pv8_chunk_swz(int row, int chunk) { retu
 __host__ __device__ __forceinline__ int pv8_group_pos(int b, int j) { return 32 * (2 * (b & 1) + (j >> 4)) + 16 * (b >> 1) + (j & 15); }
 __host__ __device__ __forceinline__ int pv8_scale_index(int dim, int group) { return 4 * (16 * group + (dim & 15)) + (dim >> 4); }
 __host__ __device__ __forceinline__ int pv8_steps(int lk) { return (lk + PV8_STEP - 1) / PV8_STEP; }
-
-// attention.hip: the combine of attn16_kernel's K/V-split partials (attn_combine_kernel), for the split instantiation here
-int seva_attn_combine_launch(const float* part_o, const float* part_ml, int nsplit, void* out, int64_t o_sb0, int64_t o_sb1,
-                             int64_t o_sl, int nb1, int heads, int lq, int64_t rows_all, hipStream_t s);

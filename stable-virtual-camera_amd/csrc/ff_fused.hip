@@ -54,11 +54,6 @@ struct Ff8Args {
   const uint8_t* w2_exp;
 };
 
-template <int N>
-__device__ __forceinline__ void ff_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // glds16_raw with a wave-uniform 64-bit base in SGPRs and a 32-bit per-lane byte offset (saddr form): one VGPR per staging pass
 // instead of a 64-bit address pair (the e4m3 kernel runs at the register limit)
 static __device__ __forceinline__ void glds16_sv(const void* sbase, unsigned voff, unsigned lds_wave_base) {
@@ -239,18 +234,18 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_kernel(FfArgs p) {
   constexpr int NTILES = NCH * NK1;
   auto stage_w1_seq = [&](int g) { stage_w1(g % W1_RING, g / NK1, g % NK1); };
   auto wait_all_but = [&](int n) {  // wave-uniform count of the loads this wave issued during the current K-tile
-    if (n >= 3) ff_wait_vm<3>();
-    else if (n == 2) ff_wait_vm<2>();
-    else if (n == 1) ff_wait_vm<1>();
-    else ff_wait_vm<0>();
+    if (n >= 3) wait_vm<3>();
+    else if (n == 2) wait_vm<2>();
+    else if (n == 1) wait_vm<1>();
+    else wait_vm<0>();
   };
   __syncthreads();
   stage_w1_seq(0);
 #pragma unroll
   for (int part = 0; part < NK1; ++part) stage_w2_part(0, 0, part);
   if (NTILES > 1) stage_w1_seq(1);
-  if (NTILES > 1) ff_wait_vm<2>();  // tile 0 and the first W2 slice have landed; tile 1 (2 loads) flies on
-  else ff_wait_vm<0>();
+  if (NTILES > 1) wait_vm<2>();  // tile 0 and the first W2 slice have landed; tile 1 (2 loads) flies on
+  else wait_vm<0>();
   barrier_raw();
 
   int g = 0;  // W1 tile sequence number
@@ -545,17 +540,17 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_fp8_kernel(Ff8Args q) {
   constexpr int NTILES = NCH * NK1;
   auto stage_w1_seq = [&](int g) { stage_w1(g % W1_RING, g / NK1, g % NK1); };
   auto wait_all_but = [&](int n) {
-    if (n >= 3) ff_wait_vm<3>();
-    else if (n == 2) ff_wait_vm<2>();
-    else if (n == 1) ff_wait_vm<1>();
-    else ff_wait_vm<0>();
+    if (n >= 3) wait_vm<3>();
+    else if (n == 2) wait_vm<2>();
+    else if (n == 1) wait_vm<1>();
+    else wait_vm<0>();
   };
   __syncthreads();
   stage_w1_seq(0);
 #pragma unroll
   for (int part = 0; part < 2 * NK1; ++part) stage_w2_part(0, 0, part);
   stage_w1_seq(1);
-  ff_wait_vm<2>();  // tile 0 and the first W2 slice have landed; tile 1 (2 loads) flies on
+  wait_vm<2>();  // tile 0 and the first W2 slice have landed; tile 1 (2 loads) flies on
   barrier_raw();
 
   int g = 0;  // W1 tile sequence number

@@ -24,11 +24,6 @@ namespace {
 
 constexpr int BK = 64;  // fp16 elements per K-tile -> 128-byte LDS rows
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // DBGK: ablation instantiation (run-time p.dbg bits, SEVA_GEMM_DBG); the production one folds them away
 // PAIRED: weight-row -> MFMA-row assignment that gives a lane 8 consecutive features (f16-only outputs, GEGLU)
 // ASTAT (K <= 320, f16-only outputs): the A row-panel of the workgroup lives in REGISTERS.  Waves are

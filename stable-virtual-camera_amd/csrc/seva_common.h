@@ -76,6 +76,30 @@ __device__ __forceinline__ f32x4 first_read(f32x4 v) {
   return v;
 }
 #endif
+// LDS-DMA issued from inline asm: hipcc (ROCm 7.2) treats the builtin (gemm_common.h: glds16) as an LDS store that may alias
+// every later ds_read and protects it with `s_waitcnt vmcnt(0)`, which drains a multi-stage prefetch
+// ring at every K-tile.  Hidden in asm, the DMA is ordered only by the kernel's own counted
+// wait_vm<N>() + barrier.  M0 (LDS byte address of the wave's 1 KiB destination; 256 B for glds4) is written in
+// the same statement that consumes it and restored afterwards (compiler-reserved register).
+__device__ __forceinline__ void glds16_raw(const void* gsrc, unsigned lds_wave_base) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(gsrc), "s"(lds_wave_base)
+      : "memory");
+}
+__device__ __forceinline__ void glds4(const void* gsrc, unsigned lds_wave_base) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(gsrc), "s"(lds_wave_base)
+               : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
