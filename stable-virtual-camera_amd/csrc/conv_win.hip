@@ -18,11 +18,10 @@
 // and smaller at 160 rows), consecutive pixels of ONE image otherwise (72x72); an output row gets the same bits either way.  Per slab and 160 x 160 tile the LDS-DMA traffic drops from
 // 9 * (160 + 160) * 128 B = 360 KiB to 316 * 128 B + 9 * 160 * 128 B = 220 KiB; the weight tile is now the main stream.
 //
-// Everything else is gemm.hip's core: K-tile 64, 128-byte LDS rows, lane-linear LDS-DMA with the chunk swizzle
-// (chunk c of row r at c ^ ((r >> 1) & 7)) applied on the per-lane SOURCE address and on the fragment reads, weight
-// fragment as the MFMA A operand (features on the lane), fp32 residual loaded straight into the accumulators, GroupNorm
-// statistics from the epilogue.  The window's swizzle key is the WINDOW pixel index, so a tap shift that is not a multiple
-// of 16 leaves some 2-way bank conflicts on the A fragment reads (measured: see DESIGN.md section 4).
+// Everything else is the shared tile core (gemm_tile.h): K-tile 64, 128-byte LDS rows, lane-linear LDS-DMA with the natural chunk
+// swizzle, weight fragment as the MFMA A operand, fp32 residual loaded straight into the accumulators, GroupNorm statistics from the
+// epilogue.  The window's swizzle key is the WINDOW pixel index, so a tap shift that is not a multiple of 16 leaves some 2-way bank
+// conflicts on the A fragment reads (measured: see DESIGN.md section 4).
 //
 // Wide images (the VAE decoder's 144 .. 576 px rows: a linear window of BM pixels + two image rows does not fit LDS): 2-D tiles of
 // 16 output columns x BM / 16 output rows (TW = 16).  The window is the tile's (rows + 2) x 18 source pixels stored row after row
@@ -183,7 +182,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
   for (int i = 0; i < PPW; ++i) {
     const int pc = i * NW + wave;
     const int j = 8 * pc + sr;
-    const int chunk = sp ^ ((j >> 1) & 7);
+    const int chunk = sp ^ ((j >> 1) & 7);  // = src_chunk(sp, key_nat(j)), written out here and for the weight rows: four instantiations change registers otherwise
     bool ok;
     uint32_t pix;
     if constexpr (T2D && S2) {  // slot j = (wy, r): source row 2 t_y0 + wy, column 2 t_x0 + (r < 17 ? 2 r : 2 (r - 17) + 1)
@@ -254,7 +253,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
 #pragma unroll
   for (int s2 = 0; s2 < 2; ++s2) {
     const int rb = wn * WN + fr;
-    b_off[s2] = rb * 128 + (((4 * s2 + fg) ^ ((rb >> 1) & 7)) << 4);
+    b_off[s2] = rb * 128 + (((4 * s2 + fg) ^ ((rb >> 1) & 7)) << 4);  // (frag_off, written out like the window's below: see there)
   }
   // window pixel of row (16 i + fr) of the wave's tile: plain conv at tap (0, 0), the tap shift ky * Wp + kx is a uniform scalar;
   // UP: at ky = 0 / 1 / 2 with kx = 1, plus the pixel's column parity (the kx shift is (xpar - 1, 0, xpar))
@@ -291,7 +290,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
   const int nslab = p.cin / BK;
   fill_window(0, 0);
   stage_w(0, 0);
-  // FP8: E8M0 scale bytes of this lane's weight rows (MFMA row fr of block j), four blocks per word (plain byte loads, retired below)
+  // FP8: E8M0 scale bytes of this lane's weight rows (MFMA row fr of block j), four blocks per word (plain byte loads, retired below; this,
+  // the pins and the tap's product are written out: as shared helpers they change 11 / 9 / 4 instantiations)
   constexpr int NSC = (NJ + 3) / 4;
   int wsc[FP8 ? NSC : 1];
   if constexpr (FP8) {
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
   }
 
   f32x4 acc[MI][NJ];
-  if (!PH && p.residual) {  // the residual tile goes straight into the accumulators (clamped addresses; stores are guarded)
+  if (!PH && p.residual) {  // the residual tile goes straight into the accumulators (written out: as a shared helper 21 instantiations change registers)
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
       int64_t m = row_m(i);
@@ -325,9 +325,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
 #pragma unroll
       for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  drain_barrier();
   // retire the residual loads for hipcc's wait bookkeeping HERE: a load still "possibly pending" at the loop header gets a literal
   // vmcnt in front of its first use in every iteration, and that literal would also drain the LDS-DMA the compiler cannot see
 #pragma unroll
@@ -375,7 +373,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
           } else {
             j = a_base[i] + toff;
           }
-          const int addr = j * 128 + ((fg ^ ((j >> 1) & 7)) << 4);
+          const int addr = j * 128 + ((fg ^ ((j >> 1) & 7)) << 4);  // (frag_off written out: the 256-row phase kernel's tap loop loses an s_nop otherwise, and the 72 x 72, 960 -> 320 conv measured 0.8 % slower)
           af[0][i] = *(const half8_t*)(win + addr);
           af[1][i] = *(const half8_t*)(win + (addr ^ 64));
         }
@@ -413,15 +411,11 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
       }
       if constexpr (!DBW) {
         if (t == NT - 1 && more) {  // every wave has read the last tap's fragments: the window is free for the next slab
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
+          lds_barrier();
           fill_window(s + 1, 0);
         }
       }
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      drain_barrier();
       cur ^= 1;
     }
   }
@@ -467,10 +461,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
       const int64_t f = n0 + wn * WN + 16 * j + 4 * fg;
       if (!row_ok || f >= p.N) continue;
       if (p.out_f32) *(f32x4*)(p.out_f32 + mo * p.ldo32 + f) = v[j];
-      if (!PH && p.out_f16) {
-        half4_t h = {(half_t)v[j][0], (half_t)v[j][1], (half_t)v[j][2], (half_t)v[j][3]};
-        *(half4_t*)(p.out_f16 + m * p.ldo16 + f) = h;
-      }
+      if (!PH && p.out_f16) *(half4_t*)(p.out_f16 + m * p.ldo16 + f) = to_f16x4(v[j]);
     }
     if constexpr (O8) {
       // e4m3 output (saturating, RNE; gemm.hip's GEGLU out_f8): a lane holds 4 features of block j, its partner lane ^ 16 the next 4.  One
@@ -492,7 +483,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
     }
   }
   if constexpr (STATS) {
-    if (p.ch_stats != nullptr) {  // per 64-row block and channel: sum and sum of squares (gemm.hip, same association)
+    if (p.ch_stats != nullptr) {  // per 64-row block and channel: sum and sum of squares (gemm.hip, same association; written out: as a shared helper 14 instantiations change)
       // block number: linear tiles: 64 consecutive rows of the tensor; 2-D tiles: the wave's 4 tile rows x 16 pixels, numbered inside the image
       const int64_t mw = (int64_t)m0 + wm * WM;
       // PH: the wave's 64 source pixels are 64 OUTPUT pixels of one phase and one image (hw % 64 == 0): block 4 * (source block) + phase,

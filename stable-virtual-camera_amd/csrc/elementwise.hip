@@ -84,9 +84,8 @@ __global__ void cast_concat_f16_split_kernel(const float* __restrict__ x1, int c
     const int c = (int)(i - row * cq) * 4;
     const f32x4 v = (c < c1) ? *(const f32x4*)(x1 + row * c1 + c)
                              : *(const f32x4*)(x2 + row * c2 + (c - c1));
-    const half4_t h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-    const half4_t l = {(half_t)(v[0] - (float)h[0]), (half_t)(v[1] - (float)h[1]), (half_t)(v[2] - (float)h[2]),
-                       (half_t)(v[3] - (float)h[3])};
+    half4_t h, l;
+    split_f16x4(v, h, l);
     *(half4_t*)(out + row * 2 * C + c) = h;
     *(half4_t*)(out + row * 2 * C + C + c) = l;
   }

@@ -38,7 +38,7 @@ struct FfArgs {
   half_t* out_f16;
   int64_t M, lda, ldr, ldo32, ldo16;
   int32_t tiles_m;
-  // optional LayerNorm prologue (8-wave kernel): a = LayerNorm(ln_x) computed in registers, `a` unused
+  // optional LayerNorm prologue: a = LayerNorm(ln_x) computed in registers, `a` unused
   const float* ln_x;
   const float* ln_gamma;
   const float* ln_beta;
@@ -67,12 +67,12 @@ static __device__ __forceinline__ void glds16_sv(const void* sbase, unsigned vof
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// 8-wave variant: the same 128-row tile, but TWO waves per 32-row group (2 waves per SIMD -> one wave's LDS / barrier waits
-// and GEGLU VALU run under the other's MFMAs; the 4-wave kernel above measured 29 % MFMA-busy with 40 % of its wave time in
-// waits and 25 % in VALU, profiles/r02_pmc_ff_fused_4wave.txt).  Wave (mr, h): rows 32*mr .. +31; in stage 1 it takes the
+// 8 waves on the 128-row tile, TWO waves per 32-row group (2 waves per SIMD -> one wave's LDS / barrier waits and GEGLU VALU run
+// under the other's MFMAs).  Wave (mr, h): rows 32*mr .. +31; in stage 1 it takes the
 // chunk's GEGLU group q = h (64 of the 128 interleaved W1 rows -> 32 hidden features), the partner's 32 features arrive
 // through a 1 KiB-per-fragment LDS exchange; in stage 2 it owns output blocks h*NJ2/2 .. (half of the output row).
 // Registers per wave: A 80 + stage-2 accumulators 80 + stage-1 accumulators 32 + fragments: <= 256.
+// LDS rows, chunk swizzle (W1: the paired key, W2: the natural one) and the W1 row assignment are the shared tile core: gemm_tile.h.
 template <int C>
 __global__ __launch_bounds__(512, 2) void ff_fused8_kernel(FfArgs p) {
   constexpr int KS = C / 32, NK1 = C / 64, NJ2 = C / 16, NJH = NJ2 / 2, NCH = C / 16;
@@ -187,6 +187,7 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_kernel(FfArgs p) {
     for (int jj = 0; jj < NJH; ++jj) asm volatile("" : "+v"(acc2[i][jj]));
   }
 
+  // (W1: gemm_tile.h's paired key and WRowMap<4, true>, W2: the natural key; written out in both kernels: the helpers change 1 - 3 of 8 instantiations)
   auto w1_key = [](int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); };
   const half_t* w1_src[2];  // W1 tile: wave w stages rows 16w .. 16w+15 (2 passes)
 #pragma unroll
@@ -213,11 +214,6 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_kernel(FfArgs p) {
       const int i = part * W2_PER_KT + u;
       if (i < W2_PASSES) glds16_raw(w2_src[i & 1] + (int64_t)(i >> 1) * 16 * (4 * C) + hc * 64, dst + i * 1024);
     }
-  };
-  auto barrier_raw = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
   };
 
   int w1_off[2], w2_off[2];
@@ -246,7 +242,7 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_kernel(FfArgs p) {
   if (NTILES > 1) stage_w1_seq(1);
   if (NTILES > 1) wait_vm<2>();  // tile 0 and the first W2 slice have landed; tile 1 (2 loads) flies on
   else wait_vm<0>();
-  barrier_raw();
+  lds_barrier();
 
   int g = 0;  // W1 tile sequence number
   for (int hc = 0; hc < NCH; ++hc) {
@@ -283,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_kernel(FfArgs p) {
           for (int j = 0; j < 4; ++j)
             acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bfr[s][j], areg[i][2 * kt + s], acc1[i][j], 0, 0, 0);
       wait_all_but(issued);  // tile g + 1 (issued a K-tile ago) has landed; this K-tile's loads stay in flight
-      barrier_raw();
+      lds_barrier();
       ++g;
     }
     // GEGLU of this wave's 32 hidden features (group q = h of the chunk), handed to the partner through LDS
@@ -294,7 +290,7 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_kernel(FfArgs p) {
       *(half8_t*)(x_mine + i * 1024) = half8_t{(half_t)o0[0], (half_t)o0[1], (half_t)o0[2], (half_t)o0[3],
                                                (half_t)o1[0], (half_t)o1[1], (half_t)o1[2], (half_t)o1[3]};
     }
-    barrier_raw();  // both halves of every row group have published their 32 features
+    lds_barrier();  // both halves of every row group have published their 32 features
     half8_t hq[2][2];  // [k-step q = half that produced the features][token block i], both read back from LDS
 #pragma unroll
     for (int q = 0; q < 2; ++q)
@@ -312,7 +308,7 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_kernel(FfArgs p) {
         acc2[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1f, hq[1][i], acc2[i][jj], 0, 0, 0);
       }
     }
-    barrier_raw();  // W2 buffer (hc & 1) and the exchange slots are rewritten during the next chunk
+    lds_barrier();  // W2 buffer (hc & 1) and the exchange slots are rewritten during the next chunk
   }
 
 #pragma unroll
@@ -325,28 +321,9 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_kernel(FfArgs p) {
       const f32x4 v = acc2[i][jj] + first_read(*(const f32x4*)(p.b2 + f));
       if (!ok) continue;
       if (p.out_f32) *(f32x4*)(p.out_f32 + m * p.ldo32 + f) = v;
-      if (p.out_f16) {
-        const half4_t hh = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-        *(half4_t*)(p.out_f16 + m * p.ldo16 + f) = hh;
-      }
+      if (p.out_f16) *(half4_t*)(p.out_f16 + m * p.ldo16 + f) = to_f16x4(v);
     }
   }
-}
-
-
-template <int C>
-int ff_launch8(const FfArgs& a, hipStream_t s) {
-  constexpr int lds = 3 * 128 * 128 + 2 * C * 128 + 8 * C * 4 + 16 * 1024;
-  static std::atomic<uint64_t> attr_devs{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(attr_devs.load(std::memory_order_relaxed) & bit)) {
-    (void)hipFuncSetAttribute((const void*)ff_fused8_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_devs.fetch_or(bit, std::memory_order_relaxed);
-  }
-  hipLaunchKernelGGL((ff_fused8_kernel<C>), dim3((unsigned)a.tiles_m), dim3(512), lds, s, a);
-  return seva_check_launch("ff_fused8_kernel");
 }
 
 
@@ -520,11 +497,6 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_fp8_kernel(Ff8Args q) {
         glds16_sv((const uint8_t*)p.w2 + (int64_t)(i >> 1) * 16 * (4 * C) + pp * 128, w2_voff[i & 1], dst + i * 1024);
     }
   };
-  auto barrier_raw = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
 
   int w1_off[2], w2_off[2];
 #pragma unroll
@@ -551,7 +523,7 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_fp8_kernel(Ff8Args q) {
   for (int part = 0; part < 2 * NK1; ++part) stage_w2_part(0, 0, part);
   stage_w1_seq(1);
   wait_vm<2>();  // tile 0 and the first W2 slice have landed; tile 1 (2 loads) flies on
-  barrier_raw();
+  lds_barrier();
 
   int g = 0;  // W1 tile sequence number
   for (int pp = 0; pp < NP; ++pp) {
@@ -599,7 +571,7 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_fp8_kernel(Ff8Args q) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(acc1[i][j]));
         wait_all_but(issued);  // tile g + 1 (issued a K-tile ago) has landed; this K-tile's loads stay in flight
-        barrier_raw();
+        lds_barrier();
         ++g;
       }
       f32x4 bias[4];  // blocks 0, 1 = value e = 0, 1; blocks 2, 3 = gate
@@ -619,7 +591,7 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_fp8_kernel(Ff8Args q) {
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) *(v4i_t*)(x_mine + i * 1024) = hx[i];
-    barrier_raw();  // both halves of every row group have published the pair's features
+    lds_barrier();  // both halves of every row group have published the pair's features
     half8_t hq[2][2];  // [half q that produced the features = lo / hi 16 bytes of the operand][token block i]
 #pragma unroll
     for (int qq = 0; qq < 2; ++qq)
@@ -637,7 +609,7 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_fp8_kernel(Ff8Args q) {
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int jj = 0; jj < NJH; ++jj) asm volatile("" : "+v"(acc2[i][jj]));
-    barrier_raw();  // W2 buffer (pp & 1) and the exchange slots are rewritten during the next pair
+    lds_barrier();  // W2 buffer (pp & 1) and the exchange slots are rewritten during the next pair
   }
 
 #pragma unroll
@@ -651,61 +623,90 @@ __global__ __launch_bounds__(512, 2) void ff_fused8_fp8_kernel(Ff8Args q) {
       f32x4 v = acc2[i][jj] + first_read(*(const f32x4*)(p.b2 + f));
       if (p.residual) v += first_read(*(const f32x4*)(p.residual + m * p.ldr + f));
       if (p.out_f32) *(f32x4*)(p.out_f32 + m * p.ldo32 + f) = v;
-      if (p.out_f16) {
-        const half4_t hh = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-        *(half4_t*)(p.out_f16 + m * p.ldo16 + f) = hh;
-      }
+      if (p.out_f16) *(half4_t*)(p.out_f16 + m * p.ldo16 + f) = to_f16x4(v);
     }
   }
 }
 
-template <int C>
-int ff_launch8_fp8(const Ff8Args& a, hipStream_t s) {
-  constexpr int lds = 3 * 128 * 128 + 2 * C * 128 + 8 * C * 4 + (C / 16) * 32 * 4 + 16 * 1024;
-  static_assert(lds <= 160 * 1024, "LDS budget of one workgroup per CU");
-  static std::atomic<uint64_t> attr_devs{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(attr_devs.load(std::memory_order_relaxed) & bit)) {
-    (void)hipFuncSetAttribute((const void*)ff_fused8_fp8_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_devs.fetch_or(bit, std::memory_order_relaxed);
+// ---- host side: one set of checks, one argument builder, one work account and one launcher for both entry points ----
+// `pre`: "ff_fused" / "ff_fused_fp8", the prefix of every error text.  FP8: e4m3 operands (lda counts bytes; `a` is not read, so not
+// checked, under the LayerNorm prologue) and the two E8M0 scale vectors.
+template <bool FP8>
+int validate_ff(const seva_ff_desc* d, const char* pre) {
+  SEVA_REQUIRE(d != nullptr, "%s: null desc", pre);
+  SEVA_REQUIRE(d->C == 64 || d->C == 128 || d->C == 256 || d->C == 320, "%s: C=%d unsupported (64, 128, 256, 320)", pre, d->C);
+  if constexpr (FP8) {
+    SEVA_REQUIRE(d->a || d->ln_x, "%s: neither a nor ln_x given", pre);
+    SEVA_REQUIRE(d->w1 && d->b1 && d->w2 && d->b2, "%s: null operand", pre);
+    SEVA_REQUIRE(d->w1_exp && d->w2_exp, "%s: w1_exp and w2_exp (per-row E8M0 scale bytes) are required", pre);
+  } else {
+    SEVA_REQUIRE((d->a || d->ln_x) && d->w1 && d->b1 && d->w2 && d->b2, "%s: null operand", pre);
   }
-  hipLaunchKernelGGL((ff_fused8_fp8_kernel<C>), dim3((unsigned)a.f.tiles_m), dim3(512), lds, s, a);
-  return seva_check_launch("ff_fused8_fp8_kernel");
-}
-
-}  // namespace
-
-extern "C" int seva_ff_fused_f16(const seva_ff_desc* d, seva_stream_t stream) {
-  SEVA_REQUIRE(d != nullptr, "ff_fused: null desc");
-  SEVA_REQUIRE((d->a || d->ln_x) && d->w1 && d->b1 && d->w2 && d->b2, "ff_fused: null operand");
   SEVA_REQUIRE(!d->ln_x || (d->ln_gamma && d->ln_beta && d->ldx >= d->C && d->ldx % 4 == 0 &&
                             ((uintptr_t)d->ln_x | (uintptr_t)d->ln_gamma | (uintptr_t)d->ln_beta) % 16 == 0),
-               "ff_fused: LayerNorm prologue needs gamma, beta, a row pitch >= C (multiple of 4), 16-byte aligned pointers");
-  SEVA_REQUIRE(d->out_f32 || d->out_f16, "ff_fused: no output");
-  SEVA_REQUIRE(d->M > 0, "ff_fused: empty problem");
-  SEVA_REQUIRE(d->C == 64 || d->C == 128 || d->C == 256 || d->C == 320, "ff_fused: C=%d unsupported (64, 128, 256, 320)", d->C);
-  SEVA_REQUIRE(d->ln_x || (d->lda >= d->C && d->lda % 8 == 0), "ff_fused: lda=%lld invalid", (long long)d->lda);
+               "%s: LayerNorm prologue needs gamma, beta, a row pitch >= C (multiple of 4), 16-byte aligned pointers", pre);
+  SEVA_REQUIRE(d->out_f32 || d->out_f16, "%s: no output", pre);
+  SEVA_REQUIRE(d->M > 0, "%s: empty problem", pre);
+  if constexpr (FP8) {
+    SEVA_REQUIRE(d->ln_x || (d->lda >= d->C && d->lda % 16 == 0), "%s: lda=%lld invalid (bytes, >= C, multiple of 16)", pre, (long long)d->lda);
+  } else {
+    SEVA_REQUIRE(d->ln_x || (d->lda >= d->C && d->lda % 8 == 0), "%s: lda=%lld invalid", pre, (long long)d->lda);
+  }
   SEVA_REQUIRE((!d->residual || d->ldr % 4 == 0) && (!d->out_f32 || d->ldo32 % 4 == 0) && (!d->out_f16 || d->ldo16 % 4 == 0),
-               "ff_fused: row pitches must be multiples of 4");
-  SEVA_REQUIRE(((uintptr_t)d->a | (uintptr_t)d->w1 | (uintptr_t)d->b1 | (uintptr_t)d->w2 | (uintptr_t)d->b2 |
+               "%s: row pitches must be multiples of 4", pre);
+  SEVA_REQUIRE(((uintptr_t)(FP8 && d->ln_x ? nullptr : d->a) | (uintptr_t)d->w1 | (uintptr_t)d->b1 | (uintptr_t)d->w2 | (uintptr_t)d->b2 |
                 (uintptr_t)d->residual | (uintptr_t)d->out_f32 | (uintptr_t)d->out_f16) % 16 == 0,
-               "ff_fused: pointers must be 16-byte aligned");
+               "%s: pointers must be 16-byte aligned", pre);
+  SEVA_REQUIRE((d->M + 127) / 128 <= 0x7fffffff, "%s: too many rows", pre);
+  return 0;
+}
+
+FfArgs ff_args(const seva_ff_desc* d) {
   FfArgs a{};
   a.a = (const half_t*)d->a; a.w1 = (const half_t*)d->w1; a.b1 = d->b1; a.w2 = (const half_t*)d->w2; a.b2 = d->b2;
   a.residual = d->residual; a.out_f32 = d->out_f32; a.out_f16 = (half_t*)d->out_f16;
   a.M = d->M; a.lda = d->lda; a.ldr = d->ldr; a.ldo32 = d->ldo32; a.ldo16 = d->ldo16;
   a.ln_x = d->ln_x; a.ln_gamma = d->ln_gamma; a.ln_beta = d->ln_beta; a.ldx = d->ldx; a.ln_eps = d->ln_eps;
-  const int64_t tiles = (d->M + 127) / 128;
-  SEVA_REQUIRE(tiles <= 0x7fffffff, "ff_fused: too many rows");
-  a.tiles_m = (int)tiles;
+  a.tiles_m = (int)((d->M + 127) / 128);
+  return a;
+}
+
+// algorithmic FLOP and HBM bytes: rows read (fp32 under the LayerNorm prologue, else a_bytes per element) and written once, weights once
+struct FfWork { double flops, bytes; };
+FfWork ff_work(const seva_ff_desc* d, double a_bytes, double w_bytes) {
+  const double C = (double)d->C, M = (double)d->M;
+  return {2.0 * M * C * (8.0 * C) + 2.0 * M * (4.0 * C) * C,
+          M * C * ((d->ln_x ? 4.0 : a_bytes) + (d->residual ? 4.0 : 0.0) + (d->out_f32 ? 4.0 : 0.0) + (d->out_f16 ? 2.0 : 0.0)) + w_bytes};
+}
+
+template <class Args>
+int ff_launch(void (*kernel)(Args), const char* name, int lds, std::atomic<uint64_t>& attr_devs, const Args& a, int tiles_m, hipStream_t s) {
+  seva_max_dynamic_lds_once(attr_devs, lds, {(const void*)kernel});
+  hipLaunchKernelGGL(kernel, dim3((unsigned)tiles_m), dim3(512), lds, s, a);
+  return seva_check_launch(name);
+}
+template <int C>
+int ff_launch8(const FfArgs& a, hipStream_t s) {
+  static std::atomic<uint64_t> attr_devs{0};
+  return ff_launch(ff_fused8_kernel<C>, "ff_fused8_kernel", 3 * 128 * 128 + 2 * C * 128 + 8 * C * 4 + 16 * 1024, attr_devs, a, a.tiles_m, s);
+}
+template <int C>
+int ff_launch8_fp8(const Ff8Args& a, hipStream_t s) {
+  constexpr int lds = 3 * 128 * 128 + 2 * C * 128 + 8 * C * 4 + (C / 16) * 32 * 4 + 16 * 1024;
+  static_assert(lds <= 160 * 1024, "LDS budget of one workgroup per CU");
+  static std::atomic<uint64_t> attr_devs{0};
+  return ff_launch(ff_fused8_fp8_kernel<C>, "ff_fused8_fp8_kernel", lds, attr_devs, a, a.f.tiles_m, s);
+}
+
+}  // namespace
+
+extern "C" int seva_ff_fused_f16(const seva_ff_desc* d, seva_stream_t stream) {
+  if (const int rc = validate_ff<false>(d, "ff_fused")) return rc;
+  const FfArgs a = ff_args(d);
   hipStream_t s = (hipStream_t)stream;
   const double C = (double)d->C;
-  const double flops = 2.0 * (double)d->M * C * (8.0 * C) + 2.0 * (double)d->M * (4.0 * C) * C;
-  const double bytes = (double)d->M * C * ((d->ln_x ? 4.0 : 2.0) + (d->residual ? 4.0 : 0.0) + (d->out_f32 ? 4.0 : 0.0) + (d->out_f16 ? 2.0 : 0.0)) +
-                       2.0 * (8.0 * C * C + 4.0 * C * C);
-  SevaProfScope prof(0, flops, s, bytes);
+  const FfWork w = ff_work(d, 2.0, 2.0 * (8.0 * C * C + 4.0 * C * C));
+  SevaProfScope prof(0, w.flops, s, w.bytes);
   switch (d->C) {
     case 64: return ff_launch8<64>(a, s);
     case 128: return ff_launch8<128>(a, s);
@@ -717,38 +718,12 @@ extern "C" int seva_ff_fused_f16(const seva_ff_desc* d, seva_stream_t stream) {
 // e4m3 operands (ff_fp8.h): a [M][lda] bytes (columns C .. KP - 1 are not read) or the LayerNorm prologue; w1 [8C][KP], w2 [C][4C]
 // column-permuted, w1_exp [8C] / w2_exp [C] E8M0 row scales.
 extern "C" int seva_ff_fused_fp8(const seva_ff_desc* d, seva_stream_t stream) {
-  SEVA_REQUIRE(d != nullptr, "ff_fused_fp8: null desc");
-  SEVA_REQUIRE(d->C == 64 || d->C == 128 || d->C == 256 || d->C == 320, "ff_fused_fp8: C=%d unsupported (64, 128, 256, 320)", d->C);
-  SEVA_REQUIRE(d->a || d->ln_x, "ff_fused_fp8: neither a nor ln_x given");
-  SEVA_REQUIRE(d->w1 && d->b1 && d->w2 && d->b2, "ff_fused_fp8: null operand");
-  SEVA_REQUIRE(d->w1_exp && d->w2_exp, "ff_fused_fp8: w1_exp and w2_exp (per-row E8M0 scale bytes) are required");
-  SEVA_REQUIRE(!d->ln_x || (d->ln_gamma && d->ln_beta && d->ldx >= d->C && d->ldx % 4 == 0 &&
-                            ((uintptr_t)d->ln_x | (uintptr_t)d->ln_gamma | (uintptr_t)d->ln_beta) % 16 == 0),
-               "ff_fused_fp8: LayerNorm prologue needs gamma, beta, a row pitch >= C (multiple of 4), 16-byte aligned pointers");
-  SEVA_REQUIRE(d->out_f32 || d->out_f16, "ff_fused_fp8: no output");
-  SEVA_REQUIRE(d->M > 0, "ff_fused_fp8: empty problem");
-  SEVA_REQUIRE(d->ln_x || (d->lda >= d->C && d->lda % 16 == 0), "ff_fused_fp8: lda=%lld invalid (bytes, >= C, multiple of 16)",
-               (long long)d->lda);
-  SEVA_REQUIRE((!d->residual || d->ldr % 4 == 0) && (!d->out_f32 || d->ldo32 % 4 == 0) && (!d->out_f16 || d->ldo16 % 4 == 0),
-               "ff_fused_fp8: row pitches must be multiples of 4");
-  SEVA_REQUIRE(((uintptr_t)(d->ln_x ? nullptr : d->a) | (uintptr_t)d->w1 | (uintptr_t)d->b1 | (uintptr_t)d->w2 | (uintptr_t)d->b2 |
-                (uintptr_t)d->residual | (uintptr_t)d->out_f32 | (uintptr_t)d->out_f16) % 16 == 0,
-               "ff_fused_fp8: pointers must be 16-byte aligned");
-  Ff8Args a{};
-  a.f.a = (const half_t*)d->a; a.f.w1 = (const half_t*)d->w1; a.f.b1 = d->b1; a.f.w2 = (const half_t*)d->w2; a.f.b2 = d->b2;
-  a.f.residual = d->residual; a.f.out_f32 = d->out_f32; a.f.out_f16 = (half_t*)d->out_f16;
-  a.f.M = d->M; a.f.lda = d->lda; a.f.ldr = d->ldr; a.f.ldo32 = d->ldo32; a.f.ldo16 = d->ldo16;
-  a.f.ln_x = d->ln_x; a.f.ln_gamma = d->ln_gamma; a.f.ln_beta = d->ln_beta; a.f.ldx = d->ldx; a.f.ln_eps = d->ln_eps;
-  a.w1_exp = (const uint8_t*)d->w1_exp; a.w2_exp = (const uint8_t*)d->w2_exp;
-  const int64_t tiles = (d->M + 127) / 128;
-  SEVA_REQUIRE(tiles <= 0x7fffffff, "ff_fused_fp8: too many rows");
-  a.f.tiles_m = (int)tiles;
+  if (const int rc = validate_ff<true>(d, "ff_fused_fp8")) return rc;
+  Ff8Args a{ff_args(d), (const uint8_t*)d->w1_exp, (const uint8_t*)d->w2_exp};
   hipStream_t s = (hipStream_t)stream;
   const double C = (double)d->C;
-  const double flops = 2.0 * (double)d->M * C * (8.0 * C) + 2.0 * (double)d->M * (4.0 * C) * C;
-  const double bytes = (double)d->M * C * ((d->ln_x ? 4.0 : 1.0) + (d->residual ? 4.0 : 0.0) + (d->out_f32 ? 4.0 : 0.0) + (d->out_f16 ? 2.0 : 0.0)) +
-                       (8.0 * C * FF8_KP(d->C) + 4.0 * C * C);
-  SevaProfScope prof(0, flops, s, bytes);
+  const FfWork w = ff_work(d, 1.0, 8.0 * C * FF8_KP(d->C) + 4.0 * C * C);
+  SevaProfScope prof(0, w.flops, s, w.bytes);
   switch (d->C) {
     case 64: return ff_launch8_fp8<64>(a, s);
     case 128: return ff_launch8_fp8<128>(a, s);

@@ -2,14 +2,9 @@
 //
 //   out[m][n] = sum_k A[m][k] * W[n][k] (+bias) (+row_add) (+residual)      (seva_hip.h)
 //
-// Structure: BMxBN output tile per 256-thread workgroup (4 waves as 2x2), K-tile 64 (128-byte LDS
-// rows), both operands staged by LDS-DMA (`global_load_lds_dwordx4`, 1 KiB per wave-instruction)
-// into a double-buffered LDS ring, one barrier per K-tile.  The LDS image is lane-linear; the
-// bank-conflict swizzle (16-byte chunk c of row r sits at chunk c ^ ((r>>1)&7)) is applied on the
-// per-lane SOURCE address and again on the ds_read_b128 fragment reads.  MFMA is
-// v_mfma_f32_16x16x32_f16 with the WEIGHT fragment as the A operand, so each lane ends up with 4
-// consecutive output features of one row and the epilogue (bias, broadcast add, residual, GEGLU)
-// uses 8/16-byte vector accesses.
+// Structure: BMxBN output tile per 256-thread workgroup (4 waves as 2x2), K-tile 64, both operands staged by LDS-DMA into a
+// double-buffered LDS ring, one barrier per K-tile.  The LDS image, its chunk swizzle, the weight-row assignment and the tile
+// helpers are the shared tile core: gemm_tile.h.
 //
 // The conv variant gathers the A tile straight from the NHWC image (per-lane source address per
 // (ky,kx) tap, zero page for padding, optional stride 2 or nearest-2x upsampled source), so
@@ -42,9 +37,7 @@ constexpr int BK = 64;  // fp16 elements per K-tile -> 128-byte LDS rows
 // (residual-in-accumulator, GEGLU, column scale) is the f16 kernel's.
 // (mfma_f8: gemm_common.h)
 
-// NW: waves per workgroup.  4 (2 x 2 wave tiles, two workgroups per CU) everywhere in production; the experimental library also
-// instantiates 8 (2 x 4 wave tiles, ONE workgroup per CU): two N-sibling 128 x 160 tiles fused so that their A rows are staged once
-// (128 x 320: 0.0109 operand bytes per FLOP; same per-wave tile, registers and waves per SIMD as 128 x 160) -- measured slower.
+// NW: waves per workgroup: 4 (2 x 2 wave tiles, two workgroups per CU) in every instantiation.
 // SPLIT16 (seva_gemm_f16_split_out; its own instantiations, every other kernel stays as it is): out_f16 is a split-precision operand
 // [hi | lo] -- columns [0, NO) hold hi = f16(v), columns [NO, 2 NO) hold lo = f16(v - f32(hi)) of the fp32 epilogue value v, NO = the
 // epilogue's output width (N, GEGLU: N / 2).  Plain GEMM mode, the fp32-capable plain epilogue and the GEGLU epilogue only.
@@ -54,7 +47,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
   const int dbg = DBGK ? p.dbg : 0;
   static_assert(!SPLIT16 || (MODE == 0 && !DBGK && !ASTAT && !FP8 && !SPLITK && NW == 4 && PAIRED == (EPI == 1)),
                 "split-precision f16 output: plain GEMM mode, the unpaired plain epilogue or the GEGLU epilogue");
-  static_assert(NW == 4 || (NW == 8 && !DBGK && !PAIRED && !ASTAT && !FP8 && !SPLITK), "8 waves: plain fp32-output kernels only");
+  static_assert(NW == 4, "4 waves per workgroup");
   constexpr int WNW = NW / 2;  // waves along N
   constexpr int WM = ASTAT ? BM / 4 : BM / 2, WN = ASTAT ? BN : BN / WNW;  // per-wave tile
   constexpr int MI = WM / 16, NJ = WN / 16;
@@ -65,28 +58,14 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
   constexpr int KS_A = 10;  // ASTAT: k-steps of 32 held in registers (K <= 320)
   static_assert(!ASTAT || (PAIRED && MODE == 0 && !DBGK), "ASTAT rides on the ASYNC f16-only schedule");
   static_assert(EPI == 0 || (NJ % 4 == 0 && PAIRED), "GEGLU epilogue needs 64-wide groups, paired rows");
-  // Weight-row -> MFMA-row assignment.  D row r of a 16-row block lands in lane group fg = r >> 2, so
-  // with the natural order a lane owns 4 consecutive output features per block and the blocks of a
-  // lane are 16 features apart: 8-byte f16 stores, 32-byte fragments per token row.  Instead, blocks
-  // are taken in PAIRS (2p, 2p+1) over 32 weight rows and MFMA row r of block 2p+e reads tile row
-  //     32p + 8*(r>>2) + 4e + (r&3),
-  // so lane group fg owns features 32p + 8fg .. 8fg+7 across the pair: one 16-byte f16 store (two
-  // adjacent 16-byte f32 stores) per pair, i.e. 64 contiguous f16 bytes per token row and store.  Only
-  // the LDS read address changes; an odd last block (NJ = 5) keeps the natural order.  Measured: f16-out
-  // GEMMs 4-11 % faster, but f32 outputs 2-9 % SLOWER (each f32 store then writes 16-byte pieces with
-  // 16-byte holes), so PAIRED is only instantiated for f16-only outputs and the GEGLU epilogue.
-  // The B tile's chunk swizzle key follows the rows read together: pairs region bits {1,3,4} of the
-  // wave-relative row, natural region bits {1,2,3}.
-  constexpr int NJP = PAIRED ? (NJ & ~1) : 0;  // blocks handled in pairs
-  auto b_key = [](int row) {
-    const int rw = row % WN;  // wave-relative
-    return rw < NJP * 16 ? (((rw >> 1) & 1) | (((rw >> 3) & 3) << 1)) : ((rw >> 1) & 7);
-  };
-  // first output feature (relative to n0 + wn*WN) of block j for lane group fg
-  auto feat_of = [](int j, int fg) { return j < NJP ? 32 * (j >> 1) + 8 * fg + 4 * (j & 1) : 16 * j + 4 * fg; };
-
-  // FP8: weight row (relative to n0 + wn*WN) that MFMA row `r` of block j reads (the fragment-read row of b_frag_off)
-  auto wrow_of = [](int j, int r) { return j < NJP ? 32 * (j >> 1) + 4 * (j & 1) + 8 * (r >> 2) + (r & 3) : 16 * j + r; };
+  // Weight-row -> MFMA-row assignment (gemm_tile.h: WRowMap).  PAIRED: one 16-byte f16 store (two adjacent 16-byte f32 stores) per
+  // pair of blocks, i.e. 64 contiguous f16 bytes per token row and store; only the LDS read address changes.  Measured: f16-out GEMMs
+  // 4-11 % faster, but f32 outputs 2-9 % SLOWER (each f32 store then writes 16-byte pieces with 16-byte holes), so PAIRED is only
+  // instantiated for f16-only outputs and the GEGLU epilogue.
+  using RM = WRowMap<NJ, PAIRED>;
+  constexpr int NJP = RM::NJP;  // blocks handled in pairs
+  auto b_key = [](int row) { return RM::key(row % WN); };                  // (of a tile row)
+  auto feat_of = [](int j, int fg) { return RM::feat_of(j, fg); };        // first output feature (relative to n0 + wn*WN) of block j
   constexpr int NSC = (NJ + 3) / 4;  // packed scale words per lane
   // instantiations that can emit GroupNorm statistics (GemmArgs::ch_stats): a wave owns a 64-row block of the f32 output
   constexpr bool STATS_OK = EPI == 0 && !PAIRED && !ASTAT && !DBGK && WM == 64 && NJ >= 4;
@@ -155,7 +134,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
 #pragma unroll
   for (int i = 0; i < A_PASSES; ++i) {
     const int row = wave * (BM / NW) + 8 * i + sr;  // row inside the tile
-    const int q = sp ^ ((row >> 1) & 7);           // logical 16-B chunk this lane fetches
+    const int q = src_chunk(sp, key_nat(row));     // logical 16-B chunk this lane fetches
     a_q[i] = q;
     a_mask[i] = 0;
     int64_t m = m0 + row;
@@ -190,7 +169,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < B_PASSES; ++i) {
       const int row = wave * (BN / NW) + 8 * i + sr;
-      const int q = sp ^ b_key(row);
+      const int q = src_chunk(sp, b_key(row));
       int64_t n = (int64_t)tn * BN + row;
       if (n >= p.N) n = p.N - 1;
       if (dbg & 4) n = row;
@@ -311,11 +290,6 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
       else wait_vm<0>();
     }
   };
-  auto barrier_raw = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's fragment reads are done
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
 
   const int fr = lane & 15, fg = lane >> 4;  // fragment row / k-group
   const int nk = (int)(p.K / BK);
@@ -325,17 +299,13 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const int ra = wm * WM + fr;
-    a_off[s] = ra * 128 + (((4 * s + fg) ^ ((ra >> 1) & 7)) << 4);
-    // paired blocks: block 2p+e adds (32p + 4e) rows, which leaves the key bits untouched
-    const int rb = wn * WN + (PAIRED ? 8 * (fr >> 2) + (fr & 3) : fr);
-    b_off[s] = rb * 128 + (((4 * s + fg) ^ b_key(rb)) << 4);
+    a_off[s] = frag_off(ra, key_nat(ra), s, fg);
+    const int rb = wn * WN + RM::lane_row(fr);  // (a paired block's row offset leaves the key untouched: gemm_tile.h)
+    b_off[s] = frag_off(rb, b_key(rb), s, fg);
     const int rl = wn * WN + 16 * (NJ - 1) + fr;  // odd last block, natural order
-    b_off_last[s] = rl * 128 + (((4 * s + fg) ^ b_key(rl)) << 4);
+    b_off_last[s] = frag_off(rl, b_key(rl), s, fg);
   }
-  auto b_frag_off = [&](int s, int j) {
-    if (!PAIRED) return b_off[s] + j * (16 * 128);
-    return j < NJP ? b_off[s] + (32 * (j >> 1) + 4 * (j & 1)) * 128 : b_off_last[s];
-  };
+  auto b_frag_off = [&](int s, int j) { return !PAIRED || j < NJP ? b_off[s] + RM::block_row(j) * 128 : b_off_last[s]; };
 
   // ASTAT: this wave's 32 x K A fragments, loaded once (MFMA B-operand layout: lane (fr, fg) holds
   // row fr, k = 32*ks + 8*fg .. +7), then retired for hipcc's wait-count bookkeeping before the loop
@@ -352,10 +322,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
         areg[i][ks] = *(const half8_t*)(ap + kk);
       }
     }
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int ks = 0; ks < KS_A; ++ks) asm volatile("" : "+v"(areg[i][ks]));
+    pin_regs(areg);
   }
 
   set_b_tile(tn_begin);
@@ -375,7 +342,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
     // its 16 loads per lane are in flight together with this tile's stage-0 DMA and cost no extra
     // registers, instead of four load->wait->store round trips in the epilogue.  Addresses are
     // clamped (M and N tails); the stores are guarded.
-    if (EPI == 0 && p.residual && !(dbg & 32) && sk_half != 1) {
+    if (EPI == 0 && p.residual && !(dbg & 32) && sk_half != 1) {  // (written out: as a shared helper 37 instantiations change registers)
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
         int64_t m = m0 + wm * WM + 16 * i + fr;
@@ -397,7 +364,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
 
     if (ASYNC) {
       wait_counted(nk > 1, stores_flying);  // stage 0 (+ bias) landed; stage 1 and old stores fly on
-      barrier_raw();
+      lds_barrier();
     } else {
       __syncthreads();  // stage 0 of this tile (and the residual) has landed (vmcnt(0) + barrier)
     }
@@ -405,12 +372,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
     // (they rode in with stage 0, like the bias: no compiler-visible global load may sit in that loop); otherwise
     // plain global byte loads.
     int wsc[FP8 ? NSC : 1];
-    if constexpr (FP8) {
+    if constexpr (FP8) {  // (written out: as a shared helper the 64 x 160 paired e4m3 kernel takes 203 VGPRs for 201)
 #pragma unroll
       for (int w = 0; w < NSC; ++w) wsc[w] = 0;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        const int row = wn * WN + wrow_of(j, lane & 15);
+        const int row = wn * WN + RM::wrow_of(j, lane & 15);
         int b;
         if (ASYNC) {
           b = *(const unsigned char*)(wexp_slot + row);
@@ -480,7 +447,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
           for (int j = 0; j < NJ; ++j) asm volatile("" : "=v"(bf[s][j]));
         }
       }
-      if constexpr (FP8) {
+      if constexpr (FP8) {  // (written out: as a shared helper the 128 x 128 paired e4m3 K-loops change, 114 -> 110 instructions)
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -489,19 +456,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
         // the K-tile's scaled MFMAs stay in front of its barrier: hipcc otherwise sinks half of them behind it, their fragments with them
         // (conv_win.hip met the extreme form).  Same-box A/B of the fp8 step, two interleaved rounds: GEMM class 36.95 -> 36.14 ms
         // (profiles/r04_ab_fp8_mfma_pin.log); 128 x 160 e4m3 tiles then compile with 13 - 19 dwords of scratch and gain nothing more
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(acc[i][j]));
+        pin_regs(acc);
       } else
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         if (!(dbg & 2)) {
-#pragma unroll
-          for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[s][j], af[s][i], acc[i][j], 0, 0, 0);
+          mfma_step_f16(acc, af[s], bf[s]);
         } else {
 #pragma unroll
           for (int i = 0; i < MI; ++i) asm volatile("" ::"v"(af[s][i]));
@@ -511,12 +471,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
       }
       // the K-tile's MFMAs stay in front of its barrier: left alone, hipcc leaves 15 of the 50 (160 x 160) behind it, their fragments live across
       // the barrier.  Same-box A/B, three interleaved rounds of the step: GEMM class 43.57 -> 43.17 ms (profiles/r04_ab_gemm_mfma_pin.log)
-      if constexpr (!PAIRED && !FP8 && !DBGK) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(acc[i][j]));
-      }
+      if constexpr (!PAIRED && !FP8 && !DBGK) pin_regs(acc);
       }  // !ASTAT
       if (ASYNC) {
         // K-tile kt+1 must have landed.  It was issued before the old stores when kt == 0 (they stay
@@ -525,7 +480,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
           if (kt == 0) wait_counted(false, stores_flying);
           else wait_vm<0>();
         }
-        barrier_raw();
+        lds_barrier();
       } else {
         if (!(dbg & 16)) __syncthreads();
       }
@@ -552,6 +507,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     const char* const bias_cur = bias_slot + bias_par(tn);
+    // (GEGLU: NJP == NJ and the second form equals feat_of(j, fg); the ternary stays: without it three paired K-loops swap a branch's sense)
     auto bias_idx = [&](int j) {  // tile-relative float index of block j's 4 bias values for this lane
       return EPI == 0 ? wn * WN + feat_of(j, fg) : wn * WN + 64 * (j >> 2) + 8 * fg + 4 * (j & 1) + 32 * ((j >> 1) & 1);
     };
@@ -658,12 +614,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
                          (half_t)v1[0], (half_t)v1[1], (half_t)v1[2], (half_t)v1[3]};
             *(half8_t*)(p.out_f16 + ms * p.ldo16 + f) = h;
           } else {
-            half4_t h0 = {(half_t)v0[0], (half_t)v0[1], (half_t)v0[2], (half_t)v0[3]};
-            *(half4_t*)(p.out_f16 + ms * p.ldo16 + f) = h0;
-            if (pair && f + 4 < p.N) {
-              half4_t h1 = {(half_t)v1[0], (half_t)v1[1], (half_t)v1[2], (half_t)v1[3]};
-              *(half4_t*)(p.out_f16 + ms * p.ldo16 + f + 4) = h1;
-            }
+            *(half4_t*)(p.out_f16 + ms * p.ldo16 + f) = to_f16x4(v0);
+            if (pair && f + 4 < p.N) *(half4_t*)(p.out_f16 + ms * p.ldo16 + f + 4) = to_f16x4(v1);
           }
         }
       }
@@ -713,7 +665,6 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
           for (int j = 0; j < NJ; ++j) acc[i][j] = v[j];  // (a register rename) the statistics pass reads the final values
         }
         const int64_t ms = (dbg & 256) ? (m & 127) : m;  // ablation bit 256: stores land in an L2-resident region
-        [[maybe_unused]] const bool pitch16_ok = (p.ldo16 & 7) == 0;  // 16-byte f16 stores need an 8-element row pitch
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           const int64_t f = n0 + wn * WN + feat_of(j, fg);
@@ -724,28 +675,17 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
           }
           if (p.out_f32) *(f32x4*)(p.out_f32 + ms * p.ldo32 + f) = v[j];
           if constexpr (SPLIT16) {
-            const half4_t h = {(half_t)v[j][0], (half_t)v[j][1], (half_t)v[j][2], (half_t)v[j][3]};
-            const half4_t l = {(half_t)(v[j][0] - (float)h[0]), (half_t)(v[j][1] - (float)h[1]), (half_t)(v[j][2] - (float)h[2]),
-                               (half_t)(v[j][3] - (float)h[3])};
+            half4_t h, l;
+            split_f16x4(v[j], h, l);
             *(half4_t*)(p.out_f16 + ms * p.ldo16 + f) = h;
             *(half4_t*)(p.out_f16 + ms * p.ldo16 + p.N + f) = l;
-          } else if (p.out_f16) {
-            if (j + 1 < NJP && (j & 1) == 0 && f + 8 <= p.N && pitch16_ok) {
-              // both halves of the pair in range: one 16-byte store of 8 consecutive features
-              half8_t h = {(half_t)v[j][0],     (half_t)v[j][1],     (half_t)v[j][2],     (half_t)v[j][3],
-                           (half_t)v[j + 1][0], (half_t)v[j + 1][1], (half_t)v[j + 1][2], (half_t)v[j + 1][3]};
-              *(half8_t*)(p.out_f16 + ms * p.ldo16 + f) = h;
-            } else if (j < NJP && (j & 1) == 1 && f + 4 <= p.N && pitch16_ok) {
-              // second half of a pair: already written by the 16-byte store above
-            } else {
-              half4_t h = {(half_t)v[j][0], (half_t)v[j][1], (half_t)v[j][2], (half_t)v[j][3]};
-              *(half4_t*)(p.out_f16 + ms * p.ldo16 + f) = h;
-            }
+          } else if (p.out_f16) {  // (unpaired blocks here: the paired 16-byte store belongs to the f16-only epilogue above)
+            *(half4_t*)(p.out_f16 + ms * p.ldo16 + f) = to_f16x4(v[j]);
           }
         }
       }
       if constexpr (STATS_OK) {
-        if (p.ch_stats != nullptr) {
+        if (p.ch_stats != nullptr) {  // (written out: as a shared helper the 128 x 128 fp32 kernels change registers, 194 -> 202 VGPRs)
           const int64_t mw = m0 + wm * WM;  // first row of the wave's 64-row block
           float* const sp = p.ch_stats + (mw >> 6) * 2 * p.N;
 #pragma unroll
@@ -797,15 +737,10 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
             *(f32x4*)(p.out_f32 + m * p.ldo32 + fo + 4) = o1;
           }
           if (p.out_f16) {
-            half8_t h = {(half_t)o0[0], (half_t)o0[1], (half_t)o0[2], (half_t)o0[3],
-                         (half_t)o1[0], (half_t)o1[1], (half_t)o1[2], (half_t)o1[3]};
+            half8_t h, l;
+            split_f16x8(o0, o1, h, l);  // (l is dead code without SPLIT16)
             *(half8_t*)(p.out_f16 + m * p.ldo16 + fo) = h;
-            if constexpr (SPLIT16) {
-              const half8_t l = {(half_t)(o0[0] - (float)h[0]), (half_t)(o0[1] - (float)h[1]), (half_t)(o0[2] - (float)h[2]),
-                                 (half_t)(o0[3] - (float)h[3]), (half_t)(o1[0] - (float)h[4]), (half_t)(o1[1] - (float)h[5]),
-                                 (half_t)(o1[2] - (float)h[6]), (half_t)(o1[3] - (float)h[7])};
-              *(half8_t*)(p.out_f16 + m * p.ldo16 + p.N / 2 + fo) = l;
-            }
+            if constexpr (SPLIT16) *(half8_t*)(p.out_f16 + m * p.ldo16 + p.N / 2 + fo) = l;
           }
           if constexpr (FP8) {
             if (p.out_f8) {  // e4m3 hidden activations, saturating (8 consecutive features = one 8-byte store)

@@ -1,4 +1,4 @@
-// Shared by gemm.hip (the staged GEMM / per-tap conv kernel) and conv_win.hip (the window-staged 3x3 conv kernel).
+// Shared by gemm.hip (the staged GEMM / per-tap conv kernel), conv_win.hip (the window-staged 3x3 conv kernel) and ff_fused.hip.
 #pragma once
 #include <atomic>
 #include <initializer_list>
@@ -117,6 +117,7 @@ static __device__ __forceinline__ f32x4 mfma_f8(int j, half8_t w_lo, half8_t w_h
   }
 }
 
+#include "gemm_tile.h"  // the tile core of the three kernel families: swizzle keys, weight-row maps, tile helpers
 
 // The dynamic-LDS attribute is per device: one bit per device ordinal in `devs`, which the caller keeps per kernel instantiation (a
 // second GPU in the same process would otherwise launch 72-80 KB kernels without it).

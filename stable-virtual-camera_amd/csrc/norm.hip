@@ -306,20 +306,14 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(GnArgs p) {
           if (p.out) {
             *(half4_t*)(p.out + ((int64_t)n * p.hw + pix) * ldo + c0) = h;
             if (SPLIT && p.split_out) {
-              const half4_t l = {(half_t)(y4[0] - (float)h[0]), (half_t)(y4[1] - (float)h[1]), (half_t)(y4[2] - (float)h[2]),
-                                 (half_t)(y4[3] - (float)h[3])};
-              *(half4_t*)(p.out + ((int64_t)n * p.hw + pix) * ldo + C + c0) = l;
+              *(half4_t*)(p.out + ((int64_t)n * p.hw + pix) * ldo + C + c0) = lo_f16x4(f32x4{y4[0], y4[1], y4[2], y4[3]}, h);
             }
           }
           if (p.out8) *(int*)(p.out8 + ((int64_t)n * p.hw + pix) * p.ld8 + c0) = pack_fp8x4(y4[0], y4[1], y4[2], y4[3]);
           if (p.raw_out) {  // the un-normalised input as f16: A operand of the ResBlock's 1x1 skip conv
-            const half4_t hr = {(half_t)v[u][0], (half_t)v[u][1], (half_t)v[u][2], (half_t)v[u][3]};
+            const half4_t hr = to_f16x4(v[u]);
             *(half4_t*)(p.raw_out + ((int64_t)n * p.hw + pix) * ldr + c0) = hr;
-            if (SPLIT && p.split_raw) {
-              const half4_t lr = {(half_t)(v[u][0] - (float)hr[0]), (half_t)(v[u][1] - (float)hr[1]), (half_t)(v[u][2] - (float)hr[2]),
-                                  (half_t)(v[u][3] - (float)hr[3])};
-              *(half4_t*)(p.raw_out + ((int64_t)n * p.hw + pix) * ldr + C + c0) = lr;
-            }
+            if (SPLIT && p.split_raw) *(half4_t*)(p.raw_out + ((int64_t)n * p.hw + pix) * ldr + C + c0) = lo_f16x4(v[u], hr);
           }
         }
       }

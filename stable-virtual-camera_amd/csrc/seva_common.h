@@ -100,6 +100,34 @@ template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// workgroup barrier behind this wave's LDS traffic (fragment reads, ds writes); the counted vmcnt of a prefetch ring stays the caller's
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+// the same, and every VMEM operation of this wave (LDS-DMA included) has completed
+__device__ __forceinline__ void drain_barrier() {
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+// hi = f16(v), lo = f16(v - f32(hi)): the split-precision [hi | lo] operand of an fp32 value (4 and 8 wide)
+__device__ __forceinline__ half4_t to_f16x4(f32x4 v) { return half4_t{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]}; }
+__device__ __forceinline__ half4_t lo_f16x4(f32x4 v, half4_t hi) {  // (for a caller that already holds hi)
+  return half4_t{(half_t)(v[0] - (float)hi[0]), (half_t)(v[1] - (float)hi[1]), (half_t)(v[2] - (float)hi[2]), (half_t)(v[3] - (float)hi[3])};
+}
+__device__ __forceinline__ void split_f16x4(f32x4 v, half4_t& hi, half4_t& lo) {
+  hi = to_f16x4(v);
+  lo = lo_f16x4(v, hi);
+}
+__device__ __forceinline__ void split_f16x8(f32x4 a, f32x4 b, half8_t& hi, half8_t& lo) {
+  half4_t h0, l0, h1, l1;
+  split_f16x4(a, h0, l0);
+  split_f16x4(b, h1, l1);
+  hi = half8_t{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+  lo = half8_t{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
