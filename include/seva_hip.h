@@ -534,6 +534,61 @@ int seva_frame_metrics_size(int32_t n, int32_t H, int32_t W, int64_t* workspace_
 int seva_frame_metrics(const seva_metrics_desc* d, seva_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LPIPS v0.1 with the VGG-16 backbone (Zhang et al. 2018; spatial = False, normalize = False): the three operators around the 13
+ * convolutions, which are seva_gemm_f16 in conv mode writing out_f16.  New symbols and one new struct; no existing struct
+ * changes (ABI version unchanged).  All fp32 arithmetic below is rounded operation by operation (no FMA; divisions and square
+ * roots correctly rounded), in the stated order.
+ *
+ * Input preparation: the scaling layer's output as the first conv's operand.
+ *   src        n frames H x W x 3.  kind 0: uint8 [n][H][W][3], rows and pixels dense, images src_pitch_n BYTES apart; the
+ *              byte is u.  kind 1: fp32 [n][3][H][W] in [-1, 1], planes and rows dense, images src_pitch_n FLOATS apart;
+ *              u is the value after the rule of seva_rgb_to_u8 ((v + 1) / 2 * 255, clamp, truncate, NaN -> 0): both kinds
+ *              feed the tower the same integers, those seva_frame_metrics scores.
+ *   out_f16    [n][H][W][64] f16 dense.  Channel c < 3:  x = float(u) / 127.5f;  x = x - 1.0f;  x = x - shift[c];
+ *              x = x / scale[c];  one round-to-nearest-even to f16;  shift = (-.030f, -.088f, -.188f), scale = (.458f, .448f,
+ *              .450f).  Channels 3..63 are written as exactly zero (the padded K of the first conv). */
+int seva_lpips_prepare_f16(const void* src, int64_t src_pitch_n, int32_t kind, void* out_f16, int32_t n, int32_t H,
+                           int32_t W, seva_stream_t stream);
+/* ReLU, with the 2 x 2 / stride-2 max-pool where asked.  x: [n][h][w][c] f16 dense, c % 64 == 0 (a conv's out_f16).
+ *   relu_out   [n][h][w][c]: x > 0 ? x : 0, a NaN stays a NaN (torch.relu).  May be x itself (in place).
+ *   pool_out   NULL, or [n][h/2][w/2][c]: the maximum of relu_out over rows 2i, 2i+1 and columns 2j, 2j+1, a NaN in the
+ *              window gives a NaN (torch max_pool2d); floor semantics, an odd last row or column is dropped.  h, w >= 2.
+ * Nothing but the n*h*w*c (+ n*(h/2)*(w/2)*c) elements is written. */
+int seva_lpips_relu_pool_f16(const void* x, void* relu_out, void* pool_out, int32_t n, int32_t h, int32_t w, int32_t c,
+                             seva_stream_t stream);
+/* Layer distance: out[i] = sum over the hw pixels of pair i of d, the caller divides by hw.
+ *   fa, fb     features of the two frames of a pair, f16 [n][hw][C], pixels and channels dense, pairs *_pitch_n ELEMENTS
+ *              apart; C = 64, 128, 256 or 512.   w: fp32 [C], the layer's linear weights (>= 0).
+ *   per pixel  L = C / 8 lanes; lane j holds channels 8j .. 8j+7 of both vectors, widened to fp32 (a_i, b_i).
+ *                squares:   s = 0; for i = 0..7: s = s + a_i * a_i                                       (likewise for b)
+ *                butterfly: for o = L/2, L/4, .. 1: s = s + s[lane ^ o]        (every lane ends with the same value)
+ *                norm:      ra = 1.0f / (sqrt(s) + 1e-10f)        (one division per vector, not one per channel; likewise rb)
+ *                distance:  d = 0; for i = 0..7: df = a_i * ra - b_i * rb;  d = d + w_i * (df * df);  then the butterfly
+ *              The two vectors' expressions are the same operations in the same order and (x - y)^2 == (y - x)^2 exactly:
+ *              a frame against itself gives exactly 0.0, and swapping fa and fb changes no bit.
+ *   reduction  a pixel's fp32 d is widened to fp64.  One 256-thread workgroup per 256 consecutive pixels of a pair: with
+ *              G = 256 / L, thread g*L of the workgroup adds the d of pixels g, g + G, g + 2G, .. of the chunk in that order
+ *              (every other thread holds 0), the 256 values go through the binary tree v[t] += v[t + s], s = 128 .. 1, into
+ *              workspace[pair][chunk]; a second kernel, one workgroup per pair, has thread t add chunks t, t + 256, .. in
+ *              that order and applies the same tree.  No atomics: results repeat bit for bit and depend on nothing but
+ *              the pair itself -- not on n, on the pitches or on what surrounds out and the workspace.
+ * seva_lpips_layer_size: bytes of `workspace` (8-byte aligned; contents need not be kept between calls). */
+typedef struct seva_lpips_layer_desc {
+  const void* fa;           /* f16 [n][hw][C] */
+  const void* fb;
+  const float* w;           /* [C] */
+  double* out;              /* [n] */
+  void* workspace;
+  int64_t a_pitch_n;        /* f16 elements between pairs, >= hw*C, % 8 == 0 */
+  int64_t b_pitch_n;
+  int64_t workspace_bytes;
+  int64_t hw;
+  int32_t n, C;
+} seva_lpips_layer_desc;
+int seva_lpips_layer_size(int32_t n, int64_t hw, int64_t* workspace_bytes);
+int seva_lpips_layer(const seva_lpips_layer_desc* d, seva_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Benchmark / debugging knobs. The library reads its SEVA_* environment variables ONCE, when it is loaded (nothing
  * on the launch path calls getenv); a host changes a knob at run time with seva_set_knob (tests, tools).  Names:
  * gemm_chunks, gemm_dbg, gemm_stagger, gemm_bm, gemm_bn, gemm_astat, attn_dbg, attn_no_tr, attn_two, attn_split,

@@ -98,6 +98,14 @@ class MetricsDesc(C.Structure):
     ]
 
 
+class LpipsLayerDesc(C.Structure):
+    _fields_ = [
+        ("fa", c_void_p), ("fb", c_void_p), ("w", c_void_p), ("out", c_void_p), ("workspace", c_void_p),
+        ("a_pitch_n", c_int64), ("b_pitch_n", c_int64), ("workspace_bytes", c_int64), ("hw", c_int64),
+        ("n", c_int32), ("C", c_int32),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/seva_hip.h
 SYMBOLS = {
     "seva_last_error": (c_char_p, []),
@@ -149,6 +157,10 @@ SYMBOLS = {
     "seva_rgb_to_u8": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "seva_frame_metrics_size": (c_int, [c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "seva_frame_metrics": (c_int, [POINTER(MetricsDesc), c_void_p]),
+    "seva_lpips_prepare_f16": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "seva_lpips_relu_pool_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "seva_lpips_layer_size": (c_int, [c_int32, c_int64, POINTER(c_int64)]),
+    "seva_lpips_layer": (c_int, [POINTER(LpipsLayerDesc), c_void_p]),
     "seva_set_knob": (c_int, [c_char_p, c_int32]),
     "seva_get_knob": (c_int, [c_char_p, POINTER(c_int32)]),
     "seva_graph_begin": (c_int, [c_void_p]),

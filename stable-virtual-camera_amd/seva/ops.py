@@ -13,7 +13,7 @@ import ctypes as C
 import torch
 
 from . import _native as nv
-from ._native import AttnDesc, GemmDesc, GroupNormDesc, ImageDesc, MetricsDesc, check, ptr, require_cuda, stream_ptr
+from ._native import AttnDesc, GemmDesc, GroupNormDesc, ImageDesc, LpipsLayerDesc, MetricsDesc, check, ptr, require_cuda, stream_ptr
 
 F16, F32 = torch.float16, torch.float32
 U8 = torch.uint8  # e4m3 bytes travel as uint8 tensors (bit pattern of torch.float8_e4m3fn)
@@ -867,6 +867,68 @@ def frame_metrics(a: torch.Tensor, b: torch.Tensor, sse: torch.Tensor, ssim_sum:
     d.a_pitch_n, d.b_pitch_n, d.workspace_bytes = a.stride(0), b.stride(0), workspace.numel()
     d.n, d.H, d.W, d.ssim = n, H, W, int(ssim_sum is not None)
     check(_lib().seva_frame_metrics(C.byref(d), stream_ptr(a.device)), "seva_frame_metrics")
+
+
+# --- LPIPS (VGG-16): the operators around the 13 convs (csrc/lpips.hip; the contract is in include/seva_hip.h) ---------
+LPIPS_CPAD = 64  # channels of the prepared first-conv operand
+
+
+def lpips_prepare(x: torch.Tensor, out_f16: torch.Tensor) -> None:
+    """x: uint8 (n,H,W,3), images dense, any image pitch -- or fp32 (n,3,H,W) in [-1, 1], planes dense, any image pitch (taken
+    through the uint8 rule of `rgb_to_u8`) -> out_f16: (n,H,W,64) contiguous, the scaling layer's output in channels 0..2,
+    exact zeros above (seva_lpips_prepare_f16)."""
+    require_cuda(x, out_f16)
+    assert x.dim() == 4 and x.dtype in (U8, F32)
+    if x.dtype == U8:
+        n, H, W, c = x.shape
+        assert c == 3 and x.stride(3) == 1 and x.stride(2) == 3 and x.stride(1) == 3 * W, "uint8 frames: (n,H,W,3) with dense images"
+    else:
+        n, c, H, W = x.shape
+        assert c == 3 and x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W, "fp32 frames: (n,3,H,W) with dense planes"
+    assert out_f16.dtype == F16 and out_f16.shape == (n, H, W, LPIPS_CPAD) and out_f16.is_contiguous()
+    check(_lib().seva_lpips_prepare_f16(x.data_ptr(), x.stride(0), 0 if x.dtype == U8 else 1, out_f16.data_ptr(), n, H, W,
+                                        stream_ptr(x.device)), "seva_lpips_prepare_f16")
+
+
+def lpips_relu_pool(x: torch.Tensor, relu_out: torch.Tensor, pool_out: torch.Tensor | None = None) -> None:
+    """x: f16 (n,h,w,c) contiguous, c % 64 == 0 -> relu_out (n,h,w,c) = relu(x) (may be x itself) and, when given, pool_out
+    (n,h//2,w//2,c) = its 2 x 2 / stride-2 max-pool, floor; NaN -> NaN in both (seva_lpips_relu_pool_f16)."""
+    require_cuda(x, relu_out, pool_out)
+    assert x.dtype == F16 and x.dim() == 4 and x.is_contiguous()
+    n, h, w, c = x.shape
+    assert relu_out.dtype == F16 and relu_out.shape == x.shape and relu_out.is_contiguous()
+    assert pool_out is None or (pool_out.dtype == F16 and pool_out.shape == (n, h // 2, w // 2, c) and pool_out.is_contiguous())
+    check(_lib().seva_lpips_relu_pool_f16(x.data_ptr(), relu_out.data_ptr(), ptr(pool_out), n, h, w, c, stream_ptr(x.device)),
+          "seva_lpips_relu_pool_f16")
+
+
+def lpips_layer_workspace_numel(n: int, hw: int) -> int:
+    """uint8 elements of `lpips_layer(workspace=...)`: one fp64 partial per 256 pixels of every pair."""
+    size = C.c_int64()
+    check(_lib().seva_lpips_layer_size(int(n), int(hw), C.byref(size)), "seva_lpips_layer_size")
+    return size.value
+
+
+def lpips_layer(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor | None = None) -> None:
+    """fa, fb: f16 (n,hw,C) features of the two frames of each pair, pixels dense, any pair pitch (a multiple of 8), C in 64, 128,
+    256, 512; w: fp32 (C) -> out: fp64 (n), the sum over the pixels of sum_c w[c] (fa_c / |fa| - fb_c / |fb|)^2
+    (seva_lpips_layer).  workspace: uint8, `lpips_layer_workspace_numel` elements (None: allocated here)."""
+    require_cuda(fa, fb, w, out, workspace)
+    assert fa.dtype == fb.dtype == F16 and fa.dim() == 3 and fa.shape == fb.shape
+    n, hw, c = fa.shape
+    for x in (fa, fb):
+        assert x.stride(2) == 1 and x.stride(1) == c, "features: (n,hw,C) with dense pixels"
+    assert w.dtype == F32 and w.shape == (c,) and w.is_contiguous()
+    assert out.dtype == torch.float64 and out.shape == (n,) and out.is_contiguous()
+    need = lpips_layer_workspace_numel(n, hw)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=U8, device=fa.device)
+    assert workspace.dtype == U8 and workspace.is_contiguous() and workspace.numel() >= need, "lpips_layer workspace too small"
+    d = LpipsLayerDesc()
+    d.fa, d.fb, d.w, d.out, d.workspace = fa.data_ptr(), fb.data_ptr(), w.data_ptr(), out.data_ptr(), workspace.data_ptr()
+    d.a_pitch_n, d.b_pitch_n, d.workspace_bytes, d.hw = fa.stride(0), fb.stride(0), workspace.numel(), hw
+    d.n, d.C = n, c
+    check(_lib().seva_lpips_layer(C.byref(d), stream_ptr(fa.device)), "seva_lpips_layer")
 
 
 # --- benchmark / debugging knobs (read from SEVA_* once at library load; see include/seva_hip.h) ---------

@@ -34,7 +34,8 @@ own rule (eval.py:1248: mean CLIP embedding of the window's conditioning views) 
 
 One pass (`plan_views` / `run_views`, `run_scene(use_traj_prior=False)`): the reference's evaluation mode (eval.py:1472-1629,
 tasks `img2img` / `img2vid`) -- the first-pass half of the plan over EVERY non-input frame, no second pass; the same driver
-runs it.  `run_scene(targets=...)` scores the generated frames against held-out pictures (`seva.metrics`: PSNR / SSIM).
+runs it.  `run_scene(targets=...)` scores the generated frames against held-out pictures (`seva.metrics`: PSNR / SSIM, and LPIPS
+with `lpips=`).
 """
 
 from __future__ import annotations
@@ -423,7 +424,7 @@ def run_views(denoise_net: Callable, input_latents: torch.Tensor, c2ws: torch.Te
 
 def run_scene(denoise_net: Callable, ae, images: Sequence, c2ws: torch.Tensor, Ks: torch.Tensor, input_ids: Sequence[int], *,
               size=(576, 576), conditioner: Callable | None = None, clip_token: torch.Tensor | None = None,
-              use_traj_prior: bool = True, targets: dict | None = None, **run_trajectory_kwargs) -> dict:
+              use_traj_prior: bool = True, targets: dict | None = None, lpips=None, **run_trajectory_kwargs) -> dict:
     """Pictures + cameras in, uint8 frames out: `frames.load_img_and_K` per input picture (a path, a uint8 (h,w,3|4) array
     or tensor; covered and cropped to `size` = (W, H)), `ae.encode`, `run_trajectory`, `ae.decode`, `frames.to_uint8`.
     `Ks` (n,3,3) as `run_trajectory` takes them (normalised); the input views' rows are replaced by the intrinsics of the
@@ -433,7 +434,8 @@ def run_scene(denoise_net: Callable, ae, images: Sequence, c2ws: torch.Tensor, K
     `use_traj_prior=False`: the reference's one-pass evaluation mode (`run_views`; `chunk_strategy` then defaults to "gt",
     `options` / `task` go to `plan_views`).  `targets` = {frame id: picture}: held-out pictures, loaded exactly like the inputs
     and scored against the generated frames of those ids (`metrics.compare` on the uint8 frames) -> on rank 0
-    "metrics" = {"frame_ids", "sse", "psnr", "ssim"}; in either mode."""
+    "metrics" = {"frame_ids", "sse", "psnr", "ssim"}; in either mode.  `lpips` (a `metrics.LPIPS` on the device; frames of at
+    least 32 x 32) adds "lpips" to that table: the complete score table without the frames leaving the card."""
     from . import frames
     device = torch.device(run_trajectory_kwargs.pop("device", None) or "cuda")
     ids = [int(i) for i in input_ids]
@@ -460,6 +462,8 @@ def run_scene(denoise_net: Callable, ae, images: Sequence, c2ws: torch.Tensor, K
             from . import metrics
             tids = sorted(int(f) for f in targets)
             want = torch.cat([frames.to_uint8(frames.load_img_and_K(targets[f], size, device=device)[0]) for f in tids])
-            m = metrics.compare(res["frames"][tids], want)
+            m = metrics.compare(res["frames"][tids], want, lpips=lpips)
             res["metrics"] = {"frame_ids": tids, "sse": m["sse"], "psnr": m["psnr"], "ssim": m["ssim"]}
+            if lpips is not None:
+                res["metrics"]["lpips"] = m["lpips"]
     return res

@@ -59,6 +59,26 @@ def synth_state_dict(shapes: Mapping[str, tuple], seed: int = 0) -> dict[str, to
     return {k: synth_tensor(k, s, seed) for k, s in shapes.items()}
 
 
+def synth_lpips_state_dict(shapes: Mapping[str, tuple], seed: int = 0) -> dict[str, torch.Tensor]:
+    """Name-keyed deterministic weights for the keys of `seva.metrics.LpipsWeights` (`features.{i}.weight` / `.bias`,
+    `lin{k}.model.1.weight`).  A ReLU halves the second moment it passes on, so the conv weights carry the He gain sqrt(2 / fan_in)
+    and the activations stay O(1) through the 13 layers (f16 operands neither overflow nor vanish); biases are small; the linear
+    weights are |N(0, 1)| / C: non-negative, as the trained ones, and a layer's distance stays O(1 / C) per unit difference."""
+    out = {}
+    for key, shape in shapes.items():
+        shape = tuple(int(s) for s in shape)
+        g = torch.Generator(device="cpu")
+        g.manual_seed(_key_seed(key, seed))
+        if key.startswith("lin"):
+            w = torch.randn(shape, generator=g, dtype=torch.float32).abs() / shape[1]
+        elif key.endswith(".weight"):
+            w = torch.randn(shape, generator=g, dtype=torch.float32) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
+        else:
+            w = 0.05 * torch.randn(shape, generator=g, dtype=torch.float32)
+        out[key] = w.to(torch.bfloat16).to(torch.float32)
+    return out
+
+
 def orbit_c2w(num_frames: int, radius: float = 2.0, height: float = 0.3) -> torch.Tensor:
     """(T,4,4) camera-to-world poses on a circle looking at the origin (OpenCV axes)."""
     c2ws = []
