@@ -589,6 +589,44 @@ int seva_lpips_layer_size(int32_t n, int64_t hw, int64_t* workspace_bytes);
 int seva_lpips_layer(const seva_lpips_layer_desc* d, seva_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dynamic-range audit of one tensor: exponent histogram, special-value counts and finite extrema in one pass.  New symbols and
+ * one new struct; no existing struct changes (ABI version unchanged).  Everything is decided by integer tests on the elements' bit
+ * patterns (every f16 and e4m3 value is exact in f32), so denormal-flush modes do not enter; all counts are exact integers.
+ *   x          rows x cols elements, unit inner stride, rows `pitch` ELEMENTS apart (>= cols), aligned to the element size.
+ *              dtype SEVA_RANGE_F32, SEVA_RANGE_F16, or SEVA_RANGE_E4M3 (bytes in the OCP e4m3 "fn" encoding: no infinity,
+ *              NaN = 0x7F / 0xFF -- the encoding of every e4m3 tensor of this library).  Only the rows x cols elements are read.
+ *   out        SEVA_RANGE_WORDS uint64 words, device memory, 8-byte aligned.  With e(x) = floor(log2 |x|) of the exact value
+ *              (subnormals of the format included):
+ *                [0]            elements equal to +-0
+ *                [1 + k]        k = 0..63: finite non-zero elements with clamp(e(x), -32, 31) == k - 32
+ *                [65]           +-inf (always 0 for e4m3)
+ *                [66]           NaN, any payload
+ *                [67]           elements with |x| equal to the format's largest finite value (65504, 448, FLT_MAX); they are
+ *                               counted in their exponent bin as well -- the saturation signal of the e4m3 producers
+ *                [68]           f32 bit pattern of the largest finite |x|; 0 if there is none
+ *                [69]           f32 bit pattern of the smallest finite non-zero |x|; 0x7F800000 if there is none
+ *                [70]           rows * cols == [0] + sum [1..64] + [65] + [66]
+ *                [71]           0
+ *   workspace  seva_tensor_range_size(rows, cols) bytes, 8-byte aligned; contents need not be kept between calls.  It holds one
+ *              partial table per workgroup of the counting kernel; workgroup w counts elements [w * S, (w + 1) * S) of the
+ *              row-major rows x cols index space, S = SEVA_RANGE_WG_ELEMS (a larger multiple of it above 2048 * S elements), and
+ *              a second kernel adds the tables.  No atomics in global memory; the result is independent of the split.
+ * Nothing but the 72 words and the workspace is written.  rows * cols <= 2^46. */
+enum { SEVA_RANGE_F32 = 0, SEVA_RANGE_F16 = 1, SEVA_RANGE_E4M3 = 2 };
+#define SEVA_RANGE_WORDS 72
+#define SEVA_RANGE_WG_ELEMS 32768
+typedef struct seva_range_desc {
+  const void* x;
+  int32_t dtype;
+  int64_t rows, cols, pitch;   /* pitch in elements, >= cols */
+  void* workspace;
+  int64_t workspace_bytes;
+  uint64_t* out;               /* SEVA_RANGE_WORDS words, device memory */
+} seva_range_desc;
+int seva_tensor_range_size(int64_t rows, int64_t cols, int64_t* workspace_bytes);
+int seva_tensor_range(const seva_range_desc* d, seva_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Benchmark / debugging knobs. The library reads its SEVA_* environment variables ONCE, when it is loaded (nothing
  * on the launch path calls getenv); a host changes a knob at run time with seva_set_knob (tests, tools).  Names:
  * gemm_chunks, gemm_dbg, gemm_stagger, gemm_bm, gemm_bn, gemm_astat, attn_dbg, attn_no_tr, attn_two, attn_split,

@@ -19,9 +19,10 @@ import math
 
 import torch
 
-from . import ops
+from . import audit, ops
 from ._engine import _EngineBase, interleave_geglu
 from ._native import require_cuda
+from .ops import audit_mark  # (bound here: the tests' seam swaps this module's `ops`)
 
 F16, F32 = torch.float16, torch.float32
 
@@ -62,6 +63,7 @@ class ClipEngine(_EngineBase):
         self.W = W
 
     def _patches(self, x):
+        audit_mark("visual.conv1")
         p = self.p
         n = x.shape[0]
         g = p.image_size // p.patch_size
@@ -80,6 +82,7 @@ class ClipEngine(_EngineBase):
         img = pm[:, : 3 * P * P].float().view(x.shape[0], g, g, 3, P, P).permute(0, 3, 1, 4, 2, 5)
         return img.reshape(x.shape[0], 3, p.image_size, p.image_size)
 
+    @audit.first_call
     @torch.no_grad()
     def encode(self, x):
         """x: (n,3,H,W) fp32 in [-1,1] on the GPU -> (n, embed_dim) fp32."""
@@ -93,6 +96,7 @@ class ClipEngine(_EngineBase):
         tok[:, 0] = W["cls"] + W["pos"][0]  # class token rows: 1280 constants per image (index plumbing)
         for i in range(n):  # patch rows of image i = patches @ Wc^T + positional embedding (as the GEMM's residual)
             ops.gemm(pm[i * g * g:(i + 1) * g * g], W["patch.w"], residual=W["pos"][1:], out_f32=tok[i, 1:])
+        audit_mark("visual.ln_pre")
         cur = self._buf("stream_a", (rows, w), F32)
         ops.layernorm(tok.view(rows, w), W["ln_pre.g"], W["ln_pre.b"], cur)
         a16 = self._buf("ln16", (rows, w), F16)
@@ -103,6 +107,7 @@ class ClipEngine(_EngineBase):
         scale = 1.0 / math.sqrt(d)
         for i in range(p.layers):
             o = f"blk{i}"
+            audit_mark(f"visual.transformer.resblocks.{i}")
             ops.layernorm(cur, W[o + ".ln_1.g"], W[o + ".ln_1.b"], a16)
             ops.gemm(a16, W[o + ".qkv.w"], bias=W[o + ".qkv.b"], out_f16=qkv)
             ops.attention_small(qkv[:, :w], qkv[:, w:2 * w], qkv[:, 2 * w:], att, batch=n, heads=heads, L=L, head_dim=d,
@@ -111,6 +116,7 @@ class ClipEngine(_EngineBase):
             ops.layernorm(nxt, W[o + ".ln_2.g"], W[o + ".ln_2.b"], a16)
             ops.gemm(a16, W[o + ".fc1.w"], bias=W[o + ".fc1.b"], out_f16=hid, geglu=True)
             ops.gemm(hid, W[o + ".fc2.w"], bias=W[o + ".fc2.b"], residual=nxt, out_f32=cur)
+        audit_mark("visual.ln_post")
         cls32 = cur.view(n, L, w)[:, 0].contiguous()  # n class-token rows (index plumbing)
         m = max(n, 1)
         c16 = self._buf("cls16", (m, w), F16)

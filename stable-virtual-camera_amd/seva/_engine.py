@@ -27,9 +27,10 @@ import os
 
 import torch
 
-from . import _native, ops
+from . import _native, audit, ops
 from ._arch import Layout
 from ._native import SevaNativeError, require_cuda
+from .ops import audit_mark  # (bound here: the tests' seam swaps this module's `ops` for kernel emulations)
 
 F16, F32, U8 = torch.float16, torch.float32, torch.uint8
 # softmax scale of head dim 64 (reference transformer.py:66-72) times log2(e): exp(x) == exp2(x * log2 e)
@@ -117,6 +118,7 @@ class _Arena:
     def __init__(self, device):
         self.device = device
         self.bufs: dict = {}
+        audit.register_arena(self)  # (weakly: the audit names the buffer an output lies in)
 
     def get(self, name: str, shape, dtype, zero: bool = False) -> torch.Tensor:
         """zero: zeroed once, when the buffer is made (pad columns that nothing writes again, flag areas)"""
@@ -536,6 +538,7 @@ class SevaEngine(_EngineBase):
     # ------------------------------------------------------------------ blocks
     def _resblock(self, spec, x1, x2, n, h, w, dense, emb_all):
         """ResBlock.forward, reference layers.py:120-139.  x1 (‖ x2) fp32 [n, hw, c]."""
+        audit_mark(spec.prefix)
         W, pfx, hw = self.W, spec.prefix, h * w
         cin, cout = spec.cin, spec.cout
         f8_1, f8_2 = pfx + ".conv1.w8" in W, pfx + ".conv2.w8" in W  # fp8 mode: the conv consumes e4m3 activations
@@ -673,6 +676,7 @@ class SevaEngine(_EngineBase):
 
     def _transformer(self, spec, x, n, h, w, T, ctxvec, ctx16, lc):
         """MultiviewTransformer.forward, reference transformer.py:215-247."""
+        audit_mark(spec.prefix)
         W, pfx, hw, c, heads = self.W, spec.prefix, h * w, spec.channels, spec.heads
         rows = n * hw
         sp_in, sp_out = "proj_in" in self.split, "proj_out" in self.split
@@ -689,6 +693,7 @@ class SevaEngine(_EngineBase):
             b = f"{pfx}.transformer_blocks.{i}"
             m = f"{pfx}.time_mix_blocks.{i}"
             regime = "joint" if spec.joint else "frame"
+            audit_mark(b)
             # x = attn1(norm1 x) + x ; x = attn2(norm2 x, ctx) + x
             h1 = self._buf("t_h1", (rows, c), F32)
             if collapse:
@@ -713,6 +718,7 @@ class SevaEngine(_EngineBase):
             h2 = self._buf("t_h2", (rows, c), F32)
             self._ff(h1, b + ".norm3", b + ".ff", rows, c, residual=h1, out_f32=h2, unit=hw)
             # ---- time-mix block on x_spatial = h2 (transformer.py:145-155) ----
+            audit_mark(m)
             m1 = self._buf("t_m1", (rows, c), F32)
             self._ff(h2, m + ".norm_in", m + ".ff_in", rows, c, residual=h2, out_f32=m1, unit=hw)
             m2 = self._buf("t_m2", (rows, c), F32)
@@ -734,6 +740,7 @@ class SevaEngine(_EngineBase):
             last16 = self._buf("t_h16", (rows, 2 * c if sp_out else c), F16)  # (split: [hi | lo], written by _ff's FF2)
             self._ff(m2, m + ".norm3", m + ".ff", rows, c, residual=h2, out_f32=nxt, out_f16=last16, unit=hw)
             cur = nxt
+        audit_mark(pfx)
         out = self._buf("out:" + pfx, (n, hw, c), F32)
         st_out = self._stats_buf("out:" + pfx, rows, hw, c)
         ops.gemm(last16, W[pfx + ".proj_out.w"], bias=W[pfx + ".proj_out.b"], residual=x.view(rows, c),
@@ -743,6 +750,7 @@ class SevaEngine(_EngineBase):
 
     def _resample(self, spec, x, n, h, w):
         """Downsample (layers.py:49-58) / Upsample (layers.py:35-46)."""
+        audit_mark(spec.prefix)
         c = spec.channels
         sp_rs = "resample" in self.split
         x16 = self._buf("rs16", (n, h, w, 2 * c if sp_rs else c), F16)
@@ -829,6 +837,7 @@ class SevaEngine(_EngineBase):
         st["y"].copy_(y)
         st["dense"].copy_(dense_y)
 
+    @audit.first_call
     def __call__(self, x, concat, t, y, dense_y, num_frames):
         # inside a whole-step capture (seva/_stepgraph.py) or its warm-up the network is launched eagerly: its ~600
         # kernels become nodes of the step graph instead of a nested replay
@@ -860,6 +869,7 @@ class SevaEngine(_EngineBase):
         self._stats = {}
 
         # --- prologue: timestep embedding MLP, all ResBlock emb projections, folded cross-attn ---
+        audit_mark("time_embed")
         mc, ed = p.model_channels, lay.time_embed_dim
         te16 = self._buf("te16", (n, mc), F16)
         ops.timestep_embedding_f16(t, W["freqs"], te16)
@@ -892,6 +902,7 @@ class SevaEngine(_EngineBase):
 
         # --- stem ---
         stem = lay.input_blocks[0][0]
+        audit_mark(stem.prefix)
         sp_stem = "stem" in self.split and 2 * cin <= CIN_PAD
         cpad = CIN_PAD * (((2 if sp_stem else 1) * cin + CIN_PAD - 1) // CIN_PAD)
         x16 = self._buf("x16", (n, h, w, cpad), F16)
@@ -925,6 +936,7 @@ class SevaEngine(_EngineBase):
             cur, ch, cw = run(block, cur, skip, ch, cw)
 
         # --- head: GroupNorm + SiLU + conv3x3 (model.py:170-174) ---
+        audit_mark("out")
         cfin = lay.final_channels
         sp_head = "head" in self.split
         cf2 = (2 if sp_head else 1) * cfin

@@ -106,6 +106,13 @@ class LpipsLayerDesc(C.Structure):
     ]
 
 
+class RangeDesc(C.Structure):
+    _fields_ = [
+        ("x", c_void_p), ("dtype", c_int32), ("rows", c_int64), ("cols", c_int64), ("pitch", c_int64),
+        ("workspace", c_void_p), ("workspace_bytes", c_int64), ("out", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/seva_hip.h
 SYMBOLS = {
     "seva_last_error": (c_char_p, []),
@@ -161,6 +168,8 @@ SYMBOLS = {
     "seva_lpips_relu_pool_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "seva_lpips_layer_size": (c_int, [c_int32, c_int64, POINTER(c_int64)]),
     "seva_lpips_layer": (c_int, [POINTER(LpipsLayerDesc), c_void_p]),
+    "seva_tensor_range_size": (c_int, [c_int64, c_int64, POINTER(c_int64)]),
+    "seva_tensor_range": (c_int, [POINTER(RangeDesc), c_void_p]),
     "seva_set_knob": (c_int, [c_char_p, c_int32]),
     "seva_get_knob": (c_int, [c_char_p, POINTER(c_int32)]),
     "seva_graph_begin": (c_int, [c_void_p]),

@@ -70,6 +70,7 @@ class StepGraphCache:
         self.key = None
         self.state = 0
         self.graph: StepGraph | None = None
+        self.keep = None  # tensors of the warm-up step that the captured graph reads by address
         self.disabled = False
         self.captures = 0
 
@@ -87,8 +88,8 @@ class StepGraphCache:
 
     def lookup(self, key):
         if self.key is None or not self._same(self.key, key):
-            self.key, self.state, self.graph = key, 0, None
+            self.key, self.state, self.graph, self.keep = key, 0, None, None
         return self
 
     def reset(self):
-        self.key, self.state, self.graph = None, 0, None
+        self.key, self.state, self.graph, self.keep = None, 0, None, None

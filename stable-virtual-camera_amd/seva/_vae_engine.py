@@ -19,9 +19,10 @@ import os
 
 import torch
 
-from . import ops
+from . import audit, ops
 from ._engine import CIN_PAD, _EngineBase, combine_up_phases, env_flag, pack_conv3x3
 from ._native import require_cuda
+from .ops import audit_mark  # (bound here: the tests' seam swaps this module's `ops`)
 
 F16, F32 = torch.float16, torch.float32
 U8 = torch.uint8  # e4m3 bytes (ops.py)
@@ -231,6 +232,7 @@ class _VaeEngineBase(_EngineBase):
         out of the first GroupNorm's pass over x (`raw_f16`) instead of a cast pass of its own.
         fp8 decode / encode: a conv with e4m3 weights in `self._w8` reads the e4m3 output of its GroupNorm; f8_out is f16_out's
         e4m3 twin (the upsample / downsample conv's A operand, written by the e4m3 conv2's epilogue, saturating)."""
+        audit_mark(p)
         W, W8, hw = self.W, self._w8, h * w
         f8_1, f8_2 = p + ".conv1.w8" in W8, p + ".conv2.w8" in W8
         assert f8_out is None or f8_2
@@ -275,6 +277,7 @@ class _VaeEngineBase(_EngineBase):
 
     def _attention(self, p, x, n, h, w, c):
         """Single-head self-attention over h*w tokens of dim c (diffusers Attention in the VAE mid block)."""
+        audit_mark(p)
         W, hw = self.W, h * w
         if hw % 4:
             raise ValueError(f"VAE attention needs h*w % 4 == 0 (got {h}x{w}); latents are multiples of 8 per side")
@@ -345,9 +348,11 @@ class VaeDecoderEngine(_VaeEngineBase):
         wq[:, : self.latent] = sd["post_quant_conv.weight"].reshape(self.latent, self.latent).to(F16)
         self.W["post_quant_conv.w"], self.W["post_quant_conv.b"] = wq, sd["post_quant_conv.bias"].float().contiguous()
 
+    @audit.first_call
     @torch.no_grad()
     def decode(self, z: torch.Tensor, scale_factor: float) -> torch.Tensor:
         require_cuda(z)
+        audit_mark("post_quant_conv")
         W = self.W
         z = z.to(F32).contiguous()
         n, cz, h, w = z.shape
@@ -365,6 +370,7 @@ class VaeDecoderEngine(_VaeEngineBase):
         pq = self._buf("v_pq16", (n * h * w, CIN_PAD), F16, zero=True)      # cols >= 4 stay zero
         ops.gemm(z16.view(n * h * w, CIN_PAD), W["post_quant_conv.w"], bias=W["post_quant_conv.b"], out_f16=pq)
         top = self.block_out[-1]
+        audit_mark("decoder.conv_in")
         x = self._buf("out:conv_in", (n, h * w, top), F32)
         st = self._stats_buf("out:conv_in", n * h * w, h * w, top)
         ops.conv3x3(pq.view(n, h, w, CIN_PAD), W["decoder.conv_in.w"], bias=W["decoder.conv_in.b"], out_f32=x, ch_stats=st)
@@ -387,6 +393,7 @@ class VaeDecoderEngine(_VaeEngineBase):
             cin = cout
             if up:
                 h, w = 2 * h, 2 * w
+                audit_mark(p)
                 x = self._buf("out:" + p, (n, h * w, cout), F32)
                 st = self._stats_buf("out:" + p, n * h * w, h * w, cout)
                 if up8:
@@ -401,6 +408,7 @@ class VaeDecoderEngine(_VaeEngineBase):
                     ops.conv3x3(x16, W[p + ".w"], upsample=True, bias=W[p + ".b"], out_f32=x, ch_stats=st)
                 self._produced(x, st)
         c = rev[-1]
+        audit_mark("decoder.conv_norm_out")
         g16 = self._buf("gn16", (n, h * w, c), F16)
         ops.groupnorm(x, None, W["decoder.conv_norm_out.g"], W["decoder.conv_norm_out.b"], g16, self.gn_ws,
                       eps=1e-6, silu=True, stats1=self._gn_stats(x)[0])
@@ -440,9 +448,11 @@ class VaeEncoderEngine(_VaeEngineBase):
         b = wq @ bo + sd["quant_conv.bias"].double()[:L]
         self.W["enc_out.w"], self.W["enc_out.b"] = pack_conv3x3(w.float()), b.float().contiguous()
 
+    @audit.first_call
     @torch.no_grad()
     def encode(self, x: torch.Tensor, scale_factor: float) -> torch.Tensor:
         require_cuda(x)
+        audit_mark("encoder.conv_in")
         W = self.W
         x = x.to(F32).contiguous()
         n, cx, h, w = x.shape
@@ -473,6 +483,7 @@ class VaeEncoderEngine(_VaeEngineBase):
             cin = cout
             if i != nd:
                 h, w = h // 2, w // 2
+                audit_mark(p)
                 cur = self._buf("out:" + p, (n, h * w, cout), F32)
                 st = self._stats_buf("out:" + p, n * h * w, h * w, cout)
                 if dn8:
@@ -485,6 +496,7 @@ class VaeEncoderEngine(_VaeEngineBase):
         cur = self._resnet("encoder.mid_block.resnets.0", cur, n, h, w, top, top)
         cur = self._attention("encoder.mid_block.attentions.0", cur, n, h, w, top)
         cur = self._resnet("encoder.mid_block.resnets.1", cur, n, h, w, top, top)
+        audit_mark("encoder.conv_norm_out")
         g16 = self._buf("gn16", (n, h * w, top), F16)
         ops.groupnorm(cur, None, W["encoder.conv_norm_out.g"], W["encoder.conv_norm_out.b"], g16, self.gn_ws,
                       eps=1e-6, silu=True, stats1=self._gn_stats(cur)[0])

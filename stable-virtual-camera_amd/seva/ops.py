@@ -9,6 +9,8 @@ channels-last activations, f16 GEMM operands, f32 residual stream.
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import inspect
 
 import torch
 
@@ -23,6 +25,173 @@ def _lib():
     return nv.load()
 
 
+# --- dynamic-range audit (seva/audit.py; the kernel's contract is in include/seva_hip.h) --------------------------------
+RANGE_WORDS = 72         # SEVA_RANGE_WORDS
+RANGE_WG_ELEMS = 32768   # SEVA_RANGE_WG_ELEMS: elements one workgroup of the counting kernel takes (tensors up to 2048 of them)
+RANGE_DTYPES = {F32: 0, F16: 1, U8: 2}  # SEVA_RANGE_F32 / _F16 / _E4M3
+
+# wrapper name -> names of its floating-point (f32 / f16 / e4m3) output parameters; filled by `_audited`.  While a recorder is
+# active (`audit.record()`), a listed wrapper hands each output it was given to the recorder after its launch.
+AUDITED: dict = {}
+# every other function of this module that calls the library, and why its outputs are not audited
+NOT_AUDITED = {
+    "tensor_range": "the audit's own instrument (uint64 words)",
+    "tensor_range_workspace_numel": "size query",
+    "_up_phases": "shared body of conv3x3_up_phases / conv3x3_up_phases128, which are audited",
+    "_v_fp8_parts": "size query",
+    "rgb_to_u8": "uint8 output",
+    "frame_metrics_workspace_numel": "size query",
+    "frame_metrics": "integer and fp64 sums",
+    "lpips_layer_workspace_numel": "size query",
+    "lpips_layer": "fp64 sums",
+    "set_knob": "knob",
+    "get_knob": "knob",
+    "last_plan": "plan name of the last launch",
+    "prof_enable": "profiling switch",
+    "prof_collect": "profiling counters",
+}
+_AUDIT = None  # the active recorder (seva.audit.Recorder), None = off: the wrappers then do exactly what they did before
+
+
+def audit_mark(scope: str) -> None:
+    """Name the part of the network the following launches belong to (a state-dict prefix), until the next mark.  A no-op
+    unless a recorder is active."""
+    if _AUDIT is not None:
+        _AUDIT.scope = scope
+
+
+def _audited(*outputs: str):
+    def deco(fn):
+        AUDITED[fn.__name__] = outputs
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def wrapper(*a, **kw):
+            if _AUDIT is None:
+                return fn(*a, **kw)
+            r = fn(*a, **kw)
+            bound = sig.bind(*a, **kw)
+            bound.apply_defaults()
+            audit_outputs(fn.__name__, bound.arguments)
+            return r
+
+        return wrapper
+
+    return deco
+
+
+def audit_outputs(op: str, a: dict) -> None:
+    """Hand the outputs of one call of wrapper `op` (a: its arguments by name) to the active recorder."""
+    if _AUDIT is None:
+        return
+    for name in AUDITED[op]:
+        t = a.get(name)
+        if t is not None:
+            for label, off, rows, cols, pitch in _audit_views(op, name, t, a):
+                _AUDIT.output(op, label, t, off, rows, cols, pitch)
+
+
+def _as_2d(t: torch.Tensor) -> list:
+    """(element offset, rows, cols, pitch) pieces that cover exactly the elements of `t` (unit inner stride)."""
+    if t.dim() == 0 or t.numel() == 0:
+        return [] if t.numel() == 0 else [(0, 1, 1, 1)]
+    assert t.stride(-1) == 1 or t.shape[-1] == 1, "audited outputs have unit inner stride"
+    shape, stride = list(t.shape), list(t.stride())
+    cols, j = 1, len(shape) - 1
+    while j >= 0 and (shape[j] == 1 or stride[j] == cols):  # the dense tail
+        cols *= shape[j]
+        j -= 1
+    if j < 0:
+        return [(0, t.numel() // shape[-1], shape[-1], shape[-1])]
+    if all(shape[i + 1] == 1 or stride[i] == stride[i + 1] * shape[i + 1] for i in range(j)):  # one pitch above the tail
+        rows = 1
+        for i in range(j + 1):
+            rows *= shape[i]
+        return [(0, rows, cols, stride[j])]
+    return [(i * stride[0] + o, r, c, p) for i in range(shape[0]) for o, r, c, p in _as_2d(t[i])]
+
+
+def _audit_views(op: str, name: str, t: torch.Tensor, a: dict) -> list:
+    """(label, element offset, rows, cols, pitch) records of output `name` of wrapper `op`: the logical area the launch wrote.
+    A split-precision [hi | lo] output is two records."""
+    def lastdim(cols, split=False, rows=None):
+        rows = t.numel() // t.shape[-1] if rows is None else rows
+        pitch = t.stride(-2) if t.dim() >= 2 else t.shape[-1]
+        if split:
+            return [(name + ".hi", 0, rows, cols, pitch), (name + ".lo", cols, rows, cols, pitch)]
+        return [(name, 0, rows, cols, pitch)]
+
+    if op == "gemm":
+        no = a["w"].shape[0] // (2 if a["geglu"] else 1)
+        return lastdim(no, split=a["split_out"] and name == "out_f16", rows=a["a"].shape[0])
+    if op == "conv3x3":
+        return lastdim(a["w"].shape[0])
+    if op in ("conv3x3_up_phases", "conv3x3_up_phases128"):
+        return lastdim(a["w4"].shape[1])
+    if op in ("ff_fused", "ff_fused_fp8"):
+        return lastdim(a["w2"].shape[0])
+    if op == "groupnorm":
+        c = a["x1"].shape[2] + (a["x2"].shape[2] if a["x2"] is not None else 0)
+        return lastdim(c, split=(name == "out_f16" and a["split_out"]) or (name == "raw_f16" and a["split_raw"]),
+                       rows=a["x1"].shape[0] * a["x1"].shape[1])
+    if op == "layernorm":
+        c = a["x"].shape[-1]
+        return lastdim(c, rows=a["x"].numel() // c)
+    if op in ("layernorm_split", "cast_concat_f16_split"):
+        return lastdim(t.shape[-1] // 2, split=True)
+    if op == "nchw_to_nhwc_f16":  # (the pad channels behind them are zeros, not values)
+        return lastdim(a["x1"].shape[1] + (a["x2"].shape[1] if a["x2"] is not None else 0), split=a["split"])
+    if op == "softmax_rows":  # (likewise the zero columns from `cols` up)
+        return lastdim(a["cols"])
+    if op == "clip_preprocess":
+        return lastdim(3 * a["patch"] * a["patch"])
+    if op == "quantize_v_fp8":  # the e4m3 values; the E8M0 scale bytes behind them are no e4m3 numbers
+        return [(name, 0, 1, _v_fp8_parts(a["nb0"] * a["nb1"], a["heads"], a["lk"])[0], t.numel())]
+    return [(name, off, rows, cols, pitch) for off, rows, cols, pitch in _as_2d(t)]
+
+
+def tensor_range_workspace_numel(rows: int, cols: int) -> int:
+    """uint8 elements of `tensor_range(workspace=...)`: one 72-word partial table per workgroup of the counting kernel."""
+    size = C.c_int64()
+    check(_lib().seva_tensor_range_size(int(rows), int(cols), C.byref(size)), "seva_tensor_range_size")
+    return size.value
+
+
+def tensor_range(x: torch.Tensor, out: torch.Tensor | None = None, *, rows: int | None = None, cols: int | None = None,
+                 workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """Exponent histogram, special-value counts and finite extrema of x in one pass (seva_tensor_range; the 72-word contract is in
+    include/seva_hip.h).  x: a 2-D view (or 1-D: one row) with unit inner stride, f32, f16, or uint8 = e4m3 bytes; rows / cols
+    narrow the audited area to its top-left corner.  Returns `out`: 72 uint64 words on the device, held as int64 (the same
+    bits; None: allocated here).  workspace: uint8, `tensor_range_workspace_numel` elements (None: allocated here).  No host sync."""
+    require_cuda(x, out, workspace)
+    if x.dtype not in RANGE_DTYPES:
+        raise nv.SevaNativeError(f"tensor_range: dtype {x.dtype} (float32, float16, or uint8 holding e4m3 bytes)")
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    if x.dim() != 2 or (x.stride(1) != 1 and x.shape[1] != 1):
+        raise nv.SevaNativeError(f"tensor_range: a 2-D view with unit inner stride (got shape {tuple(x.shape)}, strides {x.stride()})")
+    rows = x.shape[0] if rows is None else int(rows)
+    cols = x.shape[1] if cols is None else int(cols)
+    if not (0 < rows <= x.shape[0] and 0 < cols <= x.shape[1]):
+        raise nv.SevaNativeError(f"tensor_range: rows x cols = {rows} x {cols} outside the view {tuple(x.shape)}")
+    pitch = x.stride(0) if rows > 1 else cols
+    if pitch < cols:
+        raise nv.SevaNativeError(f"tensor_range: row pitch {pitch} below cols {cols} (overlapping rows)")
+    if out is None:
+        out = torch.empty(RANGE_WORDS, dtype=torch.int64, device=x.device)
+    assert out.dtype == torch.int64 and out.numel() == RANGE_WORDS and out.is_contiguous()
+    need = tensor_range_workspace_numel(rows, cols)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=U8, device=x.device)
+    assert workspace.dtype == U8 and workspace.is_contiguous() and workspace.numel() >= need, "tensor_range workspace too small"
+    d = nv.RangeDesc()
+    d.x, d.dtype, d.rows, d.cols, d.pitch = x.data_ptr(), RANGE_DTYPES[x.dtype], rows, cols, pitch
+    d.workspace, d.workspace_bytes, d.out = workspace.data_ptr(), workspace.numel(), out.data_ptr()
+    check(_lib().seva_tensor_range(C.byref(d), stream_ptr(x.device)), "seva_tensor_range")
+    return out
+
+
+@_audited("out_f32", "out_f16", "out_f8")
 def gemm(
     a: torch.Tensor,
     w: torch.Tensor,
@@ -192,6 +361,7 @@ def _ff_desc(a, w1, b1, w2, b2, M, c, residual, out_f32, out_f16, ln_x, ln_gamma
     return d
 
 
+@_audited("out_f32", "out_f16")
 def ff_fused(a: torch.Tensor | None, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, *,
              residual: torch.Tensor | None = None, out_f32: torch.Tensor | None = None,
              out_f16: torch.Tensor | None = None, ln_x: torch.Tensor | None = None,
@@ -232,6 +402,7 @@ def pack_ff_fp8(w1: torch.Tensor, w2: torch.Tensor):
     return w1_8, w1_exp, w2_8[:, perm].contiguous(), w2_exp
 
 
+@_audited("out_f32", "out_f16")
 def ff_fused_fp8(a: torch.Tensor | None, w1: torch.Tensor, w1_exp: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
                  w2_exp: torch.Tensor, b2: torch.Tensor, *, residual: torch.Tensor | None = None,
                  out_f32: torch.Tensor | None = None, out_f16: torch.Tensor | None = None, ln_x: torch.Tensor | None = None,
@@ -253,6 +424,7 @@ def ff_fused_fp8(a: torch.Tensor | None, w1: torch.Tensor, w1_exp: torch.Tensor,
     check(_lib().seva_ff_fused_fp8(C.byref(d), stream_ptr(src.device)), "seva_ff_fused_fp8")
 
 
+@_audited("out_f32", "out_f16", "out_f8")
 def conv3x3(
     x: torch.Tensor,
     w: torch.Tensor,
@@ -328,6 +500,7 @@ def _up_phases(name: str, code: int, what: str, x, w4, bias, out_f32, ch_stats, 
     check(_lib().seva_gemm_f16(C.byref(d), stream_ptr(x.device)), what)
 
 
+@_audited("out_f32")
 def conv3x3_up_phases(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tensor | None = None, out_f32: torch.Tensor | None = None,
                       ch_stats: torch.Tensor | None = None, alg_k: int = 0) -> None:
     """Nearest-2x upsample + 3x3 pad-1 conv as four 2x2 phase convs on the source image (seva_gemm_desc.upsample = 2): 4/9 of the
@@ -339,6 +512,7 @@ def conv3x3_up_phases(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tensor |
     _up_phases("conv3x3_up_phases", 2, "seva_gemm_f16(conv, upsample phases)", x, w4, bias, out_f32, ch_stats, alg_k)
 
 
+@_audited("out_f32")
 def conv3x3_up_phases128(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tensor | None = None, out_f32: torch.Tensor | None = None,
                          ch_stats: torch.Tensor | None = None, alg_k: int = 0) -> None:
     """`conv3x3_up_phases` on the 128-column tiles (seva_gemm_desc.upsample = 4): the VAE decoders' upsample convs.  Same operands
@@ -349,6 +523,7 @@ def conv3x3_up_phases128(x: torch.Tensor, w4: torch.Tensor, *, bias: torch.Tenso
     _up_phases("conv3x3_up_phases128", 4, "seva_gemm_f16(conv, upsample phases, 128 columns)", x, w4, bias, out_f32, ch_stats, alg_k)
 
 
+@_audited("out")
 def attention(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -421,6 +596,7 @@ def _attn_desc(q, k, v, out, nb0, nb1, heads, lq, lk, q_strides, k_strides, o_st
     return d
 
 
+@_audited("ws")
 def quantize_v_fp8(v: torch.Tensor, ws: torch.Tensor, *, nb0: int, nb1: int, heads: int, lk: int,
                    k_strides: tuple[int, int, int]) -> None:
     """V (f16, the attention strides) -> the e4m3 + E8M0 workspace `attention_pv8` reads (seva_attn_quant_v_fp8).
@@ -431,6 +607,7 @@ def quantize_v_fp8(v: torch.Tensor, ws: torch.Tensor, *, nb0: int, nb1: int, hea
     check(_lib().seva_attn_quant_v_fp8(C.byref(d), v8, sc, stream_ptr(v.device)), "seva_attn_quant_v_fp8")
 
 
+@_audited("out")
 def attention_pv8(q: torch.Tensor, k: torch.Tensor, ws: torch.Tensor, out: torch.Tensor, *, nb0: int, nb1: int, heads: int,
                   lq: int, lk: int, q_strides: tuple[int, int, int], k_strides: tuple[int, int, int],
                   o_strides: tuple[int, int, int], split_ws: torch.Tensor | None = None) -> None:
@@ -449,6 +626,7 @@ def groupnorm_workspace(n: int, device) -> torch.Tensor:
     return torch.empty(n * GN_WORKSPACE_SLABS * 32 * 2, dtype=F32, device=device)
 
 
+@_audited("out_f16", "raw_f16", "out_f8")
 def groupnorm(
     x1: torch.Tensor,
     x2: torch.Tensor | None,
@@ -506,6 +684,7 @@ def groupnorm(
     check(_lib().seva_groupnorm_f16(C.byref(d), stream_ptr(x1.device)), "seva_groupnorm_f16")
 
 
+@_audited("out_f16")
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_f16: torch.Tensor,
               eps: float = 1e-5) -> None:
     """LayerNorm over the last dim; the output dtype selects the kernel: f16, or uint8 = e4m3 bytes (seva_layernorm_fp8)."""
@@ -530,6 +709,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_f16:
           "seva_layernorm_f16")
 
 
+@_audited("out_f16")
 def layernorm_split(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_f16: torch.Tensor, eps: float = 1e-5) -> None:
     """LayerNorm over the last dim as a split-precision operand (seva_layernorm_f16_split): out_f16 [rows, 2 c] f16 = [hi | lo], hi
     bitwise `layernorm`'s f16 output, lo = f16(y - f32(hi))."""
@@ -561,6 +741,7 @@ def to_fp8(x: torch.Tensor) -> torch.Tensor:
     return x.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
 
 
+@_audited("patches_f16")
 def clip_preprocess(x: torch.Tensor, patches_f16: torch.Tensor, mean, std, *, out_size: int = 224, patch: int = 14,
                     antialias: bool = True) -> None:
     """kornia-style resize + CLIP normalisation, emitted as the patch matrix of the patch-embedding GEMM
@@ -577,6 +758,7 @@ def clip_preprocess(x: torch.Tensor, patches_f16: torch.Tensor, mean, std, *, ou
                                           1 if antialias else 0, stream_ptr(x.device)), "seva_clip_preprocess_f16")
 
 
+@_audited("out")
 def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, batch: int, heads: int,
                     L: int, head_dim: int, q_strides: tuple[int, int], k_strides: tuple[int, int],
                     o_strides: tuple[int, int], scale: float) -> None:
@@ -589,6 +771,7 @@ def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torc
                                           heads, L, head_dim, scale, stream_ptr(q.device)), "seva_attention_small_f16")
 
 
+@_audited("out_f16")
 def softmax_rows(x: torch.Tensor, out_f16: torch.Tensor, cols: int, scale: float) -> None:
     """x: [rows, >=cols] f32 -> out_f16: [rows, cols_pad] f16 = softmax(x[:, :cols]*scale), zero padded."""
     require_cuda(x, out_f16)
@@ -598,6 +781,7 @@ def softmax_rows(x: torch.Tensor, out_f16: torch.Tensor, cols: int, scale: float
           "seva_softmax_rows_f16")
 
 
+@_audited("out_f16")
 def nchw_to_nhwc_f16(x1: torch.Tensor, x2: torch.Tensor | None, out_f16: torch.Tensor,
                      scale: torch.Tensor | None = None, split: bool = False) -> None:
     """split: channels [C, 2C) of the output receive the low parts f16(v - f32(f16(v))) (seva_nchw_to_nhwc_f16_split)."""
@@ -610,6 +794,7 @@ def nchw_to_nhwc_f16(x1: torch.Tensor, x2: torch.Tensor | None, out_f16: torch.T
              stream_ptr(x1.device)), "seva_nchw_to_nhwc_f16")
 
 
+@_audited("out")
 def nhwc_to_nchw_f32(x: torch.Tensor, out: torch.Tensor) -> None:
     """x: [n, hw, ld] f32 (first c channels used) -> out [n, c, h, w] f32."""
     require_cuda(x, out)
@@ -619,6 +804,7 @@ def nhwc_to_nchw_f32(x: torch.Tensor, out: torch.Tensor) -> None:
                                        stream_ptr(x.device)), "seva_nhwc_to_nchw_f32")
 
 
+@_audited("out_f16")
 def cast_concat_f16(x1: torch.Tensor, x2: torch.Tensor | None, out_f16: torch.Tensor) -> None:
     require_cuda(x1, out_f16)
     c1 = x1.shape[-1]
@@ -628,6 +814,7 @@ def cast_concat_f16(x1: torch.Tensor, x2: torch.Tensor | None, out_f16: torch.Te
                                       stream_ptr(x1.device)), "seva_cast_concat_f16")
 
 
+@_audited("out_f16")
 def cast_concat_f16_split(x1: torch.Tensor, x2: torch.Tensor | None, out_f16: torch.Tensor) -> None:
     """`cast_concat_f16` as a split-precision operand (seva_cast_concat_f16_split): out_f16 [rows, 2 (c1 + c2)] = [f16(v) | f16(v - f32(f16(v)))]."""
     require_cuda(x1, out_f16)
@@ -639,6 +826,7 @@ def cast_concat_f16_split(x1: torch.Tensor, x2: torch.Tensor | None, out_f16: to
                                             stream_ptr(x1.device)), "seva_cast_concat_f16_split")
 
 
+@_audited("out")
 def bilinear_to_nhwc(src: torch.Tensor, out: torch.Tensor, oh: int, ow: int) -> None:
     require_cuda(src, out)
     n, c, sh, sw = src.shape
@@ -646,6 +834,7 @@ def bilinear_to_nhwc(src: torch.Tensor, out: torch.Tensor, oh: int, ow: int) -> 
                                            stream_ptr(src.device)), "seva_bilinear_to_nhwc_f32")
 
 
+@_audited("out_f16")
 def timestep_embedding_f16(t: torch.Tensor, freqs: torch.Tensor, out_f16: torch.Tensor) -> None:
     require_cuda(t, out_f16)
     assert t.dtype == torch.int64
@@ -655,18 +844,21 @@ def timestep_embedding_f16(t: torch.Tensor, freqs: torch.Tensor, out_f16: torch.
           "seva_timestep_embedding_f16")
 
 
+@_audited("out_f16")
 def silu_f16(x: torch.Tensor, out_f16: torch.Tensor) -> None:
     require_cuda(x, out_f16)
     check(_lib().seva_silu_f16(x.data_ptr(), out_f16.data_ptr(), x.numel(), stream_ptr(x.device)),
           "seva_silu_f16")
 
 
+@_audited("out")
 def add_f32(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> None:
     require_cuda(a, b, out)
     check(_lib().seva_add_f32(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(),
                               stream_ptr(a.device)), "seva_add_f32")
 
 
+@_audited("out")
 def replace_blend(x: torch.Tensor, replace: torch.Tensor, out: torch.Tensor) -> None:
     require_cuda(x, replace, out)
     n, c = x.shape[:2]
@@ -675,6 +867,7 @@ def replace_blend(x: torch.Tensor, replace: torch.Tensor, out: torch.Tensor) -> 
                                         stream_ptr(x.device)), "seva_replace_blend_f32")
 
 
+@_audited("out")
 def denoiser_combine(net: torch.Tensor, x: torch.Tensor, c_out: torch.Tensor, c_skip: torch.Tensor,
                      out: torch.Tensor) -> None:
     require_cuda(net, x, out)
@@ -684,6 +877,7 @@ def denoiser_combine(net: torch.Tensor, x: torch.Tensor, c_out: torch.Tensor, c_
                                            stream_ptr(x.device)), "seva_denoiser_combine_f32")
 
 
+@_audited("out")
 def add_noise(x: torch.Tensor, eps: torch.Tensor, noise_scale: torch.Tensor, out: torch.Tensor) -> None:
     require_cuda(x, eps, out)
     n = x.shape[0]
@@ -692,6 +886,7 @@ def add_noise(x: torch.Tensor, eps: torch.Tensor, noise_scale: torch.Tensor, out
           "seva_add_noise_f32")
 
 
+@_audited("out")
 def cfg_euler(x: torch.Tensor, den2: torch.Tensor, scale: torch.Tensor, sigma_hat: torch.Tensor,
               dt: torch.Tensor, out: torch.Tensor) -> None:
     require_cuda(x, den2, out)
@@ -701,6 +896,7 @@ def cfg_euler(x: torch.Tensor, den2: torch.Tensor, scale: torch.Tensor, sigma_ha
                                     x.numel() // n, stream_ptr(x.device)), "seva_cfg_euler_f32")
 
 
+@_audited("out", "den_out")
 def cfg_multistep(x: torch.Tensor, den: torch.Tensor, scale: torch.Tensor | None, old_den: torch.Tensor | None,
                   a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, out: torch.Tensor,
                   den_out: torch.Tensor | None = None) -> None:
@@ -727,6 +923,7 @@ def cfg_multistep(x: torch.Tensor, den: torch.Tensor, scale: torch.Tensor | None
                                         x.numel() // max(n, 1), stream_ptr(x.device)), "seva_cfg_multistep_f32")
 
 
+@_audited("out")
 def cfg_combine(den2: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> None:
     require_cuda(den2, scale, out)
     n = out.shape[0]
@@ -734,6 +931,7 @@ def cfg_combine(den2: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> N
                                       out.numel() // n, stream_ptr(out.device)), "seva_cfg_combine_f32")
 
 
+@_audited("out")
 def euler_step(x: torch.Tensor, den: torch.Tensor, sigma_hat: torch.Tensor, dt: torch.Tensor,
                out: torch.Tensor) -> None:
     require_cuda(x, den, out)
@@ -743,6 +941,7 @@ def euler_step(x: torch.Tensor, den: torch.Tensor, sigma_hat: torch.Tensor, dt: 
                                      stream_ptr(x.device)), "seva_euler_step_f32")
 
 
+@_audited("out")
 def to_d(x: torch.Tensor, den: torch.Tensor, sigma: torch.Tensor, out: torch.Tensor) -> None:
     require_cuda(x, den, out)
     n = x.shape[0]
@@ -750,6 +949,7 @@ def to_d(x: torch.Tensor, den: torch.Tensor, sigma: torch.Tensor, out: torch.Ten
                                x.numel() // n, stream_ptr(x.device)), "seva_to_d_f32")
 
 
+@_audited("out")
 def scale_rows(x: torch.Tensor, s: torch.Tensor, out: torch.Tensor) -> None:
     require_cuda(x, s, out)
     n = x.shape[0]
@@ -757,6 +957,7 @@ def scale_rows(x: torch.Tensor, s: torch.Tensor, out: torch.Tensor) -> None:
                                      x.numel() // n, stream_ptr(x.device)), "seva_scale_rows_f32")
 
 
+@_audited("out")
 def plucker(kinv: torch.Tensor, pose_inv: torch.Tensor, out: torch.Tensor) -> None:
     """out[v] (6,h,w) = Pluecker map of view v from its inverse intrinsics (3x3, latent-pixel units) and the
     inverse relative pose rows (3x4) (seva_plucker_f32)."""
@@ -769,6 +970,7 @@ def plucker(kinv: torch.Tensor, pose_inv: torch.Tensor, out: torch.Tensor) -> No
                                   stream_ptr(out.device)), "seva_plucker_f32")
 
 
+@_audited("c_concat", "uc_concat")
 def cond_concat(plucker_maps: torch.Tensor, mask_u8: torch.Tensor, c_concat: torch.Tensor, uc_concat: torch.Tensor) -> None:
     """c_concat = [mask | plucker], uc_concat = [0 | plucker] (seva_cond_concat_f32)."""
     require_cuda(plucker_maps, mask_u8, c_concat, uc_concat)
@@ -781,6 +983,7 @@ def cond_concat(plucker_maps: torch.Tensor, mask_u8: torch.Tensor, c_concat: tor
           "seva_cond_concat_f32")
 
 
+@_audited("out")
 def image_area_crop(src: torch.Tensor, out: torch.Tensor, *, rh: int, rw: int, ct: int = 0, cl: int = 0, pad_value: float = 0.0,
                     out_mul: float = 1.0, out_add: float = 0.0, context_rgb: torch.Tensor | None = None) -> None:
     """Source conversion + alpha compositing + F.interpolate(mode="area") to (rh, rw) + the (H, W) window at (ct, cl) of the
@@ -873,6 +1076,7 @@ def frame_metrics(a: torch.Tensor, b: torch.Tensor, sse: torch.Tensor, ssim_sum:
 LPIPS_CPAD = 64  # channels of the prepared first-conv operand
 
 
+@_audited("out_f16")
 def lpips_prepare(x: torch.Tensor, out_f16: torch.Tensor) -> None:
     """x: uint8 (n,H,W,3), images dense, any image pitch -- or fp32 (n,3,H,W) in [-1, 1], planes dense, any image pitch (taken
     through the uint8 rule of `rgb_to_u8`) -> out_f16: (n,H,W,64) contiguous, the scaling layer's output in channels 0..2,
@@ -890,6 +1094,7 @@ def lpips_prepare(x: torch.Tensor, out_f16: torch.Tensor) -> None:
                                         stream_ptr(x.device)), "seva_lpips_prepare_f16")
 
 
+@_audited("relu_out", "pool_out")
 def lpips_relu_pool(x: torch.Tensor, relu_out: torch.Tensor, pool_out: torch.Tensor | None = None) -> None:
     """x: f16 (n,h,w,c) contiguous, c % 64 == 0 -> relu_out (n,h,w,c) = relu(x) (may be x itself) and, when given, pool_out
     (n,h//2,w//2,c) = its 2 x 2 / stride-2 max-pool, floor; NaN -> NaN in both (seva_lpips_relu_pool_f16)."""

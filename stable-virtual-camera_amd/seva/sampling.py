@@ -25,7 +25,7 @@ import numpy as np
 import torch
 from tqdm import tqdm
 
-from . import _native, _stepgraph, ops
+from . import _native, _stepgraph, audit, ops
 from ._native import SevaNativeError
 
 
@@ -365,7 +365,7 @@ class EulerEDMSampler(object):
 
     def __init__(self, discretization: DDPMDiscretization, guider, num_steps: int | None = None,
                  verbose: bool = False, device: str | torch.device = "cuda", s_churn=0.0, s_tmin=0.0,
-                 s_tmax=float("inf"), s_noise=1.0, solver: str | None = None):
+                 s_tmax=float("inf"), s_noise=1.0, solver: str | None = None, check_finite: bool | None = None):
         if solver is None:
             solver = os.environ.get("SEVA_SOLVER") or "euler"
         if solver not in SOLVERS:
@@ -373,6 +373,8 @@ class EulerEDMSampler(object):
         if solver == "dpmpp2m" and s_churn > 0:
             raise ValueError("solver 'dpmpp2m' is deterministic: it has no stochastic form here, s_churn must be 0")
         self.solver = solver
+        # True: one ops.tensor_range over the final latent after the last step; an inf / NaN raises.  None: SEVA_CHECK_FINITE=1.  Off by default
+        self.check_finite = audit.check_finite_from_env() if check_finite is None else bool(check_finite)
         # multistep history (dpmpp2m only): the previous step's guided denoised latent D-, its sigma, and whether they are valid.
         # Owned by the sampler and cleared by `prepare_sampling_loop`; the buffer itself persists (the whole-step hipGraph holds
         # its address) and is never read while `_ms_have` is False.
@@ -539,7 +541,8 @@ class EulerEDMSampler(object):
 
     def _multistep_dispatch(self, sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs):
         cache = self._step_graphs
-        use_graph = (x.is_cuda and not cache.disabled and _stepgraph.enabled() and self.cfg_split is None
+        # (under an audit recorder the step is neither captured nor replayed: its launches must run, and be seen, one by one)
+        use_graph = (x.is_cuda and not cache.disabled and _stepgraph.enabled() and self.cfg_split is None and ops._AUDIT is None
                      and not torch.cuda.is_current_stream_capturing())
         if not use_graph:
             return self._multistep_math(sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs)
@@ -557,6 +560,7 @@ class EulerEDMSampler(object):
                     lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, denoiser, scale, cond, uc, guider_kwargs),
                     (sigma, next_sigma, x, prev_sigma))
                 cache.captures += 1
+                ent.keep = getattr(self.guider, "_rule_cache", None)  # the graph reads the warm-up step's rule tensor: it must outlive `reset_rule_cache`
             except Exception as e:
                 import warnings
 
@@ -587,7 +591,8 @@ class EulerEDMSampler(object):
         cache = self._step_graphs
         # (CFG-split steps are not captured as one graph: the per-step all-gather runs eagerly between the two ranks;
         #  the network call itself is still replayed from its own hipGraph)
-        use_graph = (x.is_cuda and not cache.disabled and _stepgraph.enabled() and self.cfg_split is None
+        # (under an audit recorder the step is neither captured nor replayed: its launches must run, and be seen, one by one)
+        use_graph = (x.is_cuda and not cache.disabled and _stepgraph.enabled() and self.cfg_split is None and ops._AUDIT is None
                      and not torch.cuda.is_current_stream_capturing())
         if not use_graph:
             return self._step_math(sigma, next_sigma, x, eps, denoiser, scale, cond, uc, gamma, guider_kwargs)
@@ -607,6 +612,7 @@ class EulerEDMSampler(object):
                     lambda s, n, xx, ee: self._step_math(s, n, xx, ee, denoiser, scale, cond, uc, gamma, guider_kwargs),
                     (sigma, next_sigma, x, eps))
                 cache.captures += 1
+                ent.keep = getattr(self.guider, "_rule_cache", None)  # the graph reads the warm-up step's rule tensor: it must outlive `reset_rule_cache`
             except Exception as e:  # a step that cannot be captured (foreign denoiser with host syncs, ...) runs eagerly
                 import warnings
 
@@ -638,6 +644,8 @@ class EulerEDMSampler(object):
         # producer (csrc/gemm.hip) left a wrong tile behind -- make that an error instead of a silently wrong sample
         if x.is_cuda:
             ops.check_handoffs()
+            if self.check_finite:
+                audit.check_finite(x)
         return x
 
 
