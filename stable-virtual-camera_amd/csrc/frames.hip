@@ -2,8 +2,8 @@
 // seva/eval.py) and decoded frames -> uint8 (save_output).  Memory-bound elementwise kernels, one thread per output pixel
 // (all three channels).  The arithmetic contract is in include/seva_hip.h: every fp32 operation is rounded on its own.  The
 // file is built with -ffp-contract=off AND spells each operation as __fadd_rn / __fmul_rn / __fdiv_rn, so no FMA and no
-// reciprocal-multiply can form whatever the flags are.
-#include "seva_common.h"
+// reciprocal-multiply can form whatever the flags are.  The uint8 rule itself (frame_u8) is in frame_common.h, shared with the scores.
+#include "frame_common.h"
 
 namespace {
 
@@ -84,15 +84,6 @@ __global__ void image_area_crop_kernel(const seva_image_desc d, const int affine
     o[plane] = g;
     o[2 * plane] = b;
   }
-}
-
-// (v + 1) / 2 * 255 -> clamp -> truncate; the comparisons are false for a NaN, which therefore gives 0
-__device__ __forceinline__ uint32_t frame_u8(float v) {
-  float t = __fdiv_rn(__fadd_rn(v, 1.0f), 2.0f);
-  t = __fmul_rn(t, 255.0f);
-  t = t > 0.0f ? t : 0.0f;
-  t = t < 255.0f ? t : 255.0f;
-  return (uint32_t)(int)t;
 }
 
 // One thread per group of 4 consecutive pixels of one image: 12 output bytes = three 32-bit stores where the image's output

@@ -11,30 +11,20 @@
 //   lpips_layer_kernel       per pixel: unit-normalise both feature vectors over the channels, d = sum_c w[c] (na_c - nb_c)^2.  C / 8
 //                            lanes hold a pixel (8 channels = one 16-byte load per operand and lane); two xor-butterflies give every lane
 //                            the two norms, a third gives d.  A workgroup covers 256 consecutive pixels of one frame pair; the
-//                            pixels' d are widened to fp64, summed per lane in pixel order and then by a fixed tree into the slab
+//                            pixels' d are widened to fp64, summed per lane in pixel order and then by the fixed tree (block_tree,
+//                            frame_common.h) into the slab
 //                            [n][chunks]
-//   lpips_sum_kernel         one workgroup per pair sums its slab row in a fixed order (as frame_metrics_sum_kernel)
+//   lpips_sum_kernel         one workgroup per pair folds its slab row in a fixed order (slab_fold, frame_common.h)
 // No atomics: the result of a pair depends on that pair alone and repeats bit for bit.
 #include <math.h>
 
-#include "seva_common.h"
+#include "frame_common.h"
 
 namespace {
 
 constexpr int LP_THREADS = 256;
 constexpr int LP_PIXELS = 256;  // pixels of one frame pair per workgroup of the layer kernel
 constexpr int LP_CPAD = 64;     // channels of the prepared operand
-
-enum { KIND_U8 = 0, KIND_F32 = 1 };
-
-// the uint8 rule of seva_rgb_to_u8 (frames.hip): (v + 1) / 2 * 255 -> clamp -> truncate; a NaN gives 0
-__device__ __forceinline__ uint32_t lpips_u8(float v) {
-  float t = __fdiv_rn(__fadd_rn(v, 1.0f), 2.0f);
-  t = __fmul_rn(t, 255.0f);
-  t = t > 0.0f ? t : 0.0f;
-  t = t < 255.0f ? t : 255.0f;
-  return (uint32_t)(int)t;
-}
 
 struct LpipsScaling {
   float shift[3], scale[3];
@@ -53,10 +43,10 @@ __global__ __launch_bounds__(LP_THREADS) void lpips_prepare_kernel(const void* _
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       uint32_t u;
-      if (KIND == KIND_U8)
+      if (KIND == FRAME_U8)
         u = ((const uint8_t*)src)[img * pitch_n + p * 3 + c];
       else
-        u = lpips_u8(((const float*)src)[img * pitch_n + (int64_t)c * hw + p]);
+        u = frame_u8(((const float*)src)[img * pitch_n + (int64_t)c * hw + p]);
       float x = __fsub_rn(__fdiv_rn((float)u, 127.5f), 1.0f);
       x = __fdiv_rn(__fsub_rn(x, sc.shift[c]), sc.scale[c]);
       v[c] = (half_t)x;  // one round-to-nearest-even
@@ -121,17 +111,6 @@ __device__ __forceinline__ float pixel_sum(float s) {
   return s;
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-  for (int s = LP_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 template <int L>  // lanes per pixel: C = 8 L
 __global__ __launch_bounds__(LP_THREADS) void lpips_layer_kernel(const half_t* __restrict__ fa, const half_t* __restrict__ fb,
                                                                  const int64_t pitch_a, const int64_t pitch_b, const float* __restrict__ w,
@@ -178,17 +157,16 @@ __global__ __launch_bounds__(LP_THREADS) void lpips_layer_kernel(const half_t* _
     d = pixel_sum<L>(d);
     if (ok && j == 0) acc += (double)d;
   }
-  const double s = block_sum(acc, red);
+  const double s = block_tree<LP_THREADS>(acc, red, [](double a, double b) { return a + b; });
   if (t == 0) part[blockIdx.x] = s;
 }
 
-// one workgroup per pair: thread t sums chunks t, t + 256, ... in that order, then the same fixed tree
+// one workgroup per pair folds its row of the slab
 __global__ __launch_bounds__(LP_THREADS) void lpips_sum_kernel(const double* __restrict__ part, const int chunks, double* __restrict__ out) {
   __shared__ double red[LP_THREADS];
   const int t = threadIdx.x, img = blockIdx.x;
-  double s = 0.0;
-  for (int i = t; i < chunks; i += LP_THREADS) s += part[(int64_t)img * chunks + i];
-  s = block_sum(s, red);
+  const double s = slab_fold<LP_THREADS>(0.0, chunks, [&](int i) { return part[(int64_t)img * chunks + i]; }, red,
+                                         [](double a, double b) { return a + b; });
   if (t == 0) out[img] = s;
 }
 
@@ -200,22 +178,20 @@ extern "C" int seva_lpips_prepare_f16(const void* src, int64_t src_pitch_n, int3
                                       seva_stream_t stream) {
   SEVA_REQUIRE(src && out_f16, "lpips_prepare: null src or out_f16");
   SEVA_REQUIRE(n > 0 && H > 0 && W > 0, "lpips_prepare: bad sizes n=%d H=%d W=%d", n, H, W);
-  SEVA_REQUIRE(kind == KIND_U8 || kind == KIND_F32, "lpips_prepare: kind=%d (0: uint8 NHWC, 1: fp32 NCHW)", kind);
+  if (int rc = frame_checks("lpips_prepare", kind, H, W, src, src_pitch_n)) return rc;
   const int64_t hw = (int64_t)H * W;
-  SEVA_REQUIRE(src_pitch_n >= 3 * hw, "lpips_prepare: image pitch %lld < 3*H*W", (long long)src_pitch_n);
-  SEVA_REQUIRE(kind == KIND_U8 || (((uintptr_t)src) & 3) == 0, "lpips_prepare: fp32 frames must be 4-byte aligned");
   SEVA_REQUIRE((((uintptr_t)out_f16) & 15) == 0, "lpips_prepare: out_f16 must be 16-byte aligned");
   const int64_t pixels = (int64_t)n * hw;
   const int64_t blocks = (pixels * 8 + LP_THREADS - 1) / LP_THREADS;
-  SEVA_REQUIRE(blocks <= 0x7fffffffLL, "lpips_prepare: n*H*W = %lld exceeds the grid", (long long)pixels);
+  SEVA_REQUIRE(grid_fits(blocks), "lpips_prepare: n*H*W = %lld exceeds the grid", (long long)pixels);
   const LpipsScaling sc = {{-.030f, -.088f, -.188f}, {.458f, .448f, .450f}};
   hipStream_t s = (hipStream_t)stream;
-  SevaProfScope prof(4, (double)pixels * (LP_CPAD * 2.0 + (kind == KIND_U8 ? 3.0 : 12.0)), s);
-  if (kind == KIND_U8)
-    hipLaunchKernelGGL(lpips_prepare_kernel<KIND_U8>, dim3((unsigned)blocks), dim3(LP_THREADS), 0, s, src, src_pitch_n, (half_t*)out_f16,
+  SevaProfScope prof(4, (double)pixels * (LP_CPAD * 2.0 + (kind == FRAME_U8 ? 3.0 : 12.0)), s);
+  if (kind == FRAME_U8)
+    hipLaunchKernelGGL(lpips_prepare_kernel<FRAME_U8>, dim3((unsigned)blocks), dim3(LP_THREADS), 0, s, src, src_pitch_n, (half_t*)out_f16,
                        pixels, hw, sc);
   else
-    hipLaunchKernelGGL(lpips_prepare_kernel<KIND_F32>, dim3((unsigned)blocks), dim3(LP_THREADS), 0, s, src, src_pitch_n, (half_t*)out_f16,
+    hipLaunchKernelGGL(lpips_prepare_kernel<FRAME_F32>, dim3((unsigned)blocks), dim3(LP_THREADS), 0, s, src, src_pitch_n, (half_t*)out_f16,
                        pixels, hw, sc);
   return seva_check_launch("lpips_prepare_kernel");
 }
@@ -229,7 +205,7 @@ extern "C" int seva_lpips_relu_pool_f16(const void* x, void* relu_out, void* poo
   SEVA_REQUIRE(pool_out != x && pool_out != relu_out, "lpips_relu_pool: pool_out must not be x or relu_out");
   const int64_t total = (int64_t)n * ((h + 1) / 2) * ((w + 1) / 2) * (c / 8);
   const int64_t blocks = (total + LP_THREADS - 1) / LP_THREADS;
-  SEVA_REQUIRE(blocks <= 0x7fffffffLL, "lpips_relu_pool: %lld lanes exceed the grid", (long long)total);
+  SEVA_REQUIRE(grid_fits(blocks), "lpips_relu_pool: %lld lanes exceed the grid", (long long)total);
   hipStream_t s = (hipStream_t)stream;
   const double elems = (double)n * h * w * c;
   SevaProfScope prof(4, elems * 4.0 + (pool_out ? (double)n * (h / 2) * (w / 2) * c * 2.0 : 0.0), s);
@@ -259,7 +235,7 @@ extern "C" int seva_lpips_layer(const seva_lpips_layer_desc* d, seva_stream_t st
                "lpips_layer: fa, fb must be 16-byte, w 4-byte, out 8-byte aligned");
   const int64_t chunks = layer_chunks(d->hw);
   const int64_t blocks = (int64_t)d->n * chunks;
-  SEVA_REQUIRE(blocks <= 0x7fffffffLL, "lpips_layer: n * chunks = %lld exceeds the grid", (long long)blocks);
+  SEVA_REQUIRE(grid_fits(blocks), "lpips_layer: n * chunks = %lld exceeds the grid", (long long)blocks);
   SEVA_REQUIRE(d->workspace_bytes >= blocks * 8 && (((uintptr_t)d->workspace) & 7) == 0,
                "lpips_layer: workspace of %lld bytes (need %lld, 8-byte aligned)", (long long)d->workspace_bytes, (long long)(blocks * 8));
   double* part = (double*)d->workspace;

@@ -7,11 +7,12 @@
 // One 256-thread workgroup per 32 x 32 tile of one image: the 42 x 42 halo of both frames is staged in LDS as bytes (fp32 sources
 // go through the uint8 rule on the way in), the tile's squared error is summed from the staged bytes, and per channel a horizontal
 // pass writes five LDS planes (x, y, xx, yy, xy) whose vertical pass and SSIM expression stay in registers.  Partials are reduced by
-// a fixed-order tree and written to a slab [n][tiles]; a second kernel (one workgroup per image) sums the slab in a fixed order.
+// the fixed-order tree of frame_common.h and written to a slab [n][tiles]; a second kernel (one workgroup per image) folds the slab
+// in a fixed order (slab_fold, frame_common.h).
 // No atomics: the result of an image depends on that image alone and repeats bit for bit.
 #include <math.h>
 
-#include "seva_common.h"
+#include "frame_common.h"
 
 namespace {
 
@@ -23,27 +24,16 @@ constexpr int MT_ROW_WORDS = 32;                  // staged row pitch: 128 bytes
 constexpr int MT_ROW_BYTES = 4 * MT_ROW_WORDS;
 constexpr int MT_STAGE_WORDS = MT_HALO * MT_ROW_WORDS;
 
-enum { KIND_U8 = 0, KIND_F32 = 1 };
-
 struct MetricsWeights {
   float g[MT_WIN];
 };
-
-// the uint8 rule of seva_rgb_to_u8 (frames.hip): (v + 1) / 2 * 255 -> clamp -> truncate; a NaN gives 0
-__device__ __forceinline__ uint32_t metrics_u8(float v) {
-  float t = __fdiv_rn(__fadd_rn(v, 1.0f), 2.0f);
-  t = __fmul_rn(t, 255.0f);
-  t = t > 0.0f ? t : 0.0f;
-  t = t < 255.0f ? t : 255.0f;
-  return (uint32_t)(int)t;
-}
 
 // Stages rows y0 .. y0+41, bytes 3*x0 .. 3*x0+127 of one frame's row-interleaved RGB into `st`; everything outside the image is 0.
 template <int KIND>
 __device__ __forceinline__ void stage_frame(uint32_t* st, const void* base, int64_t pitch_n, int img, int H, int W, int y0, int x0) {
   const int t = threadIdx.x;
   const int64_t rowb = (int64_t)W * 3;
-  if (KIND == KIND_U8) {
+  if (KIND == FRAME_U8) {
     const uint8_t* src = (const uint8_t*)base + (int64_t)img * pitch_n;
     const bool aligned = ((((uintptr_t)src) | (uintptr_t)rowb) & 3) == 0;  // 3 * x0 = 96 * tile is a multiple of 4
     for (int i = t; i < MT_STAGE_WORDS; i += MT_THREADS) {
@@ -76,7 +66,7 @@ __device__ __forceinline__ void stage_frame(uint32_t* st, const void* base, int6
           const int e = 4 * w + k;  // byte of the staged row: pixel e / 3, channel e % 3
           const int px = e / 3, c = e - 3 * px;
           const int x = x0 + px;
-          if (x < W) v |= metrics_u8(src[(int64_t)c * plane + (int64_t)y * W + x]) << (8 * k);
+          if (x < W) v |= frame_u8(src[(int64_t)c * plane + (int64_t)y * W + x]) << (8 * k);
         }
       }
       st[i] = v;
@@ -174,48 +164,31 @@ __global__ __launch_bounds__(MT_THREADS) void frame_metrics_tile_kernel(const se
     }
   }
 
-  red_s[t] = ssum;
-  red_e[t] = sse;
-  __syncthreads();
-  for (int s = MT_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      red_s[t] += red_s[t + s];
-      red_e[t] += red_e[t + s];
-    }
-    __syncthreads();
-  }
+  using P = Pair<double, uint32_t>;
+  const P r = block_tree<MT_THREADS>(P{ssum, sse}, PairRed<double, uint32_t>{red_s, red_e}, [](P x, P y) { return P{x.a + y.a, x.b + y.b}; });
   if (t == 0) {
-    sse_part[blockIdx.x] = red_e[0];
-    if (d.ssim) ssim_part[blockIdx.x] = red_s[0];
+    sse_part[blockIdx.x] = r.b;
+    if (d.ssim) ssim_part[blockIdx.x] = r.a;
   }
 }
 
-// one workgroup per image: thread t sums tiles t, t + 256, ... in that order, then the same fixed tree
+// one workgroup per image folds its row of the slab
 __global__ __launch_bounds__(MT_THREADS) void frame_metrics_sum_kernel(const double* __restrict__ ssim_part,
                                                                        const uint32_t* __restrict__ sse_part, int tiles,
                                                                        int64_t* __restrict__ sse, double* __restrict__ ssim_sum) {
   __shared__ double red_s[MT_THREADS];
   __shared__ unsigned long long red_e[MT_THREADS];
   const int t = threadIdx.x, img = blockIdx.x;
-  double s = 0.0;
-  unsigned long long e = 0;
-  for (int i = t; i < tiles; i += MT_THREADS) {
-    e += sse_part[(int64_t)img * tiles + i];
-    if (ssim_sum) s += ssim_part[(int64_t)img * tiles + i];
-  }
-  red_s[t] = s;
-  red_e[t] = e;
-  __syncthreads();
-  for (int k = MT_THREADS / 2; k > 0; k >>= 1) {
-    if (t < k) {
-      red_s[t] += red_s[t + k];
-      red_e[t] += red_e[t + k];
-    }
-    __syncthreads();
-  }
+  using P = Pair<double, unsigned long long>;
+  const auto part = [&](int i) {  // (the SSIM partials exist only where SSIM was asked for)
+    const int64_t k = (int64_t)img * tiles + i;
+    return P{ssim_sum ? ssim_part[k] : 0.0, sse_part[k]};
+  };
+  const P r = slab_fold<MT_THREADS>(P{0.0, 0}, tiles, part, PairRed<double, unsigned long long>{red_s, red_e},
+                                    [](P x, P y) { return P{x.a + y.a, x.b + y.b}; });
   if (t == 0) {
-    sse[img] = (int64_t)red_e[0];
-    if (ssim_sum) ssim_sum[img] = red_s[0];
+    sse[img] = (int64_t)r.b;
+    if (ssim_sum) ssim_sum[img] = r.a;
   }
 }
 
@@ -234,11 +207,8 @@ extern "C" int seva_frame_metrics_size(int32_t n, int32_t H, int32_t W, int64_t*
 extern "C" int seva_frame_metrics(const seva_metrics_desc* d, seva_stream_t stream) {
   SEVA_REQUIRE(d && d->a && d->b && d->sse && d->workspace, "frame_metrics: null descriptor, a, b, sse or workspace");
   SEVA_REQUIRE(d->n > 0 && d->H > 0 && d->W > 0, "frame_metrics: bad sizes n=%d H=%d W=%d", d->n, d->H, d->W);
-  SEVA_REQUIRE(d->kind == KIND_U8 || d->kind == KIND_F32, "frame_metrics: kind=%d (0: uint8 NHWC, 1: fp32 NCHW)", d->kind);
+  if (int rc = frame_checks("frame_metrics", d->kind, d->H, d->W, d->a, d->a_pitch_n, d->b, d->b_pitch_n)) return rc;
   const int64_t elems = 3 * (int64_t)d->H * d->W;
-  SEVA_REQUIRE(d->a_pitch_n >= elems && d->b_pitch_n >= elems, "frame_metrics: image pitches (%lld, %lld) < 3*H*W",
-               (long long)d->a_pitch_n, (long long)d->b_pitch_n);
-  SEVA_REQUIRE(d->kind == KIND_U8 || ((((uintptr_t)d->a) | ((uintptr_t)d->b)) & 3) == 0, "frame_metrics: fp32 frames must be 4-byte aligned");
   SEVA_REQUIRE(d->ssim || (!d->ssim_sum && !d->ssim_map), "frame_metrics: ssim_sum / ssim_map given without ssim");
   if (d->ssim) {
     SEVA_REQUIRE(d->ssim_sum, "frame_metrics: ssim needs ssim_sum");
@@ -246,7 +216,7 @@ extern "C" int seva_frame_metrics(const seva_metrics_desc* d, seva_stream_t stre
   }
   const int64_t tiles = metrics_tiles(d->H, d->W);
   const int64_t blocks = (int64_t)d->n * tiles;
-  SEVA_REQUIRE(blocks <= 0x7fffffffLL, "frame_metrics: n * tiles = %lld exceeds the grid", (long long)blocks);
+  SEVA_REQUIRE(grid_fits(blocks), "frame_metrics: n * tiles = %lld exceeds the grid", (long long)blocks);
   SEVA_REQUIRE(d->workspace_bytes >= blocks * 12 && (((uintptr_t)d->workspace) & 7) == 0,
                "frame_metrics: workspace of %lld bytes (need %lld, 8-byte aligned)", (long long)d->workspace_bytes, (long long)(blocks * 12));
 
@@ -263,12 +233,12 @@ extern "C" int seva_frame_metrics(const seva_metrics_desc* d, seva_stream_t stre
   uint32_t* sse_part = (uint32_t*)((char*)d->workspace + blocks * 8);
   const int tiles_x = (d->W + MT_TILE - 1) / MT_TILE;
   hipStream_t s = (hipStream_t)stream;
-  SevaProfScope prof(4, (double)d->n * elems * (d->kind == KIND_U8 ? 2.0 : 8.0), s);
-  if (d->kind == KIND_U8)
-    hipLaunchKernelGGL(frame_metrics_tile_kernel<KIND_U8>, dim3((unsigned)blocks), dim3(MT_THREADS), 0, s, *d, wt, tiles_x, (int)tiles,
+  SevaProfScope prof(4, (double)d->n * elems * (d->kind == FRAME_U8 ? 2.0 : 8.0), s);
+  if (d->kind == FRAME_U8)
+    hipLaunchKernelGGL(frame_metrics_tile_kernel<FRAME_U8>, dim3((unsigned)blocks), dim3(MT_THREADS), 0, s, *d, wt, tiles_x, (int)tiles,
                        ssim_part, sse_part);
   else
-    hipLaunchKernelGGL(frame_metrics_tile_kernel<KIND_F32>, dim3((unsigned)blocks), dim3(MT_THREADS), 0, s, *d, wt, tiles_x, (int)tiles,
+    hipLaunchKernelGGL(frame_metrics_tile_kernel<FRAME_F32>, dim3((unsigned)blocks), dim3(MT_THREADS), 0, s, *d, wt, tiles_x, (int)tiles,
                        ssim_part, sse_part);
   if (int rc = seva_check_launch("frame_metrics_tile_kernel")) return rc;
   hipLaunchKernelGGL(frame_metrics_sum_kernel, dim3((unsigned)d->n), dim3(MT_THREADS), 0, s, ssim_part, sse_part, (int)tiles, d->sse,

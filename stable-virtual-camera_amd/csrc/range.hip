@@ -13,9 +13,9 @@
 // Work split: the tensor is cut into units -- 16-byte vectors where base and pitch allow them (the vectors of a row; a dense
 // tensor is one long row and may end in a partial vector, read element by element), single elements otherwise.  Workgroup w
 // takes the units of elements [w * share, (w + 1) * share), 64-bit indices throughout.  Each workgroup flushes its table to
-// workspace[w][72]; a second kernel (one workgroup per word) adds the partial tables.  No global atomics; the counts are integers,
-// so the result does not depend on how the tensor was cut.
-#include "seva_common.h"
+// workspace[w][72]; a second kernel (one workgroup per word) folds the partial tables (slab_fold, frame_common.h; the extrema go
+// through the same fixed tree).  No global atomics; the counts are integers, so the result does not depend on how the tensor was cut.
+#include "frame_common.h"
 
 namespace {
 
@@ -214,25 +214,18 @@ __global__ __launch_bounds__(RG_THREADS) void tensor_range_kernel(const char* __
     if (lane == 0) out[w] = s;
   }
   __syncthreads();
-  tab[t] = acc.mx;
-  tab[RG_THREADS + t] = acc.mn;
-  __syncthreads();
-  for (int s = RG_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      tab[t] = max(tab[t], tab[t + s]);
-      tab[RG_THREADS + t] = min(tab[RG_THREADS + t], tab[RG_THREADS + t + s]);
-    }
-    __syncthreads();
-  }
+  using P = Pair<uint32_t, uint32_t>;  // (max, min)
+  const P ext = block_tree<RG_THREADS>(P{acc.mx, acc.mn}, PairRed<uint32_t, uint32_t>{tab, tab + RG_THREADS},
+                                       [](P x, P y) { return P{x.a > y.a ? x.a : y.a, x.b < y.b ? x.b : y.b}; });
   if (t == 0) {
-    out[W_MAXABS] = tab[0];
-    out[W_MINABS] = tab[RG_THREADS];
+    out[W_MAXABS] = ext.a;
+    out[W_MINABS] = ext.b;
     out[W_TOTAL] = 0;
     out[W_TOTAL + 1] = 0;
   }
 }
 
-// one workgroup per output word: thread t folds partial tables t, t + 256, ..., then a tree
+// one workgroup per output word folds that word of the partial tables
 __global__ __launch_bounds__(RG_THREADS) void tensor_range_sum_kernel(const uint64_t* __restrict__ part, const int64_t wgs, const int dt,
                                                                       const uint64_t total, uint64_t* __restrict__ out) {
   __shared__ uint64_t red[RG_THREADS];
@@ -241,20 +234,10 @@ __global__ __launch_bounds__(RG_THREADS) void tensor_range_sum_kernel(const uint
     if (t == 0) out[w] = w == W_TOTAL ? total : 0;
     return;
   }
-  const bool is_max = w == W_MAXABS, is_min = w == W_MINABS;
-  uint64_t s = is_min ? 0xFFFFFFFFull : 0;
-  for (int64_t i = t; i < wgs; i += RG_THREADS) {
-    const uint64_t p = part[i * RG_WORDS + w];
-    s = is_max ? max(s, p) : is_min ? min(s, p) : s + p;
-  }
-  red[t] = s;
-  __syncthreads();
-  for (int k = RG_THREADS / 2; k > 0; k >>= 1) {
-    if (t < k) red[t] = is_max ? max(red[t], red[t + k]) : is_min ? min(red[t], red[t + k]) : red[t] + red[t + k];
-    __syncthreads();
-  }
+  const bool is_max = w == W_MAXABS, is_min = w == W_MINABS;  // (uniform over the workgroup)
+  const auto op = [=](uint64_t a, uint64_t b) { return is_max ? (a > b ? a : b) : is_min ? (a < b ? a : b) : a + b; };
+  uint64_t r = slab_fold<RG_THREADS>((uint64_t)(is_min ? 0xFFFFFFFFull : 0), wgs, [&](int64_t i) { return part[i * RG_WORDS + w]; }, red, op);
   if (t == 0) {
-    uint64_t r = red[0];
     if (is_max) r = r ? to_f32_bits(dt, (uint32_t)r) : 0;
     if (is_min) r = r != 0xFFFFFFFFull ? to_f32_bits(dt, (uint32_t)r) : 0x7F800000ull;
     out[w] = r;

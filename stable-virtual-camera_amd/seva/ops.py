@@ -150,11 +150,40 @@ def _audit_views(op: str, name: str, t: torch.Tensor, a: dict) -> list:
     return [(name, off, rows, cols, pitch) for off, rows, cols, pitch in _as_2d(t)]
 
 
+def _size_query(fn, *dims: int) -> int:
+    """what a `seva_*_size(dims..., &bytes)` query of the library reports"""
+    size = C.c_int64()
+    check(fn(*(int(d) for d in dims), C.byref(size)), fn.__name__)
+    return size.value
+
+
+def _workspace(workspace: torch.Tensor | None, need: int, device, who: str) -> torch.Tensor:
+    """the caller's uint8 workspace, checked against `need` elements; None: allocated here"""
+    if workspace is None:
+        workspace = torch.empty(need, dtype=U8, device=device)
+    assert workspace.dtype == U8 and workspace.is_contiguous() and workspace.numel() >= need, f"{who} workspace too small"
+    return workspace
+
+
+def _dense_planes(x: torch.Tensor, what: str) -> None:
+    H, W = x.shape[2:]
+    assert x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W, f"{what} planes must be dense"
+
+
+def _frame_layout(x: torch.Tensor) -> tuple[int, int, int, int]:
+    """(kind, n, H, W) of a frame batch: the ABI's kind 0 = uint8 (n,H,W,3), dense images, 1 = fp32 (n,3,H,W), dense planes; any image pitch"""
+    if x.dtype == U8:
+        n, H, W, c = x.shape
+        assert c == 3 and x.stride(3) == 1 and x.stride(2) == 3 and x.stride(1) == 3 * W, "uint8 frames: (n,H,W,3) with dense images"
+        return 0, n, H, W
+    n, c, H, W = x.shape
+    assert c == 3 and x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W, "fp32 frames: (n,3,H,W) with dense planes"
+    return 1, n, H, W
+
+
 def tensor_range_workspace_numel(rows: int, cols: int) -> int:
     """uint8 elements of `tensor_range(workspace=...)`: one 72-word partial table per workgroup of the counting kernel."""
-    size = C.c_int64()
-    check(_lib().seva_tensor_range_size(int(rows), int(cols), C.byref(size)), "seva_tensor_range_size")
-    return size.value
+    return _size_query(_lib().seva_tensor_range_size, rows, cols)
 
 
 def tensor_range(x: torch.Tensor, out: torch.Tensor | None = None, *, rows: int | None = None, cols: int | None = None,
@@ -180,10 +209,7 @@ def tensor_range(x: torch.Tensor, out: torch.Tensor | None = None, *, rows: int 
     if out is None:
         out = torch.empty(RANGE_WORDS, dtype=torch.int64, device=x.device)
     assert out.dtype == torch.int64 and out.numel() == RANGE_WORDS and out.is_contiguous()
-    need = tensor_range_workspace_numel(rows, cols)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=U8, device=x.device)
-    assert workspace.dtype == U8 and workspace.is_contiguous() and workspace.numel() >= need, "tensor_range workspace too small"
+    workspace = _workspace(workspace, tensor_range_workspace_numel(rows, cols), x.device, "tensor_range")
     d = nv.RangeDesc()
     d.x, d.dtype, d.rows, d.cols, d.pitch = x.data_ptr(), RANGE_DTYPES[x.dtype], rows, cols, pitch
     d.workspace, d.workspace_bytes, d.out = workspace.data_ptr(), workspace.numel(), out.data_ptr()
@@ -993,7 +1019,7 @@ def image_area_crop(src: torch.Tensor, out: torch.Tensor, *, rh: int, rw: int, c
     require_cuda(src, out, context_rgb)
     assert out.dtype == F32 and out.dim() == 4 and out.shape[1] == 3
     n, _, H, W = out.shape
-    assert out.stride(3) == 1 and out.stride(2) == W and out.stride(1) == H * W, "output planes must be dense"
+    _dense_planes(out, "output")
     d = ImageDesc()
     if src.dtype == torch.uint8:
         assert src.dim() == 4 and src.shape[0] == n and src.shape[3] in (3, 4)
@@ -1023,16 +1049,14 @@ def rgb_to_u8(x: torch.Tensor, out: torch.Tensor) -> None:
     require_cuda(x, out)
     assert x.dtype == F32 and x.dim() == 4 and x.shape[1] == 3 and out.dtype == torch.uint8
     n, _, H, W = x.shape
-    assert x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W, "input planes must be dense"
+    _dense_planes(x, "input")
     assert out.shape == (n, H, W, 3) and out.is_contiguous()
     check(_lib().seva_rgb_to_u8(x.data_ptr(), x.stride(0), out.data_ptr(), n, H, W, stream_ptr(x.device)), "seva_rgb_to_u8")
 
 
 def frame_metrics_workspace_numel(n: int, H: int, W: int) -> int:
     """uint8 elements of `frame_metrics(workspace=...)`: one (fp64, u32) partial per 32 x 32 tile of every image."""
-    size = C.c_int64()
-    check(_lib().seva_frame_metrics_size(int(n), int(H), int(W), C.byref(size)), "seva_frame_metrics_size")
-    return size.value
+    return _size_query(_lib().seva_frame_metrics_size, n, H, W)
 
 
 def frame_metrics(a: torch.Tensor, b: torch.Tensor, sse: torch.Tensor, ssim_sum: torch.Tensor | None = None,
@@ -1045,26 +1069,13 @@ def frame_metrics(a: torch.Tensor, b: torch.Tensor, sse: torch.Tensor, ssim_sum:
     require_cuda(a, b, sse, ssim_sum, ssim_map, workspace)
     assert a.dim() == 4 and a.shape == b.shape and a.dtype == b.dtype and a.dtype in (U8, F32)
     d = MetricsDesc()
-    if a.dtype == U8:
-        n, H, W, c = a.shape
-        assert c == 3
-        for x in (a, b):
-            assert x.stride(3) == 1 and x.stride(2) == 3 and x.stride(1) == 3 * W, "uint8 frames: (n,H,W,3) with dense images"
-        d.kind = 0
-    else:
-        n, c, H, W = a.shape
-        assert c == 3
-        for x in (a, b):
-            assert x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W, "fp32 frames: (n,3,H,W) with dense planes"
-        d.kind = 1
+    d.kind, n, H, W = _frame_layout(a)
+    _frame_layout(b)
     assert sse.dtype == torch.int64 and sse.shape == (n,) and sse.is_contiguous()
     assert ssim_sum is None or (ssim_sum.dtype == torch.float64 and ssim_sum.shape == (n,) and ssim_sum.is_contiguous())
     assert ssim_map is None or (ssim_sum is not None and ssim_map.dtype == F32 and ssim_map.is_contiguous()
                                 and ssim_map.shape == (n, 3, H - 10, W - 10))
-    need = frame_metrics_workspace_numel(n, H, W)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=U8, device=a.device)
-    assert workspace.dtype == U8 and workspace.is_contiguous() and workspace.numel() >= need, "frame_metrics workspace too small"
+    workspace = _workspace(workspace, frame_metrics_workspace_numel(n, H, W), a.device, "frame_metrics")
     d.a, d.b, d.sse, d.ssim_sum, d.ssim_map, d.workspace = a.data_ptr(), b.data_ptr(), sse.data_ptr(), ptr(ssim_sum), ptr(ssim_map), \
         workspace.data_ptr()
     d.a_pitch_n, d.b_pitch_n, d.workspace_bytes = a.stride(0), b.stride(0), workspace.numel()
@@ -1083,14 +1094,9 @@ def lpips_prepare(x: torch.Tensor, out_f16: torch.Tensor) -> None:
     exact zeros above (seva_lpips_prepare_f16)."""
     require_cuda(x, out_f16)
     assert x.dim() == 4 and x.dtype in (U8, F32)
-    if x.dtype == U8:
-        n, H, W, c = x.shape
-        assert c == 3 and x.stride(3) == 1 and x.stride(2) == 3 and x.stride(1) == 3 * W, "uint8 frames: (n,H,W,3) with dense images"
-    else:
-        n, c, H, W = x.shape
-        assert c == 3 and x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W, "fp32 frames: (n,3,H,W) with dense planes"
+    kind, n, H, W = _frame_layout(x)
     assert out_f16.dtype == F16 and out_f16.shape == (n, H, W, LPIPS_CPAD) and out_f16.is_contiguous()
-    check(_lib().seva_lpips_prepare_f16(x.data_ptr(), x.stride(0), 0 if x.dtype == U8 else 1, out_f16.data_ptr(), n, H, W,
+    check(_lib().seva_lpips_prepare_f16(x.data_ptr(), x.stride(0), kind, out_f16.data_ptr(), n, H, W,
                                         stream_ptr(x.device)), "seva_lpips_prepare_f16")
 
 
@@ -1109,9 +1115,7 @@ def lpips_relu_pool(x: torch.Tensor, relu_out: torch.Tensor, pool_out: torch.Ten
 
 def lpips_layer_workspace_numel(n: int, hw: int) -> int:
     """uint8 elements of `lpips_layer(workspace=...)`: one fp64 partial per 256 pixels of every pair."""
-    size = C.c_int64()
-    check(_lib().seva_lpips_layer_size(int(n), int(hw), C.byref(size)), "seva_lpips_layer_size")
-    return size.value
+    return _size_query(_lib().seva_lpips_layer_size, n, hw)
 
 
 def lpips_layer(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor | None = None) -> None:
@@ -1125,10 +1129,7 @@ def lpips_layer(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, out: torch.
         assert x.stride(2) == 1 and x.stride(1) == c, "features: (n,hw,C) with dense pixels"
     assert w.dtype == F32 and w.shape == (c,) and w.is_contiguous()
     assert out.dtype == torch.float64 and out.shape == (n,) and out.is_contiguous()
-    need = lpips_layer_workspace_numel(n, hw)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=U8, device=fa.device)
-    assert workspace.dtype == U8 and workspace.is_contiguous() and workspace.numel() >= need, "lpips_layer workspace too small"
+    workspace = _workspace(workspace, lpips_layer_workspace_numel(n, hw), fa.device, "lpips_layer")
     d = LpipsLayerDesc()
     d.fa, d.fb, d.w, d.out, d.workspace = fa.data_ptr(), fb.data_ptr(), w.data_ptr(), out.data_ptr(), workspace.data_ptr()
     d.a_pitch_n, d.b_pitch_n, d.workspace_bytes, d.hw = fa.stride(0), fb.stride(0), workspace.numel(), hw

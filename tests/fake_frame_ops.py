@@ -55,3 +55,12 @@ def rgb_to_u8(x, out):
     t = (t * 255.0).clamp(0, 255)
     t = torch.where(torch.isnan(t), torch.zeros(()), t)
     out.copy_(t.permute(0, 2, 3, 1).to(torch.uint8))
+
+
+def as_u8(x: torch.Tensor) -> torch.Tensor:
+    """(n,H,W,3) uint8 of a frame batch of either kind: uint8 NHWC as it is, fp32 NCHW through the uint8 rule."""
+    if x.dtype == torch.uint8:
+        return x
+    out = torch.empty((x.shape[0], x.shape[2], x.shape[3], 3), dtype=torch.uint8)
+    rgb_to_u8(x, out)
+    return out

@@ -19,14 +19,6 @@ THREADS = PIXELS = 256
 LPIPS_CPAD = 64
 
 
-def _as_u8(x):
-    if x.dtype == torch.uint8:
-        return x
-    out = torch.empty((x.shape[0], x.shape[2], x.shape[3], 3), dtype=torch.uint8)
-    fake_frame_ops.rgb_to_u8(x, out)
-    return out
-
-
 def prepared(u8: torch.Tensor) -> torch.Tensor:
     """uint8 (n,H,W,3) -> f16 (n,H,W,3): x = float(u) / 127.5f; x - 1.0f; x - shift[c]; x / scale[c]; one RNE to f16."""
     x = u8.to(F32)
@@ -39,7 +31,7 @@ def prepared(u8: torch.Tensor) -> torch.Tensor:
 
 def lpips_prepare(x, out_f16):
     out_f16.zero_()
-    out_f16[..., :3] = prepared(_as_u8(x))
+    out_f16[..., :3] = prepared(fake_frame_ops.as_u8(x))
 
 
 def lpips_relu_pool(x, relu_out, pool_out=None):

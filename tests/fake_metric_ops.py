@@ -16,15 +16,6 @@ def weights() -> torch.Tensor:
     return (g / g.sum()).to(torch.float32)
 
 
-def _as_u8(x: torch.Tensor) -> torch.Tensor:
-    """(n,H,W,3) uint8 of either kind."""
-    if x.dtype == torch.uint8:
-        return x
-    out = torch.empty((x.shape[0], x.shape[2], x.shape[3], 3), dtype=torch.uint8)
-    fake_frame_ops.rgb_to_u8(x, out)
-    return out
-
-
 def _pass(v: torch.Tensor, g: torch.Tensor, dim: int) -> torch.Tensor:
     """acc = 0; for k: acc = acc + g[k] * v[k], at valid positions along `dim`."""
     size = v.shape[dim] - (WIN - 1)
@@ -50,7 +41,7 @@ def ssim_map_f32(a_u8: torch.Tensor, b_u8: torch.Tensor) -> torch.Tensor:
 
 def frame_metrics(a, b, sse, ssim_sum=None, ssim_map=None, workspace=None):
     assert a.shape == b.shape and a.dtype == b.dtype
-    ua, ub = _as_u8(a), _as_u8(b)
+    ua, ub = fake_frame_ops.as_u8(a), fake_frame_ops.as_u8(b)
     d = ua.to(torch.int64) - ub.to(torch.int64)
     sse.copy_((d * d).sum(dim=(1, 2, 3)))
     if ssim_sum is None:

@@ -6,34 +6,23 @@ plain dwordx4 accesses, or moved the flag store, would break the protocol silent
 (hipcc cross-compiles for gfx950 without a GPU; ~20 s.)"""
 import os
 import re
-import shutil
-import subprocess
+import sys
 
 import pytest
 
-from conftest import PKG
+from conftest import PKG, ROOT
 
-HIPCC = "/opt/rocm/bin/hipcc"
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import isa_lint  # noqa: E402  (tools/isa_lint.py: the library's compile line and the kernel-body parser)
+
+HIPCC = isa_lint.HIPCC
 KERNEL = re.compile(r"^(_ZN\S*gemm_kernelILi128ELi(?:128|160)ELi1ELi0ELb0ELb0ELb0ELb0ELb1ELi4E(?:Lb0E)?E\S*):\s")  # MODE 1, SPLITK = true
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-def test_splitk_handoff_uses_agent_scope_accesses_and_orders_the_flag(tmp_path):
-    src = os.path.join(PKG, "csrc", "gemm.hip")
-    out = tmp_path / "gemm.s"
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=fast", "-I", os.path.dirname(src),
-                    "--cuda-device-only", "-S", src, "-o", str(out)], check=True, stderr=subprocess.DEVNULL)
-    lines = out.read_text().split("\n")
-    bodies, cur = {}, None
-    for ln in lines:
-        m = KERNEL.match(ln)
-        if m:
-            cur = m.group(1)
-            bodies[cur] = []
-        elif cur is not None:
-            bodies[cur].append(ln.strip())
-            if ln.strip().startswith("s_endpgm"):
-                cur = None
+def test_splitk_handoff_uses_agent_scope_accesses_and_orders_the_flag():
+    asm = isa_lint.compile_to_asm(os.path.join(PKG, "csrc", "gemm.hip"))
+    bodies = {k: v for k, v in isa_lint.kernels(asm).items() if KERNEL.match(k + ": ")}
     assert len(bodies) == 2, list(bodies)  # the 128 x 128 and 128 x 160 split-K conv kernels
     for name, body in bodies.items():
         bn = 160 if "Li160E" in name else 128

@@ -7,8 +7,6 @@ profiles/r03_concurrency_*.log).  With a plain 32-bit first reader (two `v_mov_b
 clean over thousands of launches.  A compiler upgrade that folded the broadcast back into op_sel, or re-packed the shuffle adds, would bring
 the fault back silently; this test fails instead.  tests/test_model_gpu.py holds the run-time check.  (hipcc cross-compiles, ~40 s.)"""
 import os
-import re
-import subprocess
 import sys
 import tarfile
 
@@ -19,37 +17,18 @@ from conftest import PKG, ROOT
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import isa_lint  # noqa: E402  (tools/isa_lint.py: the rule as a scanner over emitted ISA)
 
-HIPCC = "/opt/rocm/bin/hipcc"
-REG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
+HIPCC = isa_lint.HIPCC
+_regs = isa_lint.regs
 
 
-def _regs(text):
-    out = set()
-    for m in REG.finditer(text):
-        out.update([int(m.group(1))] if m.group(1) is not None else range(int(m.group(2)), int(m.group(3)) + 1))
-    return out
-
-
-def _asm(tmp_path, name):
-    src = os.path.join(PKG, "csrc", name + ".hip")
-    out = tmp_path / (name + ".s")
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=fast", "-I", os.path.dirname(src),
-                    "--cuda-device-only", "-S", src, "-o", str(out)], check=True, stderr=subprocess.DEVNULL)
-    bodies, cur = {}, None
-    for ln in out.read_text().split("\n"):
-        m = re.match(r"^(_Z\w+):\s", ln)
-        if m:
-            cur = m.group(1); bodies[cur] = []
-        elif cur is not None:
-            t = ln.split(";")[0].strip()
-            if t: bodies[cur].append(t)
-            if t.startswith("s_endpgm"): cur = None
-    return bodies
+def _asm(name):
+    """{kernel: instruction lines} of one production source, built with the flags the library is built with"""
+    return isa_lint.kernels(isa_lint.compile_to_asm(os.path.join(PKG, "csrc", name + ".hip")))
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-def test_groupnorm_modulation_reads_real_register_pairs(tmp_path):
-    bodies = {k: v for k, v in _asm(tmp_path, "norm").items() if "gn_apply_kernelILb1E" in k}   # DENSE = true
+def test_groupnorm_modulation_reads_real_register_pairs():
+    bodies = {k: v for k, v in _asm("norm").items() if "gn_apply_kernelILb1E" in k}   # DENSE = true
     assert len(bodies) >= 3, list(bodies)
     for name, body in bodies.items():
         pk = [t for t in body if t.startswith("v_pk_fma_f32")]
@@ -58,8 +37,8 @@ def test_groupnorm_modulation_reads_real_register_pairs(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
-def test_fused_ff_layernorm_prologue_adds_shuffle_results_with_plain_ops(tmp_path):
-    bodies = {k: v for k, v in _asm(tmp_path, "ff_fused").items() if "ff_fused8_kernel" in k}
+def test_fused_ff_layernorm_prologue_adds_shuffle_results_with_plain_ops():
+    bodies = {k: v for k, v in _asm("ff_fused").items() if "ff_fused8_kernel" in k}
     assert len(bodies) == 4, list(bodies)
     for name, body in bodies.items():
         perm = [i for i, t in enumerate(body) if t.startswith("ds_bpermute_b32")]

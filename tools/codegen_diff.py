@@ -16,7 +16,6 @@ import re
 import shutil
 import subprocess
 import sys
-import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import isa_lint  # noqa: E402
@@ -27,15 +26,10 @@ FIGURES = (("vgpr", ".vgpr_count"), ("sgpr", ".sgpr_count"), ("vgpr_spill", ".vg
 
 def compile_asm(tree, name):
     csrc = os.path.join(tree, "stable-virtual-camera_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    m = re.search(r"^FLAGS_%s\s*:=\s*(.+)$" % re.escape(os.path.splitext(name)[0]), mk, re.M)
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        res = subprocess.run([isa_lint.HIPCC, *isa_lint.FLAGS, *(m.group(1).split() if m else []), os.path.join(csrc, name), "-o", out],
-                             stderr=subprocess.PIPE, text=True)
-        if res.returncode != 0:
-            sys.exit(f"hipcc failed on {os.path.join(csrc, name)}:\n{res.stderr}")
-        return open(out).read()
+    try:
+        return isa_lint.compile_to_asm(os.path.join(csrc, name), csrc=csrc)
+    except RuntimeError as e:
+        sys.exit(str(e))
 
 
 def figures(asm):
@@ -116,7 +110,7 @@ def demangle(names):
     if not names or not filt:
         return {n: n for n in names}
     res = subprocess.run([filt, *names], capture_output=True, text=True).stdout.split("\n")
-    short = [re.sub(r"^void \(anonymous namespace\)::|\(.*$", "", r) for r in res]
+    short = [re.sub(r"^(void )?\(anonymous namespace\)::|\(.*$", "", r) for r in res]
     return dict(zip(names, short))
 
 

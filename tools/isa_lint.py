@@ -107,18 +107,21 @@ def lint_body(body, horizon=4000):
     return found
 
 
-def file_flags(src):
-    """Per-file flags of the Makefile (FLAGS_<stem> := ...): the lint looks at the code the library is built from."""
-    mk = open(os.path.join(CSRC, "Makefile")).read()
+def file_flags(src, csrc=CSRC):
+    """Per-file flags of csrc's Makefile (FLAGS_<stem> := ...): the lint looks at the code the library is built from."""
+    mk = open(os.path.join(csrc, "Makefile")).read()
     m = re.search(r"^FLAGS_%s\s*:=\s*(.+)$" % re.escape(os.path.splitext(os.path.basename(src))[0]), mk, re.M)
     return m.group(1).split() if m else []
 
 
-def compile_to_asm(src, defines=()):
+def compile_to_asm(src, defines=(), csrc=CSRC):
+    """The gfx950 assembly of one source, built as the library builds it; csrc: the directory whose Makefile states the file's flags."""
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
-        subprocess.run([HIPCC, *FLAGS, *file_flags(src), *[f"-D{d}" for d in defines], "-I", os.path.dirname(src), src, "-o", out],
-                       check=True, stderr=subprocess.DEVNULL)
+        res = subprocess.run([HIPCC, *FLAGS, *file_flags(src, csrc), *[f"-D{d}" for d in defines], "-I", os.path.dirname(src), src, "-o", out],
+                             stderr=subprocess.PIPE, text=True)
+        if res.returncode != 0:
+            raise RuntimeError(f"hipcc failed on {src}:\n{res.stderr}")
         return open(out).read()
 
 
