@@ -25,7 +25,11 @@ csrc/clip.hip, csrc/norm.hip, csrc/elementwise.hip); a kernel trace of this file
   frame_attn2           attn2_kernel<64>   (knob attn_two = 1, lq >= 512)
   joint_split           attn16_kernel<64, true> + attn_combine_kernel  (lk >= 6144 and a workspace)
   joint_split_forced    the same with knob attn_split = 3: 21 key tiles in splits of 7, a ragged last tile in the last split
+  frame_attn16_unsplit  attn16_kernel<64> at lk >= 6144 WITHOUT a workspace: the per-frame regime of the engine passes none, so at the
+                        non-square latents 72x96 / 96x72 (6912 tokens) and 72x128 (9216) one workgroup per query block walks every key
   pv8                   quant_v_fp8_kernel + pv8_kernel<false> (5184 keys) / pv8_kernel<true> + attn_combine_kernel (>= 6144 keys)
+  pv8_unsplit_no_ws     seva_attention_pv8 at >= 6144 keys with split_ws absent: nsplit is still computed as 2, but the split branch
+                        needs the workspace, so the launch falls through to the unsplit pv8_kernel<false> over all 128-key steps
   small                 attn_small_kernel (CLIP: L = 257, head dim 80); batch 1 -> qchunks 8, batch 21 -> qchunks 1
   layernorm c<C>-<out>  layernorm_kernel<NV, 1, OUT> (rows < 65536) against <NV, 4, OUT> (rows >= 65536); NV = 2, 5, 10, 20 for
                         C = 64, 320, 640, 1280; OUT = 0 f16, 1 e4m3, 2 fp32
@@ -225,6 +229,11 @@ ATTN_A = [
     # pv8: the bound of test_attention_fp8_gpu.py::test_kernel_does_the_stated_arithmetic (against the kernel's arithmetic in fp64)
     ("pv8-5184x5184", 5184, 5184, (1, 1, 5), [(1, 1, 1, 0), (1, 1, 1, 3)], {}, "pv8", 4e-3),
     ("pv8-6804x6804", 6804, 6804, (1, 1, 5), [(1, 1, 1, 0), (1, 1, 1, 3)], {}, "pv8ws", 4e-3),
+    # the per-frame regime at the non-square latents: >= 6144 keys and NO workspace (unsplit kernels)
+    ("frame_attn16_unsplit-6912x6912", 6912, 6912, (3, 1, 2), [(1, 1, 2, 0), (3, 1, 1, 1)], {}, "pre", 1e-3),
+    ("frame_attn16_unsplit-9216x9216", 9216, 9216, (3, 1, 2), [(1, 1, 2, 0), (3, 1, 1, 1)], {}, "pre", 1e-3),
+    ("pv8_unsplit_no_ws-6912x6912", 6912, 6912, (3, 1, 2), [(1, 1, 2, 0), (3, 1, 1, 1)], {}, "pv8", 4e-3),
+    ("pv8_unsplit_no_ws-9216x9216", 9216, 9216, (3, 1, 2), [(1, 1, 2, 0), (3, 1, 1, 1)], {}, "pv8", 4e-3),
 ]
 
 
@@ -262,6 +271,9 @@ ATTN_B = [
     ("joint_split_forced", (2, 1, 2), [(2049, 1313), (2303, 1343)], {"attn_split": 3}, "ws", 1e-3),
     ("pv8", (2, 1, 2), [(2303, 2111), (2049, 2081)], {}, "pv8", 4e-3),
     ("pv8_split", (2, 1, 2), [(2049, 6145), (2303, 6177)], {}, "pv8ws", 4e-3),
+    # >= 6144 keys and no workspace: the unsplit kernels over ragged key counts (what the per-frame regime launches)
+    ("frame_attn16_unsplit", (2, 1, 2), [(2303, 6913), (2049, 9215)], {}, "pre", 1e-3),
+    ("pv8_unsplit_no_ws", (2, 1, 2), [(2049, 6945), (2303, 9215)], {}, "pv8", 4e-3),
 ]
 
 
@@ -510,15 +522,16 @@ def test_groupnorm_sample_does_not_depend_on_the_batch(dev, cid, hw, c1, c2, n_l
 # ------------------------------------------------------------------------------------------------------------------------------
 # C. softmax_rows at the VAE mid block's size
 # ------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("cols,cols_pad", [(5184, 5184), (5183, 5248)], ids=["softmax_rows-5184", "softmax_rows-5183_pad5248"])
+@pytest.mark.parametrize("cols,cols_pad", [(5184, 5184), (5183, 5248), (6912, 6912), (6911, 6976)],
+                         ids=["softmax_rows-5184", "softmax_rows-5183_pad5248", "softmax_rows-6912", "softmax_rows-6911_pad6976"])
 @pytest.mark.parametrize("data", ["random", "dominant_column"])
 def test_softmax_rows_at_the_vae_size(dev, cols, cols_pad, data):
-    """rows = 5184, scale 512^-0.5, ldx / ldo larger than needed with NaN in the input gap and guards in the output gap and behind
-    the last row; pad columns exactly +0; against an fp64 softmax (max abs 1e-3); row 0 and row 5183 launched alone are bitwise the
-    rows of the full launch.  dominant_column: one column per row beats the rest by more than 200 after scaling, in the first, a
-    middle and the last 256-column stride of the kernel's loops."""
+    """rows = 5184 (72x72 latent; 6912 for the 72x96 / 96x72 latent's columns), scale 512^-0.5, ldx / ldo larger than needed with
+    NaN in the input gap and guards in the output gap and behind the last row; pad columns exactly +0; against an fp64 softmax
+    (max abs 1e-3); row 0 and the last row launched alone are bitwise the rows of the full launch.  dominant_column: one column per
+    row beats the rest by more than 200 after scaling, in the first, a middle and the last 256-column stride of the kernel's loops."""
     from seva import ops
-    rows, scale = 5184, 512 ** -0.5
+    rows, scale = (5184 if cols <= 5184 else 6912), 512 ** -0.5
     ldx, ldo = cols + 24, cols_pad + 40
     xbuf = torch.full((rows + 1, ldx), NAN, device=dev)
     x = _randn((rows, cols), dev, 11, 30.0)

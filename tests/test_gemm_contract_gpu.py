@@ -165,6 +165,11 @@ CONV_A = [  # id, n values, ih, iw, cin, cout, stride, up, stats, fp8, split-K w
     # e4m3 window conv (128-column family, FP8 instantiations), with and without statistics
     ("fp8_win_36x36", (1, 6), 36, 36, 640, 640, 1, False, False, True, False, False),
     ("fp8_win_stats_16x16", (1, 5), 16, 16, 256, 384, 1, False, True, True, False, False),
+    # the UNet's lower levels at the non-square latents 72x96 / 72x128: producer statistics at C = 640 (1728 pixels) and C = 1280
+    # (576 pixels); 9 x 16 at C = 1280 with the engine's workspace: hw = 144 > 128, so NOT split (window kernel) at every batch size
+    ("win160_stats_36x48_c640", (1, 3, 16), 36, 48, 640, 640, 1, False, True, False, False, False),
+    ("win160_stats_18x32_c1280", (1, 3, 42), 18, 32, 1280, 1280, 1, False, True, False, False, False),
+    ("win160_9x16_c1280_hw144_unsplit", (1, 3, 42), 9, 16, 1280, 1280, 1, False, False, False, True, False),
 ]
 
 

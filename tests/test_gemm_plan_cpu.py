@@ -106,6 +106,10 @@ CONV_A_PLANS = {  # case id of test_gemm_contract_gpu.CONV_A -> allowed rows per
     "splitk_9x9": [{"conv gather 128x160 split-K"}] * 2,
     "fp8_win_36x36": [{"win e4m3 4-wave 128x128 linear stats"}] * 2,
     "fp8_win_stats_16x16": [{"win e4m3 4-wave 128x128 linear stats"}] * 2,
+    # the UNet's /2, /4 and /8 levels at the non-square latents 72x96 and 72x128
+    "win160_stats_36x48_c640": [W160S] * 3,
+    "win160_stats_18x32_c1280": [W160S] * 3,
+    "win160_9x16_c1280_hw144_unsplit": [{"win 4-wave 160x160 linear", "win 8-wave 256x160 linear stats"}] * 3,
 }
 
 
@@ -202,6 +206,19 @@ def _sweep():
                 add(f"unet{side}_c{c}_head{cout}", side, side, c, cout, row_add=False, residual=False)
             if side <= 36:  # the three Upsample convs as phase convs
                 add(f"unet{side}_c{c}_phases", side, side, c, c, up=2)
+    # the UNet's levels at the non-square latents 72x96 (768x576 px), 96x72 and 72x128 (1024x576 px): widths 12 ... 128; 1728, 2304 and 576
+    # pixels take producer statistics at C = 640 / 1280, 108 pixels are split (hw <= 128), 144 are not
+    for top_h, top_w in ((72, 96), (96, 72), (72, 128)):
+        for lvl in range(4):
+            ih, iw = top_h >> lvl, top_w >> lvl
+            for c in (320, 640, 1280):
+                for stride, up in ((1, 0), (2, 0), (1, 1)):
+                    for stats in (False, True):
+                        for sk in (False, True):
+                            add(f"unet{ih}x{iw}_c{c}_s{stride}_u{up}_st{stats:d}_sk{sk:d}", ih, iw, c, c, stride=stride, up=up, stats=stats, sk=sk)
+                add(f"unet{ih}x{iw}_c{c}_head4", ih, iw, c, 4, row_add=False, residual=False)
+                if lvl:
+                    add(f"unet{ih}x{iw}_c{c}_phases", ih, iw, c, c, up=2)
     # the widths of ADVICE.md finding 1, with statistics
     for w in range(51, 78):
         add(f"advice{w}", w, w, 320, 320, stats=True)

@@ -379,6 +379,19 @@ def test_vae_decode_576_frame(dev):
     assert out.shape == (1, 3, 576, 576) and err < 2e-3
 
 
+def test_vae_decode_nonsquare_frame(dev):
+    """One 576x768 frame (portrait: latent 96x72, 6912 tokens in the mid-block attention) through the full-width decoder."""
+    from oracle import vae_ref as V
+    ae, sd = _vae(dev, (128, 256, 512, 512))
+    z = torch.randn(1, 4, 96, 72, generator=torch.Generator().manual_seed(12)) * 0.18215 * 4
+    out = ae.decode(z.to(dev), 1)
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    ref = V.vae_decode(sd, z)
+    err = rel_l2(out.cpu(), ref)
+    print(f"vae decode 576x768 frame (latent 96x72): rel-L2 {err:.3e}")
+    assert out.shape == (1, 3, 768, 576) and err < 2e-3
+
+
 def test_softmax_rows(dev):
     from seva import ops
     x = torch.randn(300, 200, device=dev) * 5
@@ -479,6 +492,23 @@ def test_vae_encode_576_frame_and_chunking(dev):
     assert torch.equal(z[:1], z0)
     img = ae.decode(z, 1)
     assert img.shape == (2, 3, 576, 576) and torch.isfinite(img).all()
+
+
+def test_vae_encode_nonsquare_frame_and_chunking(dev):
+    """576x768 pixel frames (portrait) through the full-width encoder: the first frame against oracle/vae_ref.py (the bound of
+    test_vae_encode_vs_restatement); chunked encode == per-frame encode (bitwise)."""
+    from oracle import vae_ref as V
+    ae, sd = _vae(dev, (128, 256, 512, 512))
+    xc = torch.rand(2, 3, 768, 576, generator=torch.Generator().manual_seed(16)) * 2 - 1
+    x = xc.to(dev)
+    z = ae.encode(x, 1)
+    assert z.shape == (2, 4, 96, 72) and torch.isfinite(z).all()
+    assert torch.equal(z[:1], ae.encode(x[:1], 1)) and torch.equal(z[1:], ae.encode(x[1:], 1))
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    ref = V.vae_encode(sd, xc[:1])
+    err = rel_l2(z[:1].cpu(), ref)
+    print(f"vae encode 576x768 frame (latent 96x72): rel-L2 {err:.3e}")
+    assert err < 2e-3
 
 
 # ------------------------------------------------------------------ whole-step hipGraph (seva/_stepgraph.py)

@@ -365,6 +365,60 @@ def test_conv3x3(dev, n, ih, iw, cin, cout, stride, up):
     assert torch.equal(got, ref), f"max diff {(got - ref).abs().max()}"
 
 
+NONSQUARE_CONV_CASES = [  # n, ih, iw, cin, cout, stride, upsample, split-K workspace: the UNet's levels at 768x576 / 1024x576 / 576x768
+    (2, 36, 48, 640, 640, 1, False, False), (2, 36, 64, 640, 640, 1, False, False), (2, 18, 32, 1280, 1280, 1, False, False),
+    (3, 9, 12, 1280, 1280, 1, False, True), (3, 9, 16, 1280, 1280, 1, False, False), (2, 72, 96, 320, 320, 1, False, False),
+    (1, 72, 128, 320, 320, 1, False, False), (2, 96, 72, 320, 320, 1, False, False), (2, 72, 96, 320, 320, 2, False, False),
+    (3, 9, 12, 1280, 1280, 1, True, False),
+]
+
+
+@pytest.mark.parametrize("n,ih,iw,cin,cout,stride,up,splitk", NONSQUARE_CONV_CASES)
+def test_conv3x3_at_the_nonsquare_network_shapes(dev, n, ih, iw, cin, cout, stride, up, splitk, knobs):
+    """The 3x3 convs of the 1.3B UNet at the per-level image sizes of non-square latents (72x96, 96x72, 72x128: widths 12 / 16 /
+    32 / 48 / 64 / 72 / 96 / 128 at C = 320 / 640 / 1280), two or three images so that a tile straddles an image boundary.  Integer
+    data (x in [-2, 2], w in [-1, 1]: every partial sum of the 9 * 1280 products and of the 64-row sums of squares is an integer
+    below 2^24): bit-exact against torch with bias + row_add + residual under the default dispatch and, at stride 1 without
+    a split-K workspace, under both forced window families; the epilogue statistics wherever hw % 64 == 0 (where the engine asks for them); 9x12 with the
+    split-K workspace (hw = 108 <= 128) and 9x16 without (hw = 144).  Random data: the last image alone is bitwise its rows
+    in the batch (same workspace)."""
+    from seva import ops
+    from seva._engine import pack_conv3x3
+    eh, ew = (2 * ih, 2 * iw) if up else (ih, iw)
+    oh, ow = (eh - 1) // stride + 1, (ew - 1) // stride + 1
+    hw = oh * ow
+    M = n * hw
+    stats = hw % 64 == 0
+    x = _ints((n, ih, iw, cin), -2, 2, dev, 1).half()
+    wc = _ints((cout, cin, 3, 3), -1, 1, dev, 2)
+    bias, emb, res = _ints((cout,), -4, 4, dev, 3), _ints((n, cout), -2, 2, dev, 4), _ints((M, cout), -5, 5, dev, 5)
+    xi = x.float().permute(0, 3, 1, 2)
+    xi = F.interpolate(xi, scale_factor=2, mode="nearest") if up else xi
+    ref = F.conv2d(xi, wc, bias, stride=stride, padding=1).permute(0, 2, 3, 1).reshape(M, cout) + emb.repeat_interleave(hw, 0) + res
+    wp = pack_conv3x3(wc).half().to(dev)
+    ws = ops.splitk_workspace(M, cout, dev) if splitk else None
+    for fam in (-1, 1, 2) if stride == 1 and not splitk else (-1,):
+        knobs(conv_win=fam)
+        out = torch.full((M, cout), float("nan"), device=dev)
+        st = torch.full(ops.channel_stats_shape(M, cout), float("nan"), device=dev) if stats else None
+        ops.conv3x3(x, wp, stride=stride, upsample=up, bias=bias, row_add=emb, rows_per_group=hw, residual=res, out_f32=out,
+                    ch_stats=st, splitk_ws=ws)
+        assert torch.equal(out, ref), f"conv_win {fam}: max diff {(out - ref).abs().max()}"
+        if stats:
+            assert torch.equal(st.double(), _block_stats(out, M, cout)), f"conv_win {fam}: statistics"
+        if splitk:
+            assert int(ws[:16384].view(torch.int32).abs().sum()) == 0
+    knobs(conv_win=-1)
+    if splitk:
+        ops.check_handoffs()
+    xr, wr = _rand((n, ih, iw, cin), dev, 6).half(), pack_conv3x3(_rand((cout, cin, 3, 3), dev, 7, 0.05).cpu()).half().to(dev)
+    rr = _rand((M, cout), dev, 8)
+    o_all, o_one = torch.full((M, cout), float("nan"), device=dev), torch.full((hw, cout), float("nan"), device=dev)
+    ops.conv3x3(xr, wr, stride=stride, upsample=up, bias=bias, residual=rr, out_f32=o_all, splitk_ws=ws)
+    ops.conv3x3(xr[n - 1:], wr, stride=stride, upsample=up, bias=bias, residual=rr[(n - 1) * hw:], out_f32=o_one, splitk_ws=ws)
+    assert torch.isfinite(o_all).all() and torch.equal(o_one, o_all[(n - 1) * hw:])
+
+
 def _attn_ref(q, k, v, scale):
     att = torch.softmax((q.float() @ k.float().transpose(-1, -2)) * scale, -1)
     return att @ v.float()
@@ -621,7 +675,7 @@ def test_attention_one_hot_keys(dev):
     assert torch.equal(out[0].float().cpu().round(), v[perm])
 
 
-@pytest.mark.parametrize("T,S,H", [(21, 50, 2), (4, 36, 1), (24, 9, 5)])
+@pytest.mark.parametrize("T,S,H", [(21, 50, 2), (4, 36, 1), (24, 9, 5), (25, 36, 5)])
 def test_attention_temporal_strided(dev, T, S, H):
     """Temporal regime: tokens = frames, batch = (b, pixel); read in place from [(b t), s, 3C]."""
     from seva import ops
@@ -883,7 +937,11 @@ def test_conv_splitk_small_images(dev, n, ih, iw, cin, cout, stride):
 
 
 @pytest.mark.parametrize("n,hw,c1,c2,dense", [(3, 256, 320, 0, True), (2, 1024, 128, 0, False), (2, 64, 640, 320, True),
-                                              (5, 5184, 320, 320, False)])
+                                              (5, 5184, 320, 320, False),
+                                              # the levels that first qualify at non-square latents (72x96 /2, 72x128 /2 and /4), with skip inputs
+                                              (2, 1728, 640, 0, True), (2, 1728, 640, 0, False), (2, 576, 1280, 0, True), (2, 576, 1280, 0, False),
+                                              (2, 576, 1280, 640, True), (2, 576, 1280, 640, False), (2, 2304, 640, 320, True),
+                                              (2, 2304, 640, 320, False)])
 def test_groupnorm_with_producer_statistics(dev, n, hw, c1, c2, dense):
     """GroupNorm fed with the statistics its producers emitted (stats1 / stats2) against the separate statistics pass and
     against torch; batch composition does not change a sample's result (bitwise)."""
