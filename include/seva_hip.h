@@ -35,7 +35,14 @@ const char* seva_last_error(void);
  * seva_gemm_f16_split_out / seva_gemm_fp8 launch the calling thread planned; "" before any.  Thread-local, host only, a static
  * string (never freed).  A call that failed before a row was chosen leaves the previous name.  (No ABI change: a new symbol only.) */
 const char* seva_last_plan(void);
-/* ABI version of this header; bumped on any signature change. */
+/* ABI version of this header; bumped on any signature or struct change, and on a changed VALUE of a contract constant below.
+ * A new macro that names a number the contract already had is not an ABI change (nor is a new symbol).
+ *
+ * Contract constants: every number that both sides of this ABI must agree on -- a caller needs it to size a buffer or to predict
+ * which path a launch takes -- is a SEVA_* macro of this header, used under that name by the kernels' host code and restated once on
+ * the Python side (seva/ops.py, seva/_native.py); tests/test_abi_cpu.py compares the two.  Tuning numbers that only the kernels know
+ * are not here. */
+#define SEVA_ABI_VERSION 12
 int seva_abi_version(void);
 /* Name of the code object's target, e.g. "gfx950". */
 const char* seva_target_arch(void);
@@ -69,7 +76,7 @@ const char* seva_target_arch(void);
  *   channels, source rows up to 288 pixels): the same `w` [4][N][4*cin], K = 4*cin, oh = 2*ih, ow = 2*iw and output rows, with
  *   N % 128 == 0 and cin % 64 == 0, and bias + out_f32 + optional ch_stats.  Tiles are consecutive source pixels where one
  *   image's window fits, else 16 source columns x 8 source rows (iw % 16 == 0 and ih % 8 == 0); which is decided from one
- *   image's dimensions.  ch_stats needs ih*iw % 64 == 0 (else an ERROR): a block is then 64 source pixels of ONE phase, i.e.
+ *   image's dimensions.  ch_stats needs ih*iw % 64 == 0 (else an ERROR; 64 = SEVA_CH_STATS_ROWS): a block is then 64 source pixels of ONE phase, i.e.
  *   64 output pixels of one image, stored as block 4*(source block) + 2*py + px, so that the oh*ow/64 blocks of image i are
  *   exactly [i*oh*ow/64, (i+1)*oh*ow/64), each written once; consumers rely only on the blocks of an image adding up to that
  *   image.  residual, row_add, out_f16, out_f8, a2, splitk_ws, col_scale, GEGLU, seva_gemm_fp8, a shape neither tiling
@@ -81,6 +88,12 @@ const char* seva_target_arch(void);
  * Requirements: K % 64 == 0, cin % 64 == 0 (mode 1), N % 4 == 0, all row pitches % 4 == 0,
  * pointers 16-byte aligned.
  */
+#define SEVA_CH_STATS_ROWS 64        /* output rows per block of seva_gemm_desc.ch_stats */
+#define SEVA_SPLITK_FLAGS 16384      /* int flags at the head of seva_gemm_desc.splitk_ws */
+#define SEVA_SPLITK_ERROR_SLOT 16383 /* the last of them counts consumers that gave up waiting: a launch has fewer tiles than this */
+#define SEVA_SPLITK_TILE_M 128       /* rows and */
+#define SEVA_SPLITK_TILE_N 160       /*   largest column count of one split-K tile's fp32 slot in the workspace */
+#define SEVA_SPLITK_MAX_PIXELS 128   /* output pixels per sample up to which a convolution qualifies for the split */
 typedef struct seva_gemm_desc {
   const void* a;
   const void* w;         /* f16 [N][K] */
@@ -116,20 +129,21 @@ typedef struct seva_gemm_desc {
   int64_t ldo8;
   /* optional (NULL = off): GroupNorm statistics of out_f32, emitted by the epilogue while the values are in registers,
    * so that the GroupNorm consuming this tensor (seva_groupnorm_desc.stats1 / stats2) needs no statistics pass over it.
-   * float [ceil(M / 64)][2][N]: for every block of 64 output rows and every output channel, the sum ([..][0][n]) and the
-   * sum of squares ([..][1][n]) of the fp32 values stored (after bias / row_add / residual); rows >= M contribute
-   * nothing.  A block is 64 consecutive rows aligned to multiples of 64 rows of the whole tensor, EXCEPT for 3x3
+   * With R = SEVA_CH_STATS_ROWS, float [ceil(M / R)][2][N]: for every block of R output rows and every output channel, the sum
+   * ([..][0][n]) and the sum of squares ([..][1][n]) of the fp32 values stored (after bias / row_add / residual); rows >= M contribute
+   * nothing.  A block is R consecutive rows aligned to multiples of R rows of the whole tensor, EXCEPT for 3x3
    * convolutions over images at least 144 pixels wide with N % 160 != 0, or any such e4m3 convolution (ABI 10), or an e4m3 stride-2
-   * pad_br_only convolution whose image is too wide for its linear tiles (ABI 11) (the 2-D tiles of the window-staged kernel), or a phase-decomposed upsample conv (`upsample` = 4: blocks of one output phase), where the blocks [i * hw / 64, (i + 1) * hw / 64) partition the pixels of image i in tile order: consumers must
+   * pad_br_only convolution whose image is too wide for its linear tiles (ABI 11) (the 2-D tiles of the window-staged kernel), or a phase-decomposed upsample conv (`upsample` = 4: blocks of one output phase), where the blocks [i * hw / R, (i + 1) * hw / R) partition the pixels of image i in tile order: consumers must
    * only rely on the blocks of an image adding up to that image (seva_groupnorm does).  Per channel, so any grouping or
    * channel concatenation can be formed by the consumer.  Plain epilogue with out_f32 and N >= 128 only; forces 128-row tiles. */
   float* ch_stats;
-  /* optional (NULL = off) workspace that lets seva_gemm_f16 run a convolution over small images (<= 128 output pixels per
-   * sample, K >= 1024: the 9x9 level of a 576x576 step) as split-K = 2 on 128-row tiles: two workgroups per tile, the
+  /* optional (NULL = off) workspace that lets seva_gemm_f16 run a convolution over small images (<= SEVA_SPLITK_MAX_PIXELS output
+   * pixels per sample, K >= 1024: the 9x9 level of a 576x576 step) as split-K = 2 on 128-row tiles: two workgroups per tile, the
    * upper half of K exported raw, added by the partner before the epilogue (fixed association: deterministic, and chosen
-   * from per-sample dimensions only).  Layout: 16384 int flags (zero before first use; every launch leaves them zero), then
-   * one 128 x BN fp32 tile per output tile: splitk_ws_bytes >= 4 * (16384 + tiles * 128 * 160), tiles = ceil(M / 128) *
-   * ceil(N / 160).  The hand-off
+   * from per-sample dimensions only).  Layout: SEVA_SPLITK_FLAGS int flags (zero before first use; every launch leaves them zero;
+   * flag SEVA_SPLITK_ERROR_SLOT counts hand-offs that were given up, so a launch has fewer tiles than that), then one
+   * SEVA_SPLITK_TILE_M x BN fp32 tile per output tile, BN <= SEVA_SPLITK_TILE_N: splitk_ws_bytes >= 4 * (SEVA_SPLITK_FLAGS +
+   * tiles * SEVA_SPLITK_TILE_M * SEVA_SPLITK_TILE_N), tiles = ceil(M / SEVA_SPLITK_TILE_M) * ceil(N / BN) with BN >= 128.  The hand-off
    * uses agent-scope (sc1) stores / loads, no cache-wide fence.  One launch at a time may
    * use a given workspace (launches on ONE stream are fine).  A workspace too small for a launch that qualifies for the split is
    * an ERROR (ABI 8; it was a silent fall-back to the unsplit kernel): whether a sample is split never depends on the batch. */
@@ -219,6 +233,9 @@ int seva_ff_fused_fp8(const seva_ff_desc* d, seva_stream_t stream);
  * Element (b0, b1, token l, head h, d) of q lives at q + b0*q_sb0 + b1*q_sb1 + l*q_sl + h*64 + d
  * (strides in elements); k and v share strides; out likewise.
  */
+#define SEVA_ATTN_LONG_MIN_LQ 2048     /* query length from which the long-sequence kernels (attn16, seva_attention_pv8's) take over */
+#define SEVA_ATTN_SPLIT_MIN_LK 6144    /* key length from which those kernels split the K/V range in two, given split_ws */
+#define SEVA_ATTN_SPLIT_ROW_FLOATS 66  /* floats of split_ws per half and query row */
 typedef struct seva_attn_desc {
   const void* q;
   const void* k;
@@ -234,18 +251,20 @@ typedef struct seva_attn_desc {
   /* non-zero: q already holds q * scale * log2(e) (see seva_gemm_desc.col_scale); `scale` is ignored
    * and the kernel evaluates softmax as exp2(q' . k - max) */
   int32_t q_prescaled;
-  /* optional workspace (ABI 7) for the K/V split of LONG sequences: with it, launches whose key length is >= 6144 (the joint
+  /* optional workspace (ABI 7) for the K/V split of LONG sequences: with it, launches of the long-sequence kernels (lq >=
+   * SEVA_ATTN_LONG_MIN_LQ, q_prescaled) whose key length is >= SEVA_ATTN_SPLIT_MIN_LK (the joint
    * view x space attention at 36x36 / 18x18: L = 27216 / 6804) run every query block as TWO workgroups over the two halves of
    * the K/V tiles plus a small fp32 combine -- the split is a function of lk only, so a sample's result does not depend on
    * the batch.  It fills the last, partly empty round of workgroup slots (2140 workgroups = 4.18 rounds of the 512 slots ->
-   * 8.36 half-length rounds).  Needs 2 * nb0 * nb1 * heads * lq * 66 floats; NULL = never split. */
+   * 8.36 half-length rounds).  Needs 2 * nb0 * nb1 * heads * lq * SEVA_ATTN_SPLIT_ROW_FLOATS floats (per half and query row: 64 of
+   * the un-normalised output, the running maximum and the row sum); NULL = never split. */
   float* split_ws;
   int64_t split_ws_bytes;
 } seva_attn_desc;
 int seva_attention_f16(const seva_attn_desc* d, seva_stream_t stream);
 
 /* fp8 P.V attention (ABI 9; the opt-in `attention="fp8"` sub-option of the fp8 precision mode): the same operator for the long
- * sequences (lq >= 2048) with P and V in OCP e4m3 on the block-scaled MFMA; Q K^T stays f16.  V is first quantised into a private
+ * sequences (lq >= SEVA_ATTN_LONG_MIN_LQ) with P and V in OCP e4m3 on the block-scaled MFMA; Q K^T stays f16.  V is first quantised into a private
  * workspace -- e4m3 values in the kernel's key order plus one E8M0 (power-of-two) scale byte per 32 keys and channel, per sample,
  * keys >= lk zero-padded -- by seva_attn_quant_v_fp8, which reads d->v through the k strides (nb0 / nb1 / token); then
  * seva_attention_pv8 reads q, k (f16, the desc's strides), the quantised V and writes out.  q must be pre-scaled (q_prescaled);
@@ -264,7 +283,7 @@ int seva_attention_pv8(const seva_attn_desc* d, const void* v8, const uint8_t* v
  * Replaces GroupNorm32 + SiLU + dense_emb_layers of seva/modules/layers.py:61-63,98-100,
  * 106-111,122-131, the output head norm (seva/model.py:171) and the transformer input norm
  * (seva/modules/transformer.py:186,231).
- * workspace: at least n * 1024 * groups * 2 floats (SEVA_GN_WORKSPACE_SLABS slab slots per sample).
+ * workspace: at least n * SEVA_GN_WORKSPACE_SLABS * groups * 2 floats (that many slab slots per sample).
  */
 #define SEVA_GN_WORKSPACE_SLABS 1024
 typedef struct seva_groupnorm_desc {
@@ -289,8 +308,8 @@ typedef struct seva_groupnorm_desc {
   int64_t ld_out_f8; /* pixel pitch of out_f8 in bytes (>= c1 + c2; 0 = c1 + c2): lets a 320-channel tensor feed an fp8 conv whose
                       * channel count is padded to a multiple of 128 (pad bytes are never written: keep them zero) */
   /* optional: per-channel partial statistics of x1 / x2 as written by the kernel that produced them
-   * (seva_gemm_desc.ch_stats: [n * hw / 64][2][c]).  When given for every source, the statistics pass over the fp32
-   * tensors is skipped (x1 / x2 are then read once, by the apply pass).  Requires hw % 64 == 0 (a 64-row block then
+   * (seva_gemm_desc.ch_stats: [n * hw / SEVA_CH_STATS_ROWS][2][c]).  When given for every source, the statistics pass over the fp32
+   * tensors is skipped (x1 / x2 are then read once, by the apply pass).  Requires hw % SEVA_CH_STATS_ROWS == 0 (a block then
    * belongs to one sample and a sample's statistics stay bitwise independent of the batch). */
   const float* stats1;
   const float* stats2;
@@ -609,12 +628,13 @@ int seva_lpips_layer(const seva_lpips_layer_desc* d, seva_stream_t stream);
  *                [71]           0
  *   workspace  seva_tensor_range_size(rows, cols) bytes, 8-byte aligned; contents need not be kept between calls.  It holds one
  *              partial table per workgroup of the counting kernel; workgroup w counts elements [w * S, (w + 1) * S) of the
- *              row-major rows x cols index space, S = SEVA_RANGE_WG_ELEMS (a larger multiple of it above 2048 * S elements), and
+ *              row-major rows x cols index space, S = SEVA_RANGE_WG_ELEMS (a larger multiple of it above SEVA_RANGE_MAX_WGS * S elements), and
  *              a second kernel adds the tables.  No atomics in global memory; the result is independent of the split.
- * Nothing but the 72 words and the workspace is written.  rows * cols <= 2^46. */
+ * Nothing but the SEVA_RANGE_WORDS words and the workspace is written.  rows * cols <= 2^46. */
 enum { SEVA_RANGE_F32 = 0, SEVA_RANGE_F16 = 1, SEVA_RANGE_E4M3 = 2 };
 #define SEVA_RANGE_WORDS 72
 #define SEVA_RANGE_WG_ELEMS 32768
+#define SEVA_RANGE_MAX_WGS 2048 /* most workgroups (partial tables of the workspace) of the counting kernel */
 typedef struct seva_range_desc {
   const void* x;
   int32_t dtype;

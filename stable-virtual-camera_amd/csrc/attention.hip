@@ -824,12 +824,12 @@ extern "C" int seva_attention_f16(const seva_attn_desc* d, seva_stream_t stream)
   const bool pre = d->q_prescaled != 0;
   SEVA_REQUIRE(!pre || use_tr, "attention: q_prescaled is not available on the SEVA_ATTN_NO_TR debug path");
   if (d->lq <= 32) return launch<1, 32>(a, batch, s, use_tr, pre);
-  // Long sequences (lq >= 2048): 64 queries per wave, K / V fragments shared by all its query blocks.  Default: attn16_kernel
+  // Long sequences (lq >= SEVA_ATTN_LONG_MIN_LQ): 64 queries per wave, K / V fragments shared by all its query blocks.  Default: attn16_kernel
   // (v_mfma_f32_16x16x32; -3 ... -7 % against attn2_kernel on the long shapes of a step, same-box, profiles/r04_kattn16.log).
   // Knob attn_two: 0 forces attn_kernel, 1 / 2 select attn2_kernel (v_mfma_f32_32x32x16, bitwise equal to attn_kernel) from
   // lq >= 512, 4 selects attn16_kernel from lq >= 512.
   const int two = g_seva_knobs.attn_two;
-  if (pre && use_tr && !a.dbg && ((two < 0 && d->lq >= 2048) || ((two == 1 || two == 2 || two == 4) && d->lq >= 512))) {
+  if (pre && use_tr && !a.dbg && ((two < 0 && d->lq >= SEVA_ATTN_LONG_MIN_LQ) || ((two == 1 || two == 2 || two == 4) && d->lq >= 512))) {
     const bool k16 = two == 4 || two < 0;
     const int qrows = 256;
     AttnArgs args = a;
@@ -838,7 +838,7 @@ extern "C" int seva_attention_f16(const seva_attn_desc* d, seva_stream_t stream)
     if (int rc = attn_check_grid("attention", nb)) return rc;
     // K/V split (seva_attn_desc.split_ws): two workgroups per query block for long key sequences.  The factor is a function of
     // lk alone (never of the batch); knob attn_split: 0 = never, 2..4 = that factor wherever a workspace is given.
-    int nsplit = d->lk >= 6144 ? 2 : 1;
+    int nsplit = d->lk >= SEVA_ATTN_SPLIT_MIN_LK ? 2 : 1;
     if (g_seva_knobs.attn_split >= 0) nsplit = g_seva_knobs.attn_split > 4 ? 4 : g_seva_knobs.attn_split;
     const int nt_all = (d->lk + 63) / 64;
     while (nsplit >= 2 && (nt_all + nsplit - 1) / nsplit * (nsplit - 1) >= nt_all) --nsplit;  // every split gets >= 1 tile

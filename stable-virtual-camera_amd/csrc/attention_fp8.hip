@@ -1,5 +1,5 @@
 // Opt-in fp8 P.V attention of the fp8 precision mode (Seva.set_precision("fp8", attention="fp8")): the long-sequence launches that
-// seva_attention_f16 sends to attn16_kernel (lq >= 2048), with the P.V half of the MFMA work on v_mfma_scale_f32_16x16x128_f8f6f4.
+// seva_attention_f16 sends to attn16_kernel (lq >= SEVA_ATTN_LONG_MIN_LQ), with the P.V half of the MFMA work on v_mfma_scale_f32_16x16x128_f8f6f4.
 //
 //   quant_v_fp8_kernel  V (f16, the attention descriptor's strides) -> e4m3 V^T in the kernel's key order + E8M0 scale per 32 keys and
 //                       channel (layout: attn_pv8.h)
@@ -17,7 +17,7 @@
 // ceil(running maximum) - 8, so the e4m3 rounding of P is a function of the scores alone (e4m3(x 2^k) = e4m3(x) 2^k for integer k in
 // the normal range; tests/test_attention_fp8_cpu.py: pv8_reference).  A rescale in a later part of a tile first accumulates the
 // earlier parts' packed P (a second, rare, set of MFMAs) -- they were packed against the old reference.
-// Every tiling decision is a function of lk and per-sample sizes only (K/V split from lk >= 6144, as seva_attention_f16).
+// Every tiling decision is a function of lk and per-sample sizes only (K/V split from lk >= SEVA_ATTN_SPLIT_MIN_LK, as seva_attention_f16).
 #include "attn_common.h"
 #include "attn_pv8.h"
 
@@ -322,7 +322,7 @@ extern "C" int seva_attention_pv8(const seva_attn_desc* d, const void* v8, const
   const double alg_bytes = (double)batch * d->heads * 64.0 * (2.0 * 2.0 * (double)d->lq + 3.0 * (double)d->lk);  // q, out f16; k f16, v e4m3
   SevaProfScope prof(2, flops, s, alg_bytes);
   // K/V split as seva_attention_f16 (split_ws; a function of lk alone), counted in 128-key tiles
-  int nsplit = d->lk >= 6144 ? 2 : 1;
+  int nsplit = d->lk >= SEVA_ATTN_SPLIT_MIN_LK ? 2 : 1;
   const int nt_all = pv8_steps(d->lk);
   while (nsplit >= 2 && (nt_all + nsplit - 1) / nsplit * (nsplit - 1) >= nt_all) --nsplit;  // every split gets >= 1 tile
   if (nsplit >= 2 && d->split_ws != nullptr) {

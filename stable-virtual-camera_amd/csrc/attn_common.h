@@ -334,9 +334,10 @@ inline void attn_fill_base(AttnBase& a, const seva_attn_desc* d) {
 // K/V split into nsplit ranges of whole tiles: checks the workspace (seva_attn_desc.split_ws) and the grid of nb * nsplit workgroups
 // and points the arguments at the partials; rows_all = batch * heads * lq
 inline int attn_split_setup(AttnBase& a, const seva_attn_desc* d, const char* what, int nsplit, int64_t rows_all, int64_t nb) {
-  SEVA_REQUIRE(d->split_ws_bytes >= nsplit * rows_all * 66 * 4 && (uintptr_t)d->split_ws % 16 == 0,
-               "%s: split_ws too small (%lld bytes, need %lld) or misaligned", what, (long long)d->split_ws_bytes,
-               (long long)(nsplit * rows_all * 66 * 4));
+  static_assert(SEVA_ATTN_SPLIT_ROW_FLOATS == 64 + 2, "per split and query row: 64 floats of O in part_o, (m, l) in part_ml");
+  const int64_t need = nsplit * rows_all * SEVA_ATTN_SPLIT_ROW_FLOATS * 4;
+  SEVA_REQUIRE(d->split_ws_bytes >= need && (uintptr_t)d->split_ws % 16 == 0,
+               "%s: split_ws too small (%lld bytes, need %lld) or misaligned", what, (long long)d->split_ws_bytes, (long long)need);
   SEVA_REQUIRE(nb * nsplit <= 0x7fffffff && rows_all * 8 / 256 + 1 <= 0x7fffffff, "%s: split grid too large", what);
   a.nsplit = nsplit;
   a.part_o = d->split_ws;

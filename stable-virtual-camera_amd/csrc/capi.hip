@@ -91,7 +91,7 @@ extern "C" {
 
 const char* seva_last_error(void) { return g_err; }
 const char* seva_last_plan(void) { return g_seva_last_plan; }
-int seva_abi_version(void) { return 12; }
+int seva_abi_version(void) { return SEVA_ABI_VERSION; }
 const char* seva_target_arch(void) { return "gfx950"; }
 
 int seva_set_knob(const char* name, int value) {

@@ -488,6 +488,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_win_kernel(GemmArgs p, ConvWi
       const int64_t mw = (int64_t)m0 + wm * WM;
       // PH: the wave's 64 source pixels are 64 OUTPUT pixels of one phase and one image (hw % 64 == 0): block 4 * (source block) + phase,
       // so the hw_out / 64 blocks of image i fill [i hw_out / 64, (i + 1) hw_out / 64), each written once
+      static_assert(SEVA_CH_STATS_ROWS == 64, "a block of ch_stats is the wave's 64 rows");
       const int64_t sblk = T2D ? (int64_t)t_img * (g.hw >> 6) + (int64_t)t_k * (BM / 64) + wm : mw >> 6;
       const int64_t blk = PH ? 4 * sblk + ph : sblk;
       float* const sp_ = p.ch_stats + blk * 2 * p.N;

@@ -534,9 +534,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
     }
     if constexpr (SPLIT_OK) {
       if (sk_half >= 0) {
-        // workspace: [16384 flags (int)] [per tile: MI x NJ x 256 lanes x f32x4, lane-linear]
+        // workspace: [SEVA_SPLITK_FLAGS flags (int)] [per tile: MI x NJ x 256 lanes x f32x4, lane-linear]
         int* const flag = (int*)p.sk_ws + ((int64_t)tm * p.tiles_n + tn);
-        float* const part = p.sk_ws + 16384 + ((int64_t)tm * p.tiles_n + tn) * (BM * BN) + threadIdx.x * 4;
+        float* const part = p.sk_ws + SEVA_SPLITK_FLAGS + ((int64_t)tm * p.tiles_n + tn) * (BM * BN) + threadIdx.x * 4;
         if (sk_half == 1) {
 #pragma unroll
           for (int i = 0; i < MI; ++i)
@@ -549,13 +549,13 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
         }
         if (threadIdx.x == 0) {
           // bounded wait (a producer is always dispatched before its consumer; the bound only guards against a hang if that
-          // assumption were ever violated: the tile is then wrong and error slot 16383 counts it)
+          // assumption were ever violated: the tile is then wrong and flag SEVA_SPLITK_ERROR_SLOT counts it)
           int spins = 0;
           while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 && spins < (1 << 21)) {
             __builtin_amdgcn_s_sleep(32);
             ++spins;
           }
-          if (spins == (1 << 21)) atomicAdd((int*)p.sk_ws + 16383, 1);
+          if (spins == (1 << 21)) atomicAdd((int*)p.sk_ws + SEVA_SPLITK_ERROR_SLOT, 1);
           __hip_atomic_store(flag, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch / graph replay
         }
         __syncthreads();
@@ -687,6 +687,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void gemm_kernel(GemmArgs p) {
       if constexpr (STATS_OK) {
         if (p.ch_stats != nullptr) {  // (written out: as a shared helper the 128 x 128 fp32 kernels change registers, 194 -> 202 VGPRs)
           const int64_t mw = m0 + wm * WM;  // first row of the wave's 64-row block
+          static_assert(SEVA_CH_STATS_ROWS == 64, "a block of ch_stats is the wave's 64 rows");
           float* const sp = p.ch_stats + (mw >> 6) * 2 * p.N;
 #pragma unroll
           for (int j = 0; j < NJ; ++j) {
@@ -865,8 +866,9 @@ int validate(const seva_gemm_desc* d) {
                  "out_f16, a2, splitk_ws, col_scale)");
     SEVA_REQUIRE(d->N % 128 == 0 && d->K == 4LL * d->cin, "conv: the phase-decomposed upsample (upsample = 4) needs N %% 128 == 0 and "
                  "K = 4 * cin per phase (N=%lld K=%lld cin=%d)", (long long)d->N, (long long)d->K, d->cin);
-    SEVA_REQUIRE(!d->ch_stats || ((int64_t)d->ih * d->iw) % 64 == 0, "conv: the phase-decomposed upsample (upsample = 4) emits ch_stats only "
-                 "where a 64-pixel block of one phase stays inside one image: ih * iw %% 64 == 0 (source %dx%d)", d->ih, d->iw);
+    SEVA_REQUIRE(!d->ch_stats || ((int64_t)d->ih * d->iw) % SEVA_CH_STATS_ROWS == 0,
+                 "conv: the phase-decomposed upsample (upsample = 4) emits ch_stats only where a 64-pixel block "
+                 "of one phase stays inside one image: ih * iw %% 64 == 0 (source %dx%d)", d->ih, d->iw);
   } else if (phases) {
     // no other kernel reads this weight layout, so everything the phase family does not do is an error, never a fall-back
     SEVA_REQUIRE(!FP8, "conv: the phase-decomposed upsample (upsample = 2) is an f16 operator");
@@ -985,9 +987,10 @@ int gemm_entry(const seva_gemm_desc* d, seva_stream_t stream) {
     // A workspace that cannot hold this launch's tiles is an ERROR (it was a silent fall-back to the unsplit 64-row kernel in
     // round 3: the reduction order of a sample would then have depended on the batch it was launched in and on the size of the
     // caller's workspace -- the opposite of what the per-sample split rule promises).  Size it with the formula of seva_hip.h.
-    SEVA_REQUIRE(p.sk_tiles < 16383 && d->splitk_ws_bytes >= (int64_t)(16384 + p.sk_tiles * 128 * p.sk_bn) * 4,
-                 "gemm: splitk_ws too small for this launch: %lld tiles of 128 x %d need %lld bytes (and fewer than 16383 tiles), got %lld",
-                 (long long)p.sk_tiles, p.sk_bn, (long long)((16384 + p.sk_tiles * 128 * p.sk_bn) * 4), (long long)d->splitk_ws_bytes);
+    const int64_t need = (int64_t)(SEVA_SPLITK_FLAGS + p.sk_tiles * SEVA_SPLITK_TILE_M * p.sk_bn) * 4;
+    SEVA_REQUIRE(p.sk_tiles < SEVA_SPLITK_ERROR_SLOT && d->splitk_ws_bytes >= need,
+                 "gemm: splitk_ws too small for this launch: %lld tiles of %d x %d need %lld bytes (and fewer than %d tiles), got %lld",
+                 (long long)p.sk_tiles, SEVA_SPLITK_TILE_M, p.sk_bn, (long long)need, SEVA_SPLITK_ERROR_SLOT, (long long)d->splitk_ws_bytes);
     a.sk_ws = d->splitk_ws;
   }
   return launch_gemm(a, p, s);

@@ -238,7 +238,7 @@ inline bool win_geometry(const WinProblem& a, bool s2, WinGeom& g) {
   g.ow = a.ow;
   // GroupNorm statistics are 64-row blocks of the whole tensor: only where a block cannot straddle two images (the consumer refuses other
   // statistics anyway), for every batch size
-  if (a.ch_stats && g.hw % 64 != 0) return false;
+  if (a.ch_stats && g.hw % SEVA_CH_STATS_ROWS != 0) return false;
   // exactness of the multiply-high divisions of the LINEAR tiles (2-D tiles divide by constants
   // only): mulhi(x, floor(2^32 / d) + 1) == x / d for every x with x * e < 2^32, e = (floor(2^32 / d) + 1) * d - 2^32 in (0, d]
   const auto div_exact = [](uint64_t x_max, uint32_t d) {
@@ -680,15 +680,15 @@ inline Plan plan(const seva_gemm_desc& d, const SevaKnobs& k, Variant v) {
   }
   const bool two_src = d.mode == 1 && d.a2 != nullptr;  // MODE 3: instantiated for 128- and 160-row tiles, never split-K
   if (two_src) half_m = false;
-  // Split-K = 2 for convolutions over SMALL IMAGES (<= 128 output pixels per sample: the ds8 level, 9 x 9) with a long
+  // Split-K = 2 for convolutions over SMALL IMAGES (<= SEVA_SPLITK_MAX_PIXELS output pixels per sample: the ds8 level, 9 x 9) with a long
   // reduction: 128-row tiles, two workgroups per tile, instead of 64-row tiles.  The choice looks at per-sample dimensions
   // only, so a sample's result does not depend on the batch size.
   bool sk = false;
-  if (d.splitk_ws && d.mode == 1 && !two_src && !d.upsample && !narrow && (int64_t)d.oh * d.ow <= 128 && d.K / BK >= 16 &&
+  if (d.splitk_ws && d.mode == 1 && !two_src && !d.upsample && !narrow && (int64_t)d.oh * d.ow <= SEVA_SPLITK_MAX_PIXELS && d.K / BK >= 16 &&
       (d.K / BK) % 2 == 0 && tile_height_free(k)) {
     sk = true;
-    p.sk_bn = wide ? 160 : 128;
-    p.sk_tiles = ((d.M + 127) / 128) * ((d.N + p.sk_bn - 1) / p.sk_bn);
+    p.sk_bn = wide ? SEVA_SPLITK_TILE_N : 128;
+    p.sk_tiles = ((d.M + SEVA_SPLITK_TILE_M - 1) / SEVA_SPLITK_TILE_M) * ((d.N + p.sk_bn - 1) / p.sk_bn);
     half_m = false;
   }
   // 3x3 / stride 1 / pad 1 convs whose tile window fits LDS: the input window (+ halo) is staged once per 64-channel slab and the nine

@@ -13,7 +13,7 @@ namespace {
 
 constexpr int GN_THREADS = 256;
 constexpr int GN_MAX_THREADS = 1024;
-constexpr int GN_MAX_SLABS = 1024;  // slab slots per sample in the workspace (the last one holds the finalised statistics)
+constexpr int GN_MAX_SLABS = SEVA_GN_WORKSPACE_SLABS;  // slab slots per sample in the workspace (the last one holds the finalised statistics)
 constexpr int GN_BASE_SLABS = 64;   // slab cap of images up to 8192 pixels (every UNet level)
 constexpr int GN_MAX_GROUPS = 32;
 constexpr int GN_MAX_DENSE = 8;
@@ -138,6 +138,7 @@ __global__ __launch_bounds__(256) void gn_finalize_ch_kernel(GnArgs p) {
   __shared__ double red[4][2];
   const int n = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
   const int C = p.c1 + p.c2, cpg = C / p.groups;
+  static_assert(SEVA_CH_STATS_ROWS == 64, "row blocks of the producers' statistics");
   const int nb = p.hw >> 6;
   const int64_t rb0 = (int64_t)n * nb;
   const int total = cpg * nb;
@@ -475,7 +476,7 @@ extern "C" int seva_groupnorm_f16(const seva_groupnorm_desc* d, seva_stream_t st
   SEVA_REQUIRE((!a.split_out || d->out_f16) && (!a.split_raw || d->raw_f16), "groupnorm: split_* needs the output it splits");
   SEVA_REQUIRE(!d->stats2 || d->stats1, "groupnorm: stats2 without stats1");
   if (d->stats1) {
-    SEVA_REQUIRE(d->hw % 64 == 0, "groupnorm: producer statistics need hw %% 64 == 0 (hw=%d)", d->hw);
+    SEVA_REQUIRE(d->hw % SEVA_CH_STATS_ROWS == 0, "groupnorm: producer statistics need hw %% 64 == 0 (hw=%d)", d->hw);
     SEVA_REQUIRE(d->c2 == 0 || d->stats2, "groupnorm: statistics must be given for BOTH sources (or none)");
   }
   const int cq = C / 4;

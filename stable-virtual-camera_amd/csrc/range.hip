@@ -24,7 +24,7 @@ constexpr int RG_WORDS = SEVA_RANGE_WORDS;         // 72
 constexpr int RG_SLOTS = 68;                       // words 0 .. 67 are counts
 constexpr int RG_UNROLL = 4;                       // units a thread has in flight
 constexpr int64_t RG_SHARE = SEVA_RANGE_WG_ELEMS;  // elements per workgroup (a multiple of it for tensors above RG_SHARE * RG_MAX_WGS)
-constexpr int64_t RG_MAX_WGS = 2048;
+constexpr int64_t RG_MAX_WGS = SEVA_RANGE_MAX_WGS;
 constexpr int W_ZERO = 0, W_INF = 65, W_NAN = 66, W_ATMAX = 67, W_MAXABS = 68, W_MINABS = 69, W_TOTAL = 70;
 
 template <int DT>

@@ -31,6 +31,7 @@ from . import _native, audit, ops
 from ._arch import Layout
 from ._native import SevaNativeError, require_cuda
 from .ops import audit_mark  # (bound here: the tests' seam swaps this module's `ops` for kernel emulations)
+from .ops import SPLITK_ERROR_SLOT, SPLITK_MAX_PIXELS, splitk_tiles, splitk_workspace_numel  # (likewise: contract arithmetic, no kernel)
 
 F16, F32, U8 = torch.float16, torch.float32, torch.uint8
 # softmax scale of head dim 64 (reference transformer.py:66-72) times log2(e): exp(x) == exp2(x * log2 e)
@@ -447,15 +448,15 @@ class SevaEngine(_EngineBase):
     # ------------------------------------------------------------------ helpers
     def _sk(self, rows=0, hw=0, c=0):
         """Workspace of seva_gemm_desc.splitk_ws (one per engine; its launches are serialised on one stream): lets the library run
-        the convs of small images (the 9x9 level) as split-K.  16384 flags + one 128 x 160 fp32 slot per output tile (>= 512)."""
+        the convs of small images (the 9x9 level) as split-K.  `splitk_workspace_numel` of at least 512 tile slots."""
         if not self.conv_splitk:
             return None
         # sized from the launch (never below 512 slots), so that whether a small-image conv is split depends on the per-sample
         # image size only and not on how many samples are batched (a workspace that cannot hold a launch that qualifies for the
         # split is an error in the library, not a fall-back to unsplit tiles: seva_gemm_desc.splitk_ws)
-        tiles = max(512, ((rows + 127) // 128) * ((c + 127) // 128)) if hw and hw <= 128 else 512
-        tiles = min(tiles, 16382)
-        return self._buf("sk_ws", (16384 + tiles * 128 * 160,), F32, zero=True)
+        tiles = max(512, splitk_tiles(rows, c)) if hw and hw <= SPLITK_MAX_PIXELS else 512
+        tiles = min(tiles, SPLITK_ERROR_SLOT - 1)
+        return self._buf("sk_ws", (splitk_workspace_numel(tiles),), F32, zero=True)
 
     def _ln(self, x, pfx, rows, c, fp8=False, split=False):
         if split:  # [hi | lo] for duplicated weights
@@ -634,7 +635,7 @@ class SevaEngine(_EngineBase):
             self._attention_long(q, k, v, att, nb0=n, heads=heads, L=hw, q_strides=(hw * c3, 0, c3),
                                  k_strides=(hw * c3, 0, c3), o_strides=(hw * c, 0, c), split_ws=None)
         elif regime == "joint":  # batch = scene, tokens = (frame, pixel)
-            # long key sequences (L = T hw >= 6144) run K/V-split: the workspace for the two partial results
+            # long key sequences (L = T hw >= ops.ATTN_SPLIT_MIN_LK) run K/V-split: the workspace for the two partial results
             sws = None
             if self.attn_split and T * hw >= ops.ATTN_SPLIT_MIN_LK:
                 sws = self._buf("attn_split", (ops.attention_split_workspace_numel(n // T, heads, T * hw, self.attn_split_max),), F32)

@@ -16,8 +16,8 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SEVA_HIP_LIB: A/B benchmarking of two builds of the same library (tools/); default = the in-tree build
 LIB_PATH = os.environ.get("SEVA_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libseva_hip.so")
-ABI_VERSION = 12
-PROF_CLASSES = 5
+ABI_VERSION = 12   # SEVA_ABI_VERSION
+PROF_CLASSES = 5   # SEVA_PROF_CLASSES
 PROF_NAMES = ("gemm", "conv", "attention", "norm", "elementwise")
 
 
@@ -113,7 +113,8 @@ class RangeDesc(C.Structure):
     ]
 
 
-# name -> (restype, argtypes); must list every symbol declared in include/seva_hip.h
+# name -> (restype, argtypes): every symbol declared in include/seva_hip.h (tests/test_abi_cpu.py compares these, the Structures
+# above and their layout with the header)
 SYMBOLS = {
     "seva_last_error": (c_char_p, []),
     "seva_last_plan": (c_char_p, []),

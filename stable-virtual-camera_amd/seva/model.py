@@ -165,7 +165,7 @@ class Seva(nn.Module):
     def set_precision(self, precision: str, attention: str | None = None, ff: str | None = None, split=None) -> "Seva":
         """"f16" (default, the parity mode) or "fp8" (BASELINE config 5: e4m3 operands on the fp8 MFMA where the reduction
         length allows; separate accuracy class).  Re-packs the weights on the next forward.
-        attention (fp8 mode only): "f16" (default) or "fp8" -- the long self-attention launches (L >= 2048) with P and V in e4m3
+        attention (fp8 mode only): "f16" (default) or "fp8" -- the long self-attention launches (L >= ops.PV8_MIN_LQ) with P and V in e4m3
         (seva_attention_pv8), an accuracy class of its own; None leaves the choice to SEVA_FP8_ATTENTION (0 / 1, default 0).
         ff (fp8 mode only): "f16" (default) or "fp8" -- the feed-forwards that run the fused f16 kernel in fp8 mode (the C = 320
         level) on its e4m3 sibling (seva_ff_fused_fp8); None leaves the choice to SEVA_FP8_FF (0 / 1, default 0).

@@ -27,7 +27,8 @@ def _lib():
 
 # --- dynamic-range audit (seva/audit.py; the kernel's contract is in include/seva_hip.h) --------------------------------
 RANGE_WORDS = 72         # SEVA_RANGE_WORDS
-RANGE_WG_ELEMS = 32768   # SEVA_RANGE_WG_ELEMS: elements one workgroup of the counting kernel takes (tensors up to 2048 of them)
+RANGE_WG_ELEMS = 32768   # SEVA_RANGE_WG_ELEMS: elements one workgroup of the counting kernel takes (tensors up to RANGE_MAX_WGS of them)
+RANGE_MAX_WGS = 2048     # SEVA_RANGE_MAX_WGS: most workgroups (partial tables) of the counting kernel
 RANGE_DTYPES = {F32: 0, F16: 1, U8: 2}  # SEVA_RANGE_F32 / _F16 / _E4M3
 
 # wrapper name -> names of its floating-point (f32 / f16 / e4m3) output parameters; filled by `_audited`.  While a recorder is
@@ -275,7 +276,7 @@ def gemm_split_out(a: torch.Tensor, w: torch.Tensor, **kw) -> None:
     gemm(a, w, split_out=True, **kw)
 
 
-STATS_ROWS = 64  # rows per block of the epilogue-emitted GroupNorm statistics (include/seva_hip.h: seva_gemm_desc.ch_stats)
+STATS_ROWS = 64  # SEVA_CH_STATS_ROWS: rows per block of the epilogue-emitted GroupNorm statistics (seva_gemm_desc.ch_stats)
 
 
 def channel_stats_shape(rows: int, channels: int) -> tuple[int, int, int]:
@@ -287,8 +288,11 @@ def channel_stats_shape(rows: int, channels: int) -> tuple[int, int, int]:
 # waits for its producer with a BOUNDED spin (csrc/gemm.hip); a give-up leaves a wrong tile and counts itself in int slot
 # SPLITK_ERROR_SLOT of the workspace.  `check_handoffs` makes that loud: it is called where a host sync exists anyway (end of a
 # sampler trajectory, `prof_collect`, the GPU tests), never inside the step loop.
-SPLITK_FLAGS = 16384
-SPLITK_ERROR_SLOT = 16383
+SPLITK_FLAGS = 16384       # SEVA_SPLITK_FLAGS: int flags at the head of the workspace
+SPLITK_ERROR_SLOT = 16383  # SEVA_SPLITK_ERROR_SLOT: a launch has fewer tiles than this
+SPLITK_TILE_M = 128        # SEVA_SPLITK_TILE_M x
+SPLITK_TILE_N = 160        # SEVA_SPLITK_TILE_N: the fp32 slot of one output tile
+SPLITK_MAX_PIXELS = 128    # SEVA_SPLITK_MAX_PIXELS: output pixels per sample up to which a conv qualifies for the split
 _handoff_ws: dict = {}
 
 
@@ -320,10 +324,19 @@ def check_handoffs() -> None:
             "affected launches are wrong (flags re-armed; rerun, or set SEVA_CONV_SPLITK=0)")
 
 
+def splitk_tiles(rows: int, channels: int) -> int:
+    """Upper bound of the output tiles of a split-K launch: SPLITK_TILE_M rows by 128 columns, the narrower of the kernels' two widths."""
+    return ((rows + SPLITK_TILE_M - 1) // SPLITK_TILE_M) * ((channels + 127) // 128)
+
+
+def splitk_workspace_numel(tiles: int) -> int:
+    """fp32 elements of a split-K workspace for `tiles` output tiles: the flags, then one SPLITK_TILE_M x SPLITK_TILE_N slot each."""
+    return SPLITK_FLAGS + tiles * SPLITK_TILE_M * SPLITK_TILE_N
+
+
 def splitk_workspace(max_rows: int, max_channels: int, device) -> torch.Tensor:
-    """Zeroed workspace for `conv3x3(splitk_ws=...)`: 16384 flags + one fp32 128 x 160 tile per output tile."""
-    tiles = max(512, ((max_rows + 127) // 128) * ((max_channels + 127) // 128))
-    return torch.zeros(16384 + tiles * 128 * 160, dtype=F32, device=device)
+    """Zeroed workspace for `conv3x3(splitk_ws=...)` (seva_gemm_desc.splitk_ws), at least 512 tile slots."""
+    return torch.zeros(splitk_workspace_numel(max(512, splitk_tiles(max_rows, max_channels))), dtype=F32, device=device)
 
 
 def _stats_ptr(ch_stats, M, N, out_f32):
@@ -578,15 +591,16 @@ def attention(
     check(_lib().seva_attention_f16(C.byref(d), stream_ptr(q.device)), "seva_attention_f16")
 
 
-ATTN_SPLIT_MIN_LK = 6144  # key length from which seva_attention_f16 splits the K/V range in two (include/seva_hip.h)
+ATTN_SPLIT_MIN_LK = 6144     # SEVA_ATTN_SPLIT_MIN_LK: key length from which seva_attention_f16 splits the K/V range in two
+ATTN_SPLIT_ROW_FLOATS = 66   # SEVA_ATTN_SPLIT_ROW_FLOATS: per split and query row, 64 floats of un-normalised O plus (m, l)
 
 
 def attention_split_workspace_numel(batch: int, heads: int, lq: int, nsplit: int = 2) -> int:
-    """fp32 elements of `attention(split_ws=...)`: per split, 64 floats of un-normalised O plus (m, l) per query row."""
-    return nsplit * batch * heads * lq * 66
+    """fp32 elements of `attention(split_ws=...)`."""
+    return nsplit * batch * heads * lq * ATTN_SPLIT_ROW_FLOATS
 
 
-PV8_MIN_LQ = 2048  # query length from which seva_attention_f16 runs attn16_kernel: the launches the fp8 P.V kernel replaces
+PV8_MIN_LQ = 2048  # SEVA_ATTN_LONG_MIN_LQ: query length from which seva_attention_f16 runs attn16_kernel, the launches the fp8 P.V kernel replaces
 
 
 def _v_fp8_parts(batch: int, heads: int, lk: int) -> tuple[int, int]:
@@ -645,7 +659,7 @@ def attention_pv8(q: torch.Tensor, k: torch.Tensor, ws: torch.Tensor, out: torch
     check(_lib().seva_attention_pv8(C.byref(d), v8, sc, stream_ptr(q.device)), "seva_attention_pv8")
 
 
-GN_WORKSPACE_SLABS = 1024  # include/seva_hip.h SEVA_GN_WORKSPACE_SLABS
+GN_WORKSPACE_SLABS = 1024  # SEVA_GN_WORKSPACE_SLABS
 
 
 def groupnorm_workspace(n: int, device) -> torch.Tensor:

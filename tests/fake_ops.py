@@ -7,6 +7,9 @@ import math
 import torch
 import torch.nn.functional as F
 
+# the contract constants and the pure size arithmetic are the product's own (seva.ops imports without the library)
+from seva.ops import ATTN_SPLIT_MIN_LK, GN_WORKSPACE_SLABS, STATS_ROWS, attention_split_workspace_numel, channel_stats_shape  # noqa: F401
+
 F16, F32, U8 = torch.float16, torch.float32, torch.uint8
 
 
@@ -31,15 +34,8 @@ def dequantize_weight_fp8(w8, w_exp):
     return _from_fp8(w8) * torch.exp2(w_exp.float() - 127.0)[:, None]
 
 
-STATS_ROWS = 64
-
-
 def splitk_workspace(max_rows, max_channels, device):
     return torch.zeros(16, dtype=F32)
-
-
-def channel_stats_shape(rows, channels):
-    return ((rows + STATS_ROWS - 1) // STATS_ROWS, 2, channels)
 
 
 def _emit_stats(acc, ch_stats):
@@ -151,13 +147,6 @@ def conv3x3(x, w, *, stride=1, upsample=False, bias=None, row_add=None, rows_per
               out_f16, False, ch_stats=ch_stats)
 
 
-ATTN_SPLIT_MIN_LK = 6144
-
-
-def attention_split_workspace_numel(batch, heads, lq, nsplit=2):
-    return nsplit * batch * heads * lq * 66
-
-
 def attention(q, k, v, out, *, nb0, nb1, heads, lq, lk, q_strides, k_strides, o_strides, scale=0.125,
               q_prescaled=False, split_ws=None):
     if q_prescaled:  # q carries scale * log2(e): softmax base 2
@@ -168,9 +157,6 @@ def attention(q, k, v, out, *, nb0, nb1, heads, lq, lk, q_strides, k_strides, o_
     att = torch.einsum("abqhd,abkhd->abhqk", qv, kv) * scale
     o = torch.einsum("abhqk,abkhd->abqhd", torch.softmax(att, -1), vv)
     view(out, o_strides, lq).copy_(o.half())
-
-
-GN_WORKSPACE_SLABS = 1024  # include/seva_hip.h SEVA_GN_WORKSPACE_SLABS
 
 
 def groupnorm_workspace(n, device):

@@ -4,9 +4,8 @@ device the tensor is on.  tests/test_range_cpu.py holds it against an independen
 tests compare the kernel with it word for word.  Never imported by the product."""
 import torch
 
-WORDS = 72
-WG_ELEMS = 32768   # SEVA_RANGE_WG_ELEMS
-MAX_WGS = 2048
+from seva.ops import RANGE_MAX_WGS as MAX_WGS, RANGE_WG_ELEMS as WG_ELEMS, RANGE_WORDS as WORDS
+
 INF32 = 0x7F800000
 FMT_MAX_BITS = {torch.float32: 0x7F7FFFFF, torch.float16: 0x7BFF, torch.uint8: 0x7E}
 

@@ -148,13 +148,6 @@ def test_set_precision_validates_the_ff_option():
         net.set_precision("fp8", ff="int8")
 
 
-def test_binding_declares_the_new_entry_point():
-    from seva import _native
-    assert _native.ABI_VERSION == 12 and "seva_ff_fused_fp8" in _native.SYMBOLS
-    names = [f[0] for f in _native.FfDesc._fields_]
-    assert names[-2:] == ["w1_exp", "w2_exp"] and names[:-2].index("ln_eps") == len(names) - 3
-
-
 # ------------------------------------------------------------------ tests: engine routing
 def _fake_ops_with_ff8(calls):
     class Ops:

@@ -83,18 +83,7 @@ def test_arguments_are_checked_and_there_is_no_cpu_fallback(fake, monkeypatch):
             fn(a, b)
 
 
-def test_new_symbols_in_header_and_binding():
-    from seva import _native
-    hdr = open(os.path.join(ROOT, "include", "seva_hip.h")).read()
-    declared = set(re.findall(r"\b(seva_[a-z0-9_]+)\s*\(", hdr))
-    for name in ("seva_frame_metrics", "seva_frame_metrics_size"):
-        assert name in declared and name in _native.SYMBOLS, name
-    assert declared == set(_native.SYMBOLS)
-    assert _native.ABI_VERSION == 12  # new symbols and one new struct only
-    fields = re.search(r"typedef struct seva_metrics_desc \{(.*?)\} seva_metrics_desc;", hdr, re.S).group(1)
-    fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)
-    names = [t for t in re.findall(r"[A-Za-z_]\w*", fields) if t not in ("const", "void", "float", "double", "int64_t", "int32_t")]
-    assert names == [f[0] for f in _native.MetricsDesc._fields_], names
+def test_new_symbols_in_header_and_binding():  # (header against binding: tests/test_abi_cpu.py)
     mk = open(os.path.join(ROOT, "stable-virtual-camera_amd", "csrc", "Makefile")).read()
     assert "metrics.hip" in re.search(r"^SRCS\s*:=\s*(.+)$", mk, re.M).group(1).split()
 

@@ -227,12 +227,13 @@ def test_whole_step_graph_is_bit_identical_to_eager_at_72x128(dev, full, monkeyp
 def _attention_kernel(lq, lk, pre, ws, pv8=False):
     """The kernel a launch takes, as seva_attention_f16 / seva_attention_pv8 dispatch it (csrc/attention.hip, attention_fp8.hip;
     default knobs): from the launch's own arguments, so the census needs no kernel trace."""
+    from seva import ops
     if pv8:
-        return "pv8_kernel<true> + combine" if lk >= 6144 and ws else "pv8_kernel<false>"
+        return "pv8_kernel<true> + combine" if lk >= ops.ATTN_SPLIT_MIN_LK and ws else "pv8_kernel<false>"
     if lq <= 32:
         return "attn_kernel<1,32>"
-    if pre and lq >= 2048:
-        return "attn16_kernel<64,true> + combine" if lk >= 6144 and ws else "attn16_kernel<64>"
+    if pre and lq >= ops.PV8_MIN_LQ:
+        return "attn16_kernel<64,true> + combine" if lk >= ops.ATTN_SPLIT_MIN_LK and ws else "attn16_kernel<64>"
     return "attn_kernel<4,64>"
 
 

@@ -407,7 +407,7 @@ def test_conv3x3_at_the_nonsquare_network_shapes(dev, n, ih, iw, cin, cout, stri
         if stats:
             assert torch.equal(st.double(), _block_stats(out, M, cout)), f"conv_win {fam}: statistics"
         if splitk:
-            assert int(ws[:16384].view(torch.int32).abs().sum()) == 0
+            assert int(ws[:ops.SPLITK_FLAGS].view(torch.int32).abs().sum()) == 0
     knobs(conv_win=-1)
     if splitk:
         ops.check_handoffs()
@@ -491,7 +491,7 @@ def test_attention_prescaled_q(dev, B, H, Lq, Lk, spike, two, knobs):
 def test_attention_kv_split(dev, B, H, L, Lk, split, knobs):
     """K/V split of long key sequences (seva_attn_desc.split_ws: two workgroups per query block + an fp32 combine): against an
     fp64 softmax reference, and against the unsplit kernel (same per-tile arithmetic, one extra fp32 re-association at the
-    combine).  Default rule (split -1): lk >= 6144 -> 2 halves; forced factors 2..4 cover uneven tile counts, a ragged last
+    combine).  Default rule (split -1): lk >= ops.ATTN_SPLIT_MIN_LK -> 2 halves; forced factors 2..4 cover uneven tile counts, a ragged last
     tile in the last split and spikes that trigger the rescale branch in only one of the splits.  Without a workspace, or with
     the knob at 0, nothing is split (bitwise the unsplit result)."""
     from seva import ops
@@ -884,7 +884,7 @@ def test_conv_splitk_workspace_too_small_is_an_error(dev):
     x = _ints((n, 9, 9, cin), -2, 2, dev, 1).half()
     w = pack_conv3x3(_ints((cout, cin, 3, 3), -1, 1, dev, 2)).half().to(dev)
     out = torch.empty((n * 81, cout), device=dev)
-    small = ops.splitk_workspace(2 * 81, cout, dev)[: 16384 + 4 * 128 * 160].contiguous()  # 4 tile slots; the launch has 27 x 8 tiles
+    small = ops.splitk_workspace(2 * 81, cout, dev)[: ops.splitk_workspace_numel(4)].contiguous()  # 4 tile slots; the launch has 27 x 8 tiles
     with pytest.raises(SevaNativeError, match="splitk_ws too small"):
         ops.conv3x3(x, w, out_f32=out, splitk_ws=small)
     ops.conv3x3(x, w, out_f32=out, splitk_ws=ops.splitk_workspace(n * 81, cout, dev))  # the right size runs
@@ -921,7 +921,7 @@ def test_conv_splitk_small_images(dev, n, ih, iw, cin, cout, stride):
         ops.conv3x3((x, x2)[it & 1], (wp, wp2)[it & 1], stride=stride, bias=bias, row_add=emb, rows_per_group=oh * ow,
                     residual=res, out_f32=o, splitk_ws=ws)
         assert torch.equal(o, refs[it & 1]), f"launch {it}: max diff {(o - refs[it & 1]).abs().max()}"
-        assert int(ws[:16384].view(torch.int32).abs().sum()) == 0  # flags re-armed, error slot (16383) untouched
+        assert int(ws[:ops.SPLITK_FLAGS].view(torch.int32).abs().sum()) == 0  # flags re-armed, error slot (ops.SPLITK_ERROR_SLOT) untouched
     ops.check_handoffs()  # what the product calls at the end of a trajectory: raises if any consumer gave up
     xr, wr = _rand((n, ih, iw, cin), dev, 6).half(), (pack_conv3x3(_rand((cout, cin, 3, 3), dev, 7, 0.05).cpu()).half().to(dev))
     o1, o2 = torch.empty_like(o), torch.empty_like(o)

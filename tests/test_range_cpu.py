@@ -346,19 +346,12 @@ def test_env_first_call_hook(seam, monkeypatch, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ C-ABI additions
-def test_abi_and_symbols():
-    from seva import _native
-    assert _native.ABI_VERSION == 12
-    assert "seva_tensor_range" in _native.SYMBOLS and "seva_tensor_range_size" in _native.SYMBOLS
-    fields = [f for f, _ in _native.RangeDesc._fields_]
-    assert fields == ["x", "dtype", "rows", "cols", "pitch", "workspace", "workspace_bytes", "out"]
+def test_abi_and_symbols():  # (symbols, struct and ABI version against the binding: tests/test_abi_cpu.py)
     hdr = open(os.path.join(ROOT, "include", "seva_hip.h")).read()
     assert "int seva_tensor_range(const seva_range_desc* d, seva_stream_t stream);" in hdr and "#define SEVA_RANGE_WORDS 72" in hdr
     assert f"#define SEVA_RANGE_WG_ELEMS {R.WG_ELEMS}" in hdr
     mk = open(os.path.join(ROOT, "stable-virtual-camera_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRCS := .*\brange\.hip\b", mk, re.M) and "FLAGS_range := -fno-vectorize -fno-slp-vectorize" in mk
-    cap = open(os.path.join(ROOT, "stable-virtual-camera_amd", "csrc", "capi.hip")).read()
-    assert "int seva_abi_version(void) { return 12; }" in cap
 
 
 # ------------------------------------------------------------------------------------------------ logical areas, buffer names, the report file

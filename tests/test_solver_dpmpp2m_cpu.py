@@ -3,8 +3,6 @@ history ownership, interface.  The HIP operators are emulated the way tests/test
 the new operator `ops.cfg_multistep` is emulated in this file in fp32 torch.  The fp64 restatement of the solver (sgm's
 DPMPP2MSampler form, mult1..4 from t = -ln sigma) lives here too."""
 import math
-import os
-import re
 
 import pytest
 import torch
@@ -277,12 +275,3 @@ def test_default_path_is_untouched_and_multistep_draws_no_noise(cpu_ops, monkeyp
     sm.noise_fn = noise_fn
     _solve("dpmpp2m", 5, sampler=sm)
     assert not draws and not noised and len(cpu_ops) == 5
-
-
-def test_symbol_is_bound_and_declared():
-    from conftest import ROOT
-    from seva import _native
-    assert "seva_cfg_multistep_f32" in _native.SYMBOLS and _native.ABI_VERSION == 12
-    assert len(_native.SYMBOLS["seva_cfg_multistep_f32"][1]) == 12
-    header = open(os.path.join(ROOT, "include", "seva_hip.h")).read()
-    assert re.search(r"\bint\s+seva_cfg_multistep_f32\s*\(", header)
