@@ -1,10 +1,12 @@
 """Whole-step hipGraph for `EulerEDMSampler.sampler_step` (north_star: "sampler loop captured in hipGraph").
 
-One denoising step -- noise perturbation, CFG input assembly, nearest-sigma lookup, the ~600 kernels of the
-CFG-batched network call, denoiser combine, guidance and the Euler update (reference seva/sampling.py:347-368
-plus everything it calls) -- is captured ONCE per trajectory into a hipGraph and replayed for the remaining steps.
-Per-step values enter through static device buffers (x, eps, sigma, next_sigma), so the graph is the step as a
-function, not a recording of one step's numbers.
+One denoising step of either solver -- CFG input assembly, nearest-sigma lookup, the ~600 kernels of the CFG-batched
+network call, denoiser combine, and then the solver's own part: noise perturbation, guidance and the Euler update
+(reference seva/sampling.py:347-368 plus everything it calls), or guidance, the DPM-Solver++(2M) update and the new
+history in one kernel -- is captured ONCE per trajectory into a hipGraph and replayed for the remaining steps.
+Per-step values enter through static device buffers (sigma, next_sigma, x, and eps or the previous sigma), so the graph
+is the step as a function, not a recording of one step's numbers.  The protocol -- eager warm-up, capture, fallback,
+replay -- is `StepGraphCache.run`, the same for both solvers; they differ in the key, the closure and the fourth input.
 
 PyTorch is used for what the task assigns to it -- device memory and streams: `torch.cuda.CUDAGraph` (= hipGraph on
 ROCm) drives hipStreamBeginCapture / hipGraphInstantiate / hipGraphLaunch and gives the captured region a private
@@ -12,16 +14,20 @@ allocator pool, so the few host-sized torch ops inside the step (`torch.cat` of 
 argmin over the 1000-entry sigma table) keep stable addresses across replays.  All latent-sized math inside the
 graph is libseva_hip.so kernels launched on the capturing stream.
 
-What stays OUTSIDE the graph on purpose: the per-step Gaussian draw (`noise_fn`, default `torch.randn_like`): the
-generator's Philox offset must advance per step exactly as in an eager run (and tests inject recorded eps), so
-eps is drawn eagerly and copied into a static buffer -- graph and eager runs are bit-identical.
+What stays OUTSIDE the graph on purpose: the per-step Gaussian draw of the Euler step (`noise_fn`, default
+`torch.randn_like`): the generator's Philox offset must advance per step exactly as in an eager run (and tests inject
+recorded eps), so eps is drawn eagerly and copied into a static buffer -- graph and eager runs are bit-identical.  The
+multistep solver's history buffer is not an input either: the captured kernel reads and writes it in place, by address.
 """
 
 from __future__ import annotations
 
 import os
+import warnings
 
 import torch
+
+from . import _native
 
 
 def enabled() -> bool:
@@ -75,6 +81,22 @@ class StepGraphCache:
         self.captures = 0
 
     @staticmethod
+    def flat_key(obj) -> tuple:
+        """Flatten dict / tensor / scalar arguments into a tuple compared by identity (tensors, callables) or value."""
+        if isinstance(obj, dict):
+            out = []
+            for k in sorted(obj):
+                out.append(k)
+                out.extend(StepGraphCache.flat_key(obj[k]))
+            return tuple(out)
+        if isinstance(obj, (list, tuple)):
+            out = []
+            for v in obj:
+                out.extend(StepGraphCache.flat_key(v))
+            return tuple(out)
+        return (obj,)
+
+    @staticmethod
     def _same(a, b) -> bool:
         if len(a) != len(b):
             return False
@@ -93,3 +115,37 @@ class StepGraphCache:
 
     def reset(self):
         self.key, self.state, self.graph, self.keep = None, 0, None, None
+
+    def run(self, key, fn, inputs, *, eligible, keep=None):
+        """One step `fn(*inputs)` under the protocol: eager while not `eligible`; else the first step of `key` eagerly, the
+        second captured and replayed, every later one replayed.  `fn` is the sync-free step math, `inputs` the tensors whose
+        values are refreshed per replay; `keep()`, read after a capture succeeded, is what the graph reads by address and the
+        cache therefore holds for as long as the graph lives."""
+        if not eligible:
+            return fn(*inputs)
+        self.lookup(key)
+        if self.state == 0:
+            # warm-up = the real first step, launched eagerly (also without the network-only graph: it would be
+            # captured for this one call only)
+            with _native.eager_network():
+                out = fn(*inputs)
+            self.state = 1
+            return out
+        if self.graph is None:
+            try:
+                # capture records the step without running it: what `fn` updates in place is updated by the replays alone
+                self.graph = StepGraph(fn, inputs)
+                self.captures += 1
+                self.keep = keep() if keep is not None else None
+            except Exception as e:  # a step that cannot be captured (foreign denoiser with host syncs, ...) runs eagerly
+                self.disabled = True
+                self.reset()
+                try:
+                    torch.cuda.synchronize(inputs[0].device)
+                except Exception:
+                    pass
+                warnings.warn(f"seva: whole-step hipGraph capture failed ({type(e).__name__}: {e}); "
+                              "falling back to eager steps", RuntimeWarning)
+                return fn(*inputs)
+        # the graph's output buffer is overwritten by the next replay: hand the caller its own copy (435 KB)
+        return self.graph(*inputs).clone()

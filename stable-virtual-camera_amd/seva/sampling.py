@@ -25,7 +25,7 @@ import numpy as np
 import torch
 from tqdm import tqdm
 
-from . import _native, _stepgraph, audit, ops
+from . import _stepgraph, audit, ops
 from ._native import SevaNativeError
 
 
@@ -284,8 +284,13 @@ class MultiviewCFG(VanillaCFG):
         """Called by `EulerEDMSampler.prepare_sampling_loop`: a new trajectory never reuses an old rule."""
         self._rule_cache = None
 
-    def _ruled_scale(self, scale, c2w, K, input_frame_mask):
-        """scale_rule(...) with its boolean-mask indexing (a host sync) paid once per trajectory.
+    def _rule(self, scale, c2w, K, input_frame_mask, ndim):
+        """The step-invariant per-frame scale (the hook subclasses override; this rule has no use for `ndim`)."""
+        return self.scale_rule(scale, c2w, K, input_frame_mask)
+
+    def _ruled_scale(self, scale, c2w, K, input_frame_mask, ndim):
+        """`_rule(...)`, whose boolean-mask indexing is a host sync that must not sit inside a captured step, evaluated once
+        per trajectory.
 
         The cache entry keeps STRONG references to the very tensor objects it was computed from and matches by
         object identity (`is`), so an address the caching allocator hands out again for another scene can never
@@ -300,12 +305,12 @@ class MultiviewCFG(VanillaCFG):
                 not isinstance(s0, torch.Tensor) and s0 == scale)
             if same_scale and a0 is c2w and b0 is K and m0 is input_frame_mask:
                 return val
-        val = self.scale_rule(scale, c2w, K, input_frame_mask)
+        val = self._rule(scale, c2w, K, input_frame_mask, ndim)
         self._rule_cache = ((scale, c2w, K, input_frame_mask), val)
         return val
 
     def frame_scale(self, x, sigma, scale, c2w=None, K=None, input_frame_mask=None, **_):
-        return self.scale_schedule(sigma, self._ruled_scale(scale, c2w, K, input_frame_mask))
+        return self.scale_schedule(sigma, self._ruled_scale(scale, c2w, K, input_frame_mask, x.ndim))
 
     def __call__(self, x: torch.Tensor, sigma, scale, c2w: torch.Tensor, K: torch.Tensor,  # type: ignore
                  input_frame_mask: torch.Tensor) -> torch.Tensor:
@@ -321,17 +326,8 @@ class MultiviewTemporalCFG(MultiviewCFG):
         idx = torch.arange(num_frames)
         self.distance_matrix = (idx[None] - idx[:, None]).abs()
 
-    def _ruled_scale(self, scale, c2w, K, input_frame_mask, ndim=4):
-        """Temporal ramp + close-frame rule: step-invariant, so (like MultiviewCFG) evaluated once per trajectory and
-        cached by the identity of the tensors it came from; its boolean indexing is a host sync that must not sit
-        inside a captured step."""
-        ent = self._rule_cache
-        if ent is not None:
-            (s0, a0, b0, m0), val = ent
-            same_scale = (s0 is scale) if isinstance(scale, torch.Tensor) else (
-                not isinstance(s0, torch.Tensor) and s0 == scale)
-            if same_scale and a0 is c2w and b0 is K and m0 is input_frame_mask:
-                return val
+    def _rule(self, scale, c2w, K, input_frame_mask, ndim):
+        """Temporal ramp, then the close-frame rule: step-invariant like the base's, and cached by it in the same way."""
         mask = input_frame_mask.reshape(-1, self.num_frames)
         min_distance = (
             self.distance_matrix[None].to(mask.device) + (~mask[:, None]) * self.num_frames
@@ -339,16 +335,7 @@ class MultiviewTemporalCFG(MultiviewCFG):
         min_distance = min_distance / min_distance.max(-1, keepdim=True)[0].clamp(min=1)
         ramp = min_distance * (scale - self.scale_min) + self.scale_min
         ramp = append_dims(ramp.reshape(-1), ndim)
-        val = self.scale_rule(ramp, c2w, K, mask.flatten(0, 1))
-        self._rule_cache = ((scale, c2w, K, input_frame_mask), val)
-        return val
-
-    def frame_scale(self, x, sigma, scale, c2w=None, K=None, input_frame_mask=None, **_):
-        return self.scale_schedule(sigma, self._ruled_scale(scale, c2w, K, input_frame_mask, x.ndim))
-
-    def __call__(self, x: torch.Tensor, sigma, scale, c2w: torch.Tensor, K: torch.Tensor,
-                 input_frame_mask: torch.Tensor) -> torch.Tensor:
-        return _cfg_combine(x, self.frame_scale(x, sigma, scale, c2w, K, input_frame_mask))
+        return self.scale_rule(ramp, c2w, K, mask.flatten(0, 1))
 
 
 # ------------------------------------------------------------------------------ sampler
@@ -436,21 +423,31 @@ class EulerEDMSampler(object):
         noise_scale = (sigma_hat**2 - sigma**2) ** 0.5 * self.s_noise
         x_noised = torch.empty_like(x)
         ops.add_noise(x, eps, _f32c(noise_scale), x_noised)
-        if self.cfg_split is None:
-            denoised2 = denoiser(*self.guider.prepare_inputs(x_noised, sigma_hat, cond, uc))
-        else:
-            denoised2 = self._denoise_cfg_split(denoiser, x_noised, sigma_hat, cond, uc)
+        denoised2 = self._denoised_pair(denoiser, x_noised, sigma_hat, cond, uc)
         dt = next_sigma - sigma_hat
         out = torch.empty_like(x)
-        if hasattr(self.guider, "frame_scale"):
-            # CFG combine + to_d + Euler update in one pass
-            fs = self.guider.frame_scale(denoised2, sigma_hat, scale, **guider_kwargs)
-            ops.cfg_euler(x_noised, _f32c(denoised2), _scale_vector(fs, x.shape[0], x.device),
-                          sigma_hat, dt, out)
+        den, fs = self._guidance_operands(denoised2, sigma_hat, scale, x, guider_kwargs)
+        if fs is not None:
+            ops.cfg_euler(x_noised, den, fs, sigma_hat, dt, out)  # CFG combine + to_d + Euler update in one pass
         else:
-            denoised = self.guider(denoised2, sigma_hat, scale, **guider_kwargs)
-            ops.euler_step(x_noised, _f32c(denoised), sigma_hat, dt, out)
+            ops.euler_step(x_noised, den, sigma_hat, dt, out)
         return out
+
+    def _denoised_pair(self, denoiser, x_in, sigma_in, cond, uc):
+        """The [uncond ; cond] denoised latents for (x_in, sigma_in): one CFG-batched network call, or under `cfg_split`
+        this rank's half of it and the other rank's."""
+        if self.cfg_split is None:
+            return denoiser(*self.guider.prepare_inputs(x_in, sigma_in, cond, uc))
+        return self._denoise_cfg_split(denoiser, x_in, sigma_in, cond, uc)
+
+    def _guidance_operands(self, denoised2, sigma_in, scale, x, guider_kwargs):
+        """What the fused update kernels take: (the f32 [uncond ; cond] pair, the per-frame scale vector) for them to
+        combine themselves where the guider can state its `frame_scale`, (the guider's own guided latent, None) where
+        it cannot."""
+        if hasattr(self.guider, "frame_scale"):
+            fs = self.guider.frame_scale(denoised2, sigma_in, scale, **guider_kwargs)
+            return _f32c(denoised2), _scale_vector(fs, x.shape[0], x.device)
+        return _f32c(self.guider(denoised2, sigma_in, scale, **guider_kwargs)), None
 
     def _denoise_cfg_split(self, denoiser, x_noised, sigma_hat, cond, uc):
         """[uncond ; cond] denoised latents with each half of the CFG batch computed by one rank of `cfg_split`'s
@@ -475,22 +472,6 @@ class EulerEDMSampler(object):
         return both
 
     @staticmethod
-    def _flat_key(obj):
-        """Flatten dict / tensor / scalar arguments into a tuple compared by identity (tensors, callables) or value."""
-        if isinstance(obj, dict):
-            out = []
-            for k in sorted(obj):
-                out.append(k)
-                out.extend(EulerEDMSampler._flat_key(obj[k]))
-            return tuple(out)
-        if isinstance(obj, (list, tuple)):
-            out = []
-            for v in obj:
-                out.extend(EulerEDMSampler._flat_key(v))
-            return tuple(out)
-        return (obj,)
-
-    @staticmethod
     def multistep_coefficients(sigma: torch.Tensor, next_sigma: torch.Tensor, prev_sigma: torch.Tensor):
         """DPM-Solver++(2M) coefficients as f32 vectors on the sigmas' device, without a host sync:
         x+ = a x + b D + c D-.   a = s+/s.   Rows without history (prev_sigma <= 0) and rows that land on s+ = 0:
@@ -512,121 +493,58 @@ class EulerEDMSampler(object):
         history in ONE kernel (`ops.cfg_multistep`), which reads D- from `hist` and leaves D there.  Sync-free like
         `_step_math`, and the same code for the first, the second-order and the last step (they differ in a, b, c only), so
         one hipGraph serves them all."""
-        if self.cfg_split is None:
-            denoised2 = denoiser(*self.guider.prepare_inputs(x, sigma, cond, uc))
-        else:
-            denoised2 = self._denoise_cfg_split(denoiser, x, sigma, cond, uc)
+        denoised2 = self._denoised_pair(denoiser, x, sigma, cond, uc)
         a, b, c = self.multistep_coefficients(sigma, next_sigma, prev_sigma)
         out = torch.empty_like(x)
-        if hasattr(self.guider, "frame_scale"):
-            fs = self.guider.frame_scale(denoised2, sigma, scale, **guider_kwargs)
-            ops.cfg_multistep(x, _f32c(denoised2), _scale_vector(fs, x.shape[0], x.device), hist, a, b, c, out, hist)
-        else:
-            denoised = self.guider(denoised2, sigma, scale, **guider_kwargs)
-            ops.cfg_multistep(x, _f32c(denoised), None, hist, a, b, c, out, hist)
+        den, fs = self._guidance_operands(denoised2, sigma, scale, x, guider_kwargs)
+        ops.cfg_multistep(x, den, fs, hist, a, b, c, out, hist)
         return out
 
-    def _multistep_step(self, sigma, next_sigma, denoiser, x, scale, cond, uc, guider_kwargs):
-        """`sampler_step` under solver="dpmpp2m": same eager warm-up / capture / replay protocol as the Euler step."""
+    def _multistep_history(self, x, sigma):
+        """(the history buffer D-, the previous step's sigma or 0 = "no history" to the coefficients) for one dpmpp2m step."""
         hist = self._ms_den
         if hist is None or hist.shape != x.shape or hist.device != x.device:
             # an ordinary tensor even under torch.inference_mode(), like the static buffers of `_stepgraph.StepGraph`
             with torch.inference_mode(False):
                 hist = self._ms_den = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
             self._ms_have = False
-        prev_sigma = self._ms_sigma if self._ms_have else torch.zeros_like(sigma)  # 0 = "no history" to the coefficients
-        out = self._multistep_dispatch(sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs)
-        self._ms_sigma, self._ms_have = sigma, True
-        return out
+        return hist, (self._ms_sigma if self._ms_have else torch.zeros_like(sigma))
 
-    def _multistep_dispatch(self, sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs):
-        cache = self._step_graphs
+    def _whole_step_graph_eligible(self, x) -> bool:
+        """Whether this step goes through the whole-step hipGraph protocol (`_stepgraph.StepGraphCache.run`)."""
+        # (CFG-split steps are not captured as one graph: the per-step all-gather runs eagerly between the two ranks;
+        #  the network call itself is still replayed from its own hipGraph)
         # (under an audit recorder the step is neither captured nor replayed: its launches must run, and be seen, one by one)
-        use_graph = (x.is_cuda and not cache.disabled and _stepgraph.enabled() and self.cfg_split is None and ops._AUDIT is None
-                     and not torch.cuda.is_current_stream_capturing())
-        if not use_graph:
-            return self._multistep_math(sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs)
-        key = ("dpmpp2m", tuple(x.shape), hist, self.guider, denoiser) + self._flat_key((scale, cond, uc, guider_kwargs))
-        ent = cache.lookup(key)
-        if ent.state == 0:
-            with _native.eager_network():
-                out = self._multistep_math(sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs)
-            ent.state = 1
-            return out
-        if ent.graph is None:
-            try:
-                # capture records the step without running it: the history buffer is updated by the replays alone
-                ent.graph = _stepgraph.StepGraph(
-                    lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, denoiser, scale, cond, uc, guider_kwargs),
-                    (sigma, next_sigma, x, prev_sigma))
-                cache.captures += 1
-                ent.keep = getattr(self.guider, "_rule_cache", None)  # the graph reads the warm-up step's rule tensor: it must outlive `reset_rule_cache`
-            except Exception as e:
-                import warnings
-
-                cache.disabled = True
-                cache.reset()
-                try:
-                    torch.cuda.synchronize(x.device)
-                except Exception:
-                    pass
-                warnings.warn(f"seva: whole-step hipGraph capture failed ({type(e).__name__}: {e}); "
-                              "falling back to eager steps", RuntimeWarning)
-                return self._multistep_math(sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs)
-        return ent.graph(sigma, next_sigma, x, prev_sigma).clone()
+        return (x.is_cuda and not self._step_graphs.disabled and _stepgraph.enabled() and self.cfg_split is None
+                and ops._AUDIT is None and not torch.cuda.is_current_stream_capturing())
 
     def sampler_step(self, sigma: torch.Tensor, next_sigma: torch.Tensor, denoiser, x: torch.Tensor,
                      scale, cond: dict, uc: dict, gamma: float = 0.0, **guider_kwargs) -> torch.Tensor:
-        """One Euler-EDM step (reference sampling.py:347-368).  From the second step of a trajectory on, the whole
-        step is replayed from one hipGraph (see `_stepgraph`); the first step runs eagerly and warms every cache.
-        Stays a callable unit for `GradioTrackedSampler` (reference eval.py:1037-1089)."""
+        """One Euler-EDM step (reference sampling.py:347-368), or one DPM-Solver++(2M) step under solver="dpmpp2m".  From
+        the second step of a trajectory on, the whole step is replayed from one hipGraph (see `_stepgraph`); the first step
+        runs eagerly and warms every cache.  Stays a callable unit for `GradioTrackedSampler` (reference eval.py:1037-1089)."""
         _need_gpu(x)
         x = _f32c(x)
         sigma = _f32c(sigma)
         next_sigma = _f32c(next_sigma)
-        if self.solver == "dpmpp2m":  # deterministic: no noise draw, no add_noise; `gamma` has nothing to act on
-            return self._multistep_step(sigma, next_sigma, denoiser, x, scale, cond, uc, guider_kwargs)
-        eps = _f32c(self.noise_fn(x))  # drawn eagerly: the generator advances per step exactly as in the reference
-        gamma = float(gamma)
-        cache = self._step_graphs
-        # (CFG-split steps are not captured as one graph: the per-step all-gather runs eagerly between the two ranks;
-        #  the network call itself is still replayed from its own hipGraph)
-        # (under an audit recorder the step is neither captured nor replayed: its launches must run, and be seen, one by one)
-        use_graph = (x.is_cuda and not cache.disabled and _stepgraph.enabled() and self.cfg_split is None and ops._AUDIT is None
-                     and not torch.cuda.is_current_stream_capturing())
-        if not use_graph:
-            return self._step_math(sigma, next_sigma, x, eps, denoiser, scale, cond, uc, gamma, guider_kwargs)
-        key = (tuple(x.shape), gamma, float(self.s_noise), self.guider, denoiser) + self._flat_key(
-            (scale, cond, uc, guider_kwargs))
-        ent = cache.lookup(key)
-        if ent.state == 0:
-            # warm-up = the real first step, launched eagerly (also without the network-only graph: it would be
-            # captured for this one call only)
-            with _native.eager_network():
-                out = self._step_math(sigma, next_sigma, x, eps, denoiser, scale, cond, uc, gamma, guider_kwargs)
-            ent.state = 1
-            return out
-        if ent.graph is None:
-            try:
-                ent.graph = _stepgraph.StepGraph(
-                    lambda s, n, xx, ee: self._step_math(s, n, xx, ee, denoiser, scale, cond, uc, gamma, guider_kwargs),
-                    (sigma, next_sigma, x, eps))
-                cache.captures += 1
-                ent.keep = getattr(self.guider, "_rule_cache", None)  # the graph reads the warm-up step's rule tensor: it must outlive `reset_rule_cache`
-            except Exception as e:  # a step that cannot be captured (foreign denoiser with host syncs, ...) runs eagerly
-                import warnings
-
-                cache.disabled = True
-                cache.reset()
-                try:
-                    torch.cuda.synchronize(x.device)
-                except Exception:
-                    pass
-                warnings.warn(f"seva: whole-step hipGraph capture failed ({type(e).__name__}: {e}); "
-                              "falling back to eager steps", RuntimeWarning)
-                return self._step_math(sigma, next_sigma, x, eps, denoiser, scale, cond, uc, gamma, guider_kwargs)
-        # the graph's output buffer is overwritten by the next replay: hand the caller its own copy (435 KB)
-        return ent.graph(sigma, next_sigma, x, eps).clone()
+        multistep = self.solver == "dpmpp2m"
+        flat = _stepgraph.StepGraphCache.flat_key((scale, cond, uc, guider_kwargs))
+        # per solver: the cache key (everything the closure holds), the sync-free step as a closure, the fourth graph input
+        if multistep:  # deterministic: no noise draw, no add_noise; `gamma` has nothing to act on
+            hist, fourth = self._multistep_history(x, sigma)
+            key = ("dpmpp2m", tuple(x.shape), hist, self.guider, denoiser) + flat
+            fn = lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, denoiser, scale, cond, uc, guider_kwargs)  # noqa: E731
+        else:
+            fourth = _f32c(self.noise_fn(x))  # eps, drawn eagerly: the generator advances per step exactly as in the reference
+            gamma = float(gamma)
+            key = (tuple(x.shape), gamma, float(self.s_noise), self.guider, denoiser) + flat
+            fn = lambda s, n, xx, ee: self._step_math(s, n, xx, ee, denoiser, scale, cond, uc, gamma, guider_kwargs)  # noqa: E731
+        # keep: the graph reads the warm-up step's rule tensor, which must therefore outlive `reset_rule_cache`
+        out = self._step_graphs.run(key, fn, (sigma, next_sigma, x, fourth), eligible=self._whole_step_graph_eligible(x),
+                                    keep=lambda: getattr(self.guider, "_rule_cache", None))
+        if multistep:
+            self._ms_sigma, self._ms_have = sigma, True
+        return out
 
     def __call__(self, denoiser, x: torch.Tensor, scale, cond: dict, uc: dict | None = None,
                  num_steps: int | None = None, verbose: bool = True, **guider_kwargs) -> torch.Tensor:

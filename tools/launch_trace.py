@@ -3,8 +3,9 @@
     python tools/launch_trace.py TREE [--out DIR] [--against DIGESTS]
 
 imports the package and the test helpers from the checkout TREE, replaces the loaded library by a stub that records every `seva_*`
-call (symbol, every descriptor field, every scalar) and returns 0, and runs the engines on CPU tensors: nothing is computed, so a
-configuration costs a second or two whatever the image size.  Pointers are canonicalised afterwards: a value inside a tensor of
+call (symbol, every descriptor field, every scalar) and returns 0, and runs the engines, the operators and the sampler (three steps
+per solver and guider: on the CPU a step is not eligible for capture, so this is its eager path) on CPU tensors: nothing is computed,
+so a configuration costs a second or two whatever the image size.  Pointers are canonicalised afterwards: a value inside a tensor of
 `eng.W`, the arena or the inputs becomes (kind, key, byte offset), any other one the ordinal of its first appearance.  A record =
 the engine's scalar attributes, a SHA-256 per packed weight, the arena's keys, the calls.  A host-side refactor must leave every
 record byte-identical: run the tool on a worktree of the parent commit and on the new tree, and hand the first run's digest file
@@ -390,6 +391,109 @@ def operator_records():
     record("ops: fused feed-forwards and attention", lines)
 
 
+# ------------------------------------------------------------------------------------------------------------------ sampler
+SAMPLER_OPS = ("scale_rows", "add_noise", "replace_blend", "denoiser_combine", "cfg_combine", "cfg_euler", "euler_step", "cfg_multistep")
+SAMPLER_T, SAMPLER_STEPS = 4, 3
+
+
+@contextlib.contextmanager
+def keeping_arguments(kept, host):
+    """While active, every tensor handed to an operator of the sampler stays alive in `kept`, the step's own temporaries included:
+    a freed block could be handed out again, and an ordinal would no longer mean identity.  The per-frame vectors among them (host
+    math: sigmas, noise scales, guidance scales, solver coefficients) are written to `host` by value."""
+    real = {name: getattr(ops, name) for name in SAMPLER_OPS}
+
+    def wrap(name, fn):
+        def call(*a, **kw):
+            ts = [t for t in (*a, *kw.values()) if isinstance(t, torch.Tensor)]
+            kept.extend(ts)
+            host.append(f"host {name} " + json.dumps([t.tolist() for t in ts if t.ndim == 1]))
+            return fn(*a, **kw)
+        return call
+
+    for name, fn in real.items():
+        setattr(ops, name, wrap(name, fn))
+    try:
+        yield
+    finally:
+        for name, fn in real.items():
+            setattr(ops, name, fn)
+
+
+def analytic_denoiser(xx, ss, cc):
+    """[uncond ; cond] halves of D = mu (1 - k) + x k, k = 1 / (1 + sigma^2): plain torch, no operator call"""
+    n = xx.shape[0] // 2
+    k = (1.0 / (1.0 + ss * ss)).view(-1, 1, 1, 1)
+    mu = torch.cat([torch.full((n,), 0.3), torch.full((n,), -0.2)]).view(-1, 1, 1, 1)
+    return mu * (1 - k) + xx * k
+
+
+def sampler_guider(S, kind):
+    """(guider, guider_kwargs)"""
+    T = SAMPLER_T
+    mask = torch.zeros(T, dtype=torch.bool)
+    mask[0] = True
+    views = {"c2w": synth.orbit_c2w(T), "K": synth.default_K(T), "input_frame_mask": mask}
+    if kind == "vanilla":
+        return S.VanillaCFG(), {}
+    if kind == "multiview":
+        return S.MultiviewCFG(1.2), views
+    if kind == "temporal":
+        return S.MultiviewTemporalCFG(T, 1.2), views
+
+    class PlainGuider:  # no `frame_scale`: the sampler calls it, then the plain update
+        def prepare_inputs(self, x, s, c, uc):
+            return S.VanillaCFG().prepare_inputs(x, s, c, uc)
+
+        def __call__(self, x, sigma, scale):
+            return S.ConstantGuidance()(*x.chunk(2), scale)
+
+    return PlainGuider(), {}
+
+
+def sampler_record(solver, kind, s_churn=0.0):
+    from seva import sampling as S
+    guider, guider_kwargs = sampler_guider(S, kind)
+    with environment({}):
+        sm = S.EulerEDMSampler(S.DDPMDiscretization(), guider, num_steps=SAMPLER_STEPS, verbose=False, device="cpu", s_churn=s_churn,
+                               solver=solver)
+        sm.noise_fn = torch.zeros_like
+        inp = {"x": torch.zeros(SAMPLER_T, 4, 8, 8)}
+        kept, host = [], []
+
+        def run():
+            with keeping_arguments(kept, host):
+                return sm(analytic_denoiser, inp["x"], 2.0, {}, {}, **guider_kwargs), kept
+
+        lines = traced(run, lambda: [("in", inp), ("ms", {"den": sm._ms_den})])
+    record(f"sampler {solver} {kind} s_churn={s_churn}", lines + host)
+
+
+def denoiser_record():
+    from seva import sampling as S
+    n = 2 * SAMPLER_T
+    inp = {"x": torch.zeros(n, 4, 8, 8), "sigma": torch.full((n,), 9.3527), "replace": torch.zeros(n, 5, 8, 8)}
+    kept, host = [], []
+
+    def run():
+        with keeping_arguments(kept, host):
+            den = S.DiscreteDenoiser(S.DDPMDiscretization(), num_idx=1000, device="cpu")
+            return den(lambda x, t, cond: 0.5 * x, inp["x"], inp["sigma"], {"replace": inp["replace"]}), kept
+
+    lines = traced(run, lambda: [("in", inp)])
+    record("sampler DiscreteDenoiser with replace", lines + host)
+
+
+def sampler_configurations():
+    from seva import sampling as S
+    S._need_gpu = lambda *a: None
+    for kind in ("vanilla", "multiview", "temporal", "plain"):
+        sampler_record("euler", kind)
+        sampler_record("euler", kind, s_churn=0.5)
+        sampler_record("dpmpp2m", kind)
+    denoiser_record()
+
+
 # ------------------------------------------------------------------------------------------------------------------ coverage
 def coverage():
     def field(rec, f):
@@ -417,6 +521,10 @@ def coverage():
         table[f"groupnorm {f}"] = seen("seva_groupnorm_f16", lambda r: field(r, f))
     for s in ("seva_layernorm_f16", "seva_layernorm_fp8", "seva_layernorm_f16_split"):
         table[s] = seen(s)
+    for s in ("seva_cfg_euler_f32", "seva_euler_step_f32", "seva_replace_blend_f32"):
+        table[s] = seen(s)
+    table["seva_cfg_multistep_f32 scale"] = seen("seva_cfg_multistep_f32", lambda r: field(r, "arg2"))
+    table["seva_cfg_multistep_f32 no scale"] = seen("seva_cfg_multistep_f32", lambda r: not field(r, "arg2"))
     print("\ncoverage (recorded calls over all configurations)")
     for k, v in table.items():
         print(f"  {k:32s} {v:7d}")
@@ -435,6 +543,7 @@ unet_configurations()
 vae_configurations()
 clip_record()
 operator_records()
+sampler_configurations()
 missing = coverage()
 split_ok = kv_split_check()
 digests = {name: hashlib.sha256(text.encode()).hexdigest() for name, text in RECORDS.items()}
