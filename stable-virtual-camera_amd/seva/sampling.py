@@ -406,8 +406,10 @@ class EulerEDMSampler(object):
             x.copy_(tmp)
         num_sigmas = len(sigmas)
         s_in = x.new_ones([x.shape[0]])
-        # host copy so the per-step s_tmin/s_tmax test never syncs with the device
-        self._sigmas_host = [float(v) for v in sigmas.detach().cpu()]
+        # host copy so the per-step s_tmin/s_tmax test never syncs with the device.  It keeps the sigmas' dtype: the reference
+        # compares a tensor element with the bounds (l.391), so a bound is rounded to fp32 before the comparison, and a Python
+        # double would put a step on the other side of a bound that lies within half an fp32 ulp of its sigma
+        self._sigmas_host = sigmas.detach().cpu()
         return x, s_in, sigmas, num_sigmas, cond, uc
 
     def get_sigma_gen(self, num_sigmas: int, verbose: bool = True):
