@@ -650,7 +650,7 @@ int seva_tensor_range(const seva_range_desc* d, seva_stream_t stream);
  * Benchmark / debugging knobs. The library reads its SEVA_* environment variables ONCE, when it is loaded (nothing
  * on the launch path calls getenv); a host changes a knob at run time with seva_set_knob (tests, tools).  Names:
  * gemm_chunks, gemm_dbg, gemm_stagger, gemm_bm, gemm_bn, gemm_astat, attn_dbg, attn_no_tr, attn_two, attn_split,
- * gn_min_iter, conv_win (0: per-tap conv gather everywhere; 1 / 2: force the 4-wave / 8-wave family of the window-staged conv kernel)
+ * attn_short2 (32 < lq <= 64 and lk <= 64: 1 = two waves on one K/V buffer, 0 = the four-wave kernel; same bits), gn_min_iter, conv_win (0: per-tap conv gather everywhere; 1 / 2: force the 4-wave / 8-wave family of the window-staged conv kernel)
  * (environment: SEVA_ + upper case).  -1 = unset (default heuristics).  None is needed in production.
  */
 int seva_set_knob(const char* name, int32_t value);

@@ -59,12 +59,17 @@ __device__ __forceinline__ float half_wave_max(float v) {
   return fmaxf(a, b);
 }
 
-template <int NW, int KT, bool USE_TR, bool DBGK, bool PRE>
+// NBUF: buffers of the K/V ring.  3 is the ring.  1 is the short-sequence form (lk <= KT, the host's rule): the only tile goes to the
+// only buffer, nothing is prefetched (nt == 1: attn_ring_start issues tile 0 alone and attn_ring_prefetch never fires), and the
+// workgroup holds 2 * KT * 128 bytes of LDS instead of three times that.
+template <int NW, int KT, bool USE_TR, bool DBGK, bool PRE, int NBUF = 3>
 __global__ __launch_bounds__(NW * 64, 3) void attn_kernel(AttnArgs p) {
   constexpr int KB = KT / 32;               // 32-key blocks per tile
   const int dbg = DBGK ? p.dbg : 0;
+  static_assert(NBUF == 3 || NBUF == 1, "the three-buffer ring, or one buffer for a single tile");
+  static_assert(NBUF * 2 * KT * 128 >= NW * 32 * 128, "the epilogue stages NW images of 32 rows in the K/V buffers");
 
-  __shared__ __attribute__((aligned(16))) char smem[3 * 2 * KT * 128];  // the K/V ring: [buf][K tile | V tile]
+  __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * KT * 128];  // the K/V ring: [buf][K tile | V tile]
   constexpr int BUF_BYTES = 2 * KT * 128;
   typedef AttnRing<KT, NW, BUF_BYTES, v_chunk_swz> Ring;
 
@@ -775,23 +780,28 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(AttnArgs p, int64_t r
 }
 
 
-template <int NW, int KT>
+template <int NW, int KT, int NBUF = 3>
 int launch(const AttnArgs& a, int64_t batch, hipStream_t s, bool use_tr, bool pre) {
   AttnArgs args = a;
   args.qblocks = (a.lq + 32 * NW - 1) / (32 * NW);
+  SEVA_REQUIRE(NBUF == 3 || a.lk <= KT, "attention: the one-buffer kernel takes one K/V tile (lk=%d > %d)", a.lk, KT);
   const int64_t nb = batch * a.heads * args.qblocks;
   if (int rc = attn_check_grid("attention", nb)) return rc;
   const dim3 grid((unsigned)nb), block(NW * 64);
   if (args.dbg && !pre)
-    hipLaunchKernelGGL((attn_kernel<NW, KT, true, true, false>), grid, block, 0, s, args);
+    hipLaunchKernelGGL((attn_kernel<NW, KT, true, true, false, NBUF>), grid, block, 0, s, args);
   else if (!use_tr)
-    hipLaunchKernelGGL((attn_kernel<NW, KT, false, false, false>), grid, block, 0, s, args);
+    hipLaunchKernelGGL((attn_kernel<NW, KT, false, false, false, NBUF>), grid, block, 0, s, args);
   else if (pre)
-    hipLaunchKernelGGL((attn_kernel<NW, KT, true, false, true>), grid, block, 0, s, args);
+    hipLaunchKernelGGL((attn_kernel<NW, KT, true, false, true, NBUF>), grid, block, 0, s, args);
   else
-    hipLaunchKernelGGL((attn_kernel<NW, KT, true, false, false>), grid, block, 0, s, args);
+    hipLaunchKernelGGL((attn_kernel<NW, KT, true, false, false, NBUF>), grid, block, 0, s, args);
   return seva_check_launch("attn_kernel");
 }
+
+// Whether 32 < lq <= 64, lk <= 64 takes the two-wave one-buffer kernel when knob attn_short2 is unset (the A/B: DESIGN.md §5,
+// profiles/long_window.log, tools/klong_window_time.py).
+constexpr bool kAttnShort2Default = false;
 
 }  // namespace
 
@@ -824,6 +834,12 @@ extern "C" int seva_attention_f16(const seva_attn_desc* d, seva_stream_t stream)
   const bool pre = d->q_prescaled != 0;
   SEVA_REQUIRE(!pre || use_tr, "attention: q_prescaled is not available on the SEVA_ATTN_NO_TR debug path");
   if (d->lq <= 32) return launch<1, 32>(a, batch, s, use_tr, pre);
+  // Short sequences past one wave (32 < lq <= 64, lk <= 64: the temporal regime of a 33..64-frame window): two waves, one K/V tile
+  // in ONE buffer.  attn_kernel<4, 64> gives such a launch four waves of which two own no query row, and 48 KiB of LDS for a ring
+  // that never turns.  Each of the two waves does what the same wave of attn_kernel<4, 64> does, on the same LDS image: equal bits
+  // (tests/test_long_window_gpu.py).  Knob attn_short2: 1 = this route, 0 = attn_kernel<4, 64>; unset = kAttnShort2Default.
+  if (d->lq <= 64 && d->lk <= 64 && (g_seva_knobs.attn_short2 < 0 ? kAttnShort2Default : g_seva_knobs.attn_short2 == 1))
+    return launch<2, 64, 1>(a, batch, s, use_tr, pre);
   // Long sequences (lq >= SEVA_ATTN_LONG_MIN_LQ): 64 queries per wave, K / V fragments shared by all its query blocks.  Default: attn16_kernel
   // (v_mfma_f32_16x16x32; -3 ... -7 % against attn2_kernel on the long shapes of a step, same-box, profiles/r04_kattn16.log).
   // Knob attn_two: 0 forces attn_kernel, 1 / 2 select attn2_kernel (v_mfma_f32_32x32x16, bitwise equal to attn_kernel) from

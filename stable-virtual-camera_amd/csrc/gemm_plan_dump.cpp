@@ -52,7 +52,7 @@ int main() {
     memset(&d, 0, sizeof d);
     SevaKnobs k;
     k.gemm_chunks = k.gemm_dbg = k.gemm_stagger = k.gemm_bm = k.gemm_bn = k.gemm_astat = -1;
-    k.attn_dbg = k.attn_no_tr = k.attn_two = k.attn_split = k.gn_min_iter = k.conv_win = -1;
+    k.attn_dbg = k.attn_no_tr = k.attn_two = k.attn_split = k.attn_short2 = k.gn_min_iter = k.conv_win = -1;
     Variant v = F16;
     bool any = false, bad = false;
     for (char* tok = strtok(line, " \t\r\n"); tok; tok = strtok(nullptr, " \t\r\n")) {

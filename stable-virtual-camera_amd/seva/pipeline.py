@@ -21,8 +21,15 @@ them per window (eval.py:1820-1829, 1246).  Here the default hand-off is the anc
 no decode -> encode round trip, 1.66 MB instead of 40 MB on the wire); `handoff="rgb"` reproduces the reference's
 round trip through `AutoEncoder.decode` / `.encode` when an `ae` is given.
 
+Window lengths: a sparse scene runs every window at T.  From nine input views on (`num_input_semi_dense`) the reference's
+`infer_prior_stats` gives each pass its own length (eval.py:344-421: the first pass is ONE window of all inputs + all anchors,
+`interp-gt` widens the second pass by the inputs it carries) and `run_one_scene` drives each pass with its own T, cfg and guider
+(eval.py:1654-1655, 1785-1789, 1929-1933); so do `plan_trajectory` (`TrajectoryPlan.T1` / `.T2`) and `run_trajectory`, whose `T`,
+`cfg` and `guider` take one value or a (first pass, second pass) pair.  A window is `len(win.slot_frame)` views long; nothing
+else in the driver reads a length.
+
 Randomness under sharding (SURVEY §8e last bullet; reference eval.py:1294-1295, 1450): the initial noise of window i is
-the i-th `torch.randn((T,4,h,w))` draw of ONE CPU stream seeded once per scene -- every rank draws the whole sequence
+the i-th `torch.randn((len(window),4,h,w))` draw of ONE CPU stream seeded once per scene -- every rank draws the whole sequence
 in plan order and keeps its own windows'.  The per-step device noise (`randn_like`, sampling.py:359) comes from a
 generator owned by the window (seed = scene seed, window index), so a window's result does not depend on which rank
 runs it or on what ran before it: a sharded run equals the sequential run bit for bit (tested on gloo, world size 2).
@@ -75,6 +82,12 @@ class TrajectoryPlan:
     pass1: list[Window]
     pass2: list[Window]
     pass1_serial: bool
+    T1: int | None = None         # window length of the first pass (None: `T`)
+    T2: int | None = None         # window length of the second pass (None: `T`)
+
+    def __post_init__(self):
+        self.T1 = self.T if self.T1 is None else int(self.T1)
+        self.T2 = self.T if self.T2 is None else int(self.T2)
 
 
 def _windows(pass_id, base, T, chunks, src_pool, tgt_pool, padding_mode="last"):
@@ -125,7 +138,15 @@ def plan_views(c2ws: torch.Tensor, input_ids: Sequence[int], T: int = 21, chunk_
     return TrajectoryPlan(T, ins, targets, w1, [], serial)
 
 
-def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int = 21, chunk_strategy: str = "interp",
+def _per_pass(v):
+    """A scalar or a (first pass, second pass) pair -> the pair (the reference's `--T N,21`, `cfg 3,2`; eval.py:1785-1789)."""
+    if isinstance(v, (list, tuple)):
+        assert len(v) == 2, f"one value or a (first pass, second pass) pair, not {v!r}"
+        return v[0], v[1]
+    return v, v
+
+
+def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int | Sequence[int] = 21, chunk_strategy: str = "interp",
                     first_pass_strategy: str = "gt-nearest", options: dict | None = None,
                     task: str = "img2trajvid", refine_anchors: bool = True) -> TrajectoryPlan:
     """Anchors + windows of both passes for one trajectory; frame ids index `c2ws` (inputs first, like the reference's
@@ -135,25 +156,31 @@ def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int = 21, c
     second pass targets EVERY non-input frame, so the anchors -- which the `interp` chunker places as the first target of
     the range they open -- are generated again in pass 2 and the trajectory's anchor frames are second-pass samples;
     golden: tests/golden/g10_two_pass_plans.json).  `refine_anchors=False` is this package's cheaper variant: the second
-    pass skips the anchors and their final latents are the first-pass samples (one target slot more per range)."""
+    pass skips the anchors and their final latents are the first-pass samples (one target slot more per range).
+
+    `T`: one window length or a pair (T1, T2).  From `num_input_semi_dense` (9) input views on, `infer_prior_stats` rewrites
+    the lengths as the reference does (eval.py:344-421): the first pass becomes ONE window of all inputs + all anchors, and
+    `interp-gt` widens the second pass by the input views it carries (golden: tests/golden/g15_semidense_plans.json).  The plan
+    records both (`T1`, `T2`); `T` is the first-pass length.  `options` carries `num_prior_frames_ratio`, `num_prior_frames`
+    and `num_input_semi_dense`."""
     n = c2ws.shape[0]
     ins = [int(i) for i in input_ids]
     opts = {"sampler_verbose": False, **(options or {}), "chunk_strategy": chunk_strategy}
+    T = [int(t) for t in T] if isinstance(T, (list, tuple)) else int(T)
     vd = {"T": T, "options": opts}
     n_prior = planner.infer_prior_stats(T, len(ins), n - len(ins), vd)
-    T1, T2 = vd["T"] if isinstance(vd["T"], (list, tuple)) else (T, T)
-    assert T1 == T2 == T, "different window lengths per pass are not driven by this pipeline"
+    T1, T2 = (int(t) for t in _per_pass(vd["T"]))
     anchors = [int(v) for v in planner.infer_prior_inds(c2ws, n_prior, ins, opts)]
-    w1, serial = _input_conditioned_windows(c2ws, ins, anchors, T, opts, task, first_pass_strategy)
+    w1, serial = _input_conditioned_windows(c2ws, ins, anchors, T1, opts, task, first_pass_strategy)
     order = np.argsort(ins + anchors).tolist()
     pool2 = [(ins + anchors)[o] for o in order]
     skip = set(ins) if refine_anchors else set(ins) | set(anchors)
     rest = [i for i in range(n) if i not in skip]
-    p2 = planner.chunk_input_and_test(T, c2ws[pool2], c2ws[rest], [float(i) for i in pool2], [float(r) for r in rest],
+    p2 = planner.chunk_input_and_test(T2, c2ws[pool2], c2ws[rest], [float(i) for i in pool2], [float(r) for r in rest],
                                       opts, task=task, chunk_strategy=chunk_strategy,
                                       gt_input_inds=[order.index(i) for i in range(len(ins))])
-    w2 = _windows(2, len(w1), T, p2, pool2, rest)
-    return TrajectoryPlan(T, ins, anchors, w1, w2, serial)
+    w2 = _windows(2, len(w1), T2, p2, pool2, rest)
+    return TrajectoryPlan(T1, ins, anchors, w1, w2, serial, T1, T2)
 
 
 def _rank_world(group=None):
@@ -246,8 +273,9 @@ def run_window(win: Window, latents_of: dict, denoise_net: Callable, c2ws, Ks, *
 
 def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: torch.Tensor, Ks: torch.Tensor,
                    input_ids: Sequence[int], *, clip_token: torch.Tensor | None = None, clip_fn: Callable | None = None,
-                   T: int = 21, num_steps: int = 50, cfg: float = 2.0, cfg_min: float = 1.2, guider: int = 1,
-                   camera_scale: float = 2.0, seed: int = 23, chunk_strategy: str = "interp",
+                   T: int | Sequence[int] = 21, num_steps: int = 50, cfg: float | Sequence[float] = 2.0, cfg_min: float = 1.2,
+                   guider: int | Sequence[int] = 1,
+                   camera_scale: float = 2.0, seed: int = 23, chunk_strategy: str = "interp", options: dict | None = None,
                    first_pass_strategy: str = "gt-nearest", refine_anchors: bool = True, device=None, group=None, ae=None,
                    handoff: str = "latent",
                    plan: TrajectoryPlan | None = None, timers: dict | None = None,
@@ -257,11 +285,16 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
     (`SGMWrapper(model)`); `input_latents` (n_in,4,h,w) are the VAE-encoded input views (x 0.18215), frame ids
     `input_ids` index `c2ws` (n,4,4) / `Ks` (n,3,3).  Returns, on rank 0, {"latents": (n,4,h,w) in frame order,
     "frame_ids", "plan", "anchor_latents" (first-pass anchors as pass 2 saw them), ["rgb"]}; other ranks get {"plan"} only.
-    `solver` goes to every window's sampler (`run_window`)."""
+    `solver` goes to every window's sampler (`run_window`).
+    `T`, `cfg` and `guider` each take one value or a (first pass, second pass) pair, as the reference's `--T 96,21` /
+    `cfg 3,2` do (eval.py:1785-1789, 1929-1933); `options` goes to the planner (`num_prior_frames_ratio`, ...).  A window
+    is as long as its pass of the plan says (`plan.T1` / `plan.T2`): its noise draw, its guider and its network call."""
     rank, world = _rank_world(group)
     device = torch.device(device) if device is not None else input_latents.device
     h, w = input_latents.shape[-2:]
-    plan = plan or plan_trajectory(c2ws, input_ids, T, chunk_strategy, first_pass_strategy, refine_anchors=refine_anchors)
+    plan = plan or plan_trajectory(c2ws, input_ids, T, chunk_strategy, first_pass_strategy, options,
+                                   refine_anchors=refine_anchors)
+    cfgs, guiders = _per_pass(cfg), _per_pass(guider)
     rgb_of: dict = {}
     if conditioner is not None:
         # the reference's rule (eval.py:1248): token of a window = mean CLIP embedding of its conditioning views' RGB
@@ -279,14 +312,13 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
     # initial noise: ONE CPU stream, seeded once per scene, drawn in plan order for EVERY window (eval.py:1294-1295,1450)
     g0 = torch.Generator(device="cpu")
     g0.manual_seed(int(seed))
-    n_win = len(plan.pass1) + len(plan.pass2)
-    noises = [torch.randn((plan.T, 4, h, w), generator=g0) for _ in range(n_win)]
+    noises =[torch.randn((len(win.slot_frame), 4, h, w), generator=g0) for win in plan.pass1 + plan.pass2]
 
     def step_seed(win):  # per-window device stream: independent of rank and of execution order
         return (int(seed) * 1000003 + 7919 * (win.global_index + 1)) & 0x7FFFFFFFFFFF
 
     latents_of = {fid: input_latents[i].to(device) for i, fid in enumerate(plan.input_ids)}
-    common = dict(hw=(h, w), num_steps=num_steps, cfg=cfg, cfg_min=cfg_min, guider=guider, camera_scale=camera_scale,
+    common = dict(hw=(h, w), num_steps=num_steps, cfg_min=cfg_min, camera_scale=camera_scale,
                   device=device, sampler_hook=sampler_hook, solver=solver)
 
     def mark(name):
@@ -324,7 +356,8 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
         win = plan.pass1[i]
         t_w = _now(device) if timers is not None else 0.0
         z = run_window(win, latents_of, denoise_net, c2ws, Ks, noise=noises[win.global_index], step_seed=step_seed(win),
-                       clip_token=tok(win.source_ids), cfg_split=(pairs[0], rank) if split1 else None, **common)
+                       clip_token=tok(win.source_ids), cfg_split=(pairs[0], rank) if split1 else None,
+                       cfg=cfgs[0], guider=guiders[0], **common)
         if timers is not None:
             timers.setdefault("windows", []).append((1, i, _now(device) - t_w))
         zt = handoff_latent(z[win.target_slots], win.target_ids)
@@ -370,7 +403,8 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
             t_w = _now(device) if timers is not None else 0.0
             outs[i] = run_window(win, latents_of, denoise_net, c2ws, Ks, noise=noises[win.global_index],
                                  step_seed=step_seed(win), clip_token=tok(win.source_ids),
-                                 cfg_split=(pairs[ranks[0] // 2], ranks.index(rank)) if len(ranks) == 2 else None, **common)
+                                 cfg_split=(pairs[ranks[0] // 2], ranks.index(rank)) if len(ranks) == 2 else None,
+                                 cfg=cfgs[1], guider=guiders[1], **common)
             if timers is not None:
                 timers.setdefault("windows", []).append((2, i, _now(device) - t_w))
     mark("pass2")
@@ -383,7 +417,7 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
             if mine is not None:
                 collected[sender[rank]] = mine
             continue
-        send = mine if mine is not None else torch.zeros((plan.T, 4, h, w), device=device)
+        send = mine if mine is not None else torch.zeros((plan.T2, 4, h, w), device=device)
         bufs = [torch.empty_like(send) for _ in range(world)] if rank == 0 else None
         dist.gather(send.contiguous(), bufs, dst=0, group=group)
         if rank == 0:
