@@ -260,6 +260,12 @@ class SevaEngine(_EngineBase):
         # per input signature, fed through static input buffers
         self.use_graph = env_flag("SEVA_HIPGRAPH", "not0", True)
         self._graphs: dict = {}
+        # shallow calls (`forward(shallow_levels=L)`): the signature of the last full call, and per signature what a full call
+        # left behind for each entry point L -- (tensor entering the first output block a shallow call runs, h, w, its statistics)
+        self._last_full: tuple | None = None
+        self._shallow_entries: dict = {}
+        # per depth L = 1, 2, ...: the input blocks after the stem that precede the L-th Downsample of the layout
+        self._shallow_m = tuple(i - 1 for i, blk in enumerate(self.layout.input_blocks) if blk[0].kind == "down")
         # frame-sliced execution of the token-wise chains at the largest level (see _slice_rows); 0 frames = off (default:
         # measured end-to-end it does not pay, see _slice_rows)
         self.slice_frames = env_int("SEVA_SLICE_FRAMES", 0)
@@ -781,15 +787,20 @@ class SevaEngine(_EngineBase):
 
     # ------------------------------------------------------------------ graph replay
     @torch.no_grad()
-    def forward_graphed(self, x, concat, t, y, dense_y, num_frames):
+    def forward_graphed(self, x, concat, t, y, dense_y, num_frames, shallow_levels=0):
         """Same result as `forward`, replayed from a hipGraph.  First call of a signature runs eagerly
         twice (arena warm-up, then capture on a side stream); later calls copy the inputs into the
-        static buffers and launch the instantiated graph: one launch instead of ~550."""
+        static buffers and launch the instantiated graph: one launch instead of ~550.  A shallow call has a graph of its
+        own per signature and depth, and passes the same guard as an eager one before every replay."""
         require_cuda(x, t, y, dense_y)
         if concat is not None and concat.numel() == 0:
             concat = None
-        key = (tuple(x.shape), None if concat is None else tuple(concat.shape), tuple(y.shape),
-               tuple(dense_y.shape), int(num_frames))
+        L = int(shallow_levels)
+        sig = self._signature(x, concat, y, dense_y, num_frames)
+        if L:
+            self._shallow_entry(L, sig)
+        key = sig + (L,)
+        fwd = lambda *a, **k: self.forward(*a, shallow_levels=L, **k)  # noqa: E731
         ent = self._graphs.get(key)
         if ent is None:
             # static input buffers: ordinary tensors even under torch.inference_mode() (reference eval.py:1242) -- an
@@ -804,14 +815,14 @@ class SevaEngine(_EngineBase):
                 }
                 out = torch.empty((x.shape[0], self.p.out_channels) + tuple(x.shape[2:]), dtype=F32, device=self.device)
             self._copy_inputs(st, x, concat, t, y, dense_y)
-            self.forward(st["x"], st["concat"], st["t"], st["y"], st["dense"], num_frames, out=out)  # warm the arena
+            fwd(st["x"], st["concat"], st["t"], st["y"], st["dense"], num_frames, out=out)  # warm the arena
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
             graph = ops.Graph()
             with torch.cuda.stream(side):
                 graph.capture_begin(self.device)
                 try:
-                    self.forward(st["x"], st["concat"], st["t"], st["y"], st["dense"], num_frames, out=out)
+                    fwd(st["x"], st["concat"], st["t"], st["y"], st["dense"], num_frames, out=out)
                 except BaseException:
                     # leave no stream stuck in capture mode: end + discard the partial graph, then run eagerly from now on
                     try:
@@ -826,7 +837,11 @@ class SevaEngine(_EngineBase):
             self._graphs[key] = ent
         graph, st, out = ent
         self._copy_inputs(st, x, concat, t, y, dense_y)
+        if not L:
+            self._last_full = None
         graph.launch(self.device)
+        if not L:  # the replay refilled the buffers that this signature's capture recorded as entry points
+            self._last_full = sig
         return out.clone()
 
     @staticmethod
@@ -842,15 +857,50 @@ class SevaEngine(_EngineBase):
     def __call__(self, x, concat, t, y, dense_y, num_frames):
         # inside a whole-step capture (seva/_stepgraph.py) or its warm-up the network is launched eagerly: its ~600
         # kernels become nodes of the step graph instead of a nested replay
+        L = _native.network_shallow_levels()  # (`_native.shallow_network`: the sampler's request for a shallow call)
         if self.use_graph and not _native.network_eager_forced() and not torch.cuda.is_current_stream_capturing():
-            return self.forward_graphed(x, concat, t, y, dense_y, num_frames)
-        return self.forward(x, concat, t, y, dense_y, num_frames)
+            return self.forward_graphed(x, concat, t, y, dense_y, num_frames, shallow_levels=L)
+        return self.forward(x, concat, t, y, dense_y, num_frames, shallow_levels=L)
+
+    # ------------------------------------------------------------------ shallow calls
+    @staticmethod
+    def _signature(x, concat, y, dense_y, num_frames) -> tuple:
+        """What two calls must share for one to reuse the other's buffers (also the key of `forward_graphed`'s graphs)."""
+        return (tuple(x.shape), None if concat is None or concat.numel() == 0 else tuple(concat.shape), tuple(y.shape),
+                tuple(dense_y.shape), int(num_frames))
+
+    def shallow_input_blocks(self, levels: int) -> int:
+        """m: a shallow call of depth `levels` runs the m input blocks after the stem that precede the `levels`-th Downsample of
+        the layout, and the last m + 1 output blocks (2 / 5 / 8 for the 1.3 B architecture)."""
+        if not 1 <= levels <= len(self._shallow_m):
+            raise ValueError(f"shallow_levels must be 0 (a full call) or 1..{len(self._shallow_m)}, got {levels!r}")
+        return self._shallow_m[levels - 1]
+
+    def _shallow_entry(self, levels: int, sig: tuple):
+        """The guard of a shallow call: (tensor, h, w, statistics) that the last full call left for depth `levels`, or
+        SevaNativeError when that call was not one of this signature -- never a buffer the engine cannot vouch for."""
+        self.shallow_input_blocks(levels)
+        last = self._last_full
+        if last is None:
+            raise SevaNativeError(
+                f"shallow network call (shallow_levels={levels}): this engine has made no full call to reuse (an engine built anew, "
+                "as after set_precision or a weight reload, starts without one, and so does one whose last full call failed)")
+        if last != sig:
+            names = ("x", "concat", "y", "dense_y", "num_frames")
+            diff = ", ".join(f"{k} {a} -> {b}" for k, a, b in zip(names, last, sig) if a != b)
+            raise SevaNativeError(f"shallow network call (shallow_levels={levels}): the last full call had another signature ({diff})")
+        return self._shallow_entries[sig][levels]
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
-    def forward(self, x, concat, t, y, dense_y, num_frames, out=None):
+    def forward(self, x, concat, t, y, dense_y, num_frames, out=None, shallow_levels=0):
         """x: [n, c, h, w] f32 (‖ concat on channels), t: [n] int64 sigma indices, y: [n, L, ctx],
-        dense_y: [n, 6, hd, wd].  Returns [n, out_channels, h, w] f32."""
+        dense_y: [n, 6, hd, wd].  Returns [n, out_channels, h, w] f32.
+
+        shallow_levels = L in 1..3 (opt-in; DESIGN.md section 5, "Reuse of deep features"): run only the prologue, the stem, the
+        input blocks above the L-th Downsample, the matching last output blocks and the head; what enters the first of those
+        output blocks is the tensor (and its GroupNorm statistics) that the most recent full call of the same signature left
+        in the arena.  Without such a call: SevaNativeError (`_shallow_entry`), never a silent full call."""
         require_cuda(x, t, y, dense_y)
         W, p, lay = self.W, self.p, self.layout
         x = x.to(F32).contiguous()
@@ -866,6 +916,15 @@ class SevaEngine(_EngineBase):
         assert y.ndim == 3
         lc = y.shape[1]
         t = t.to(torch.int64).contiguous()
+        L = int(shallow_levels)
+        sig = self._signature(x, concat, y, dense_y, T)
+        if L:
+            entry = self._shallow_entry(L, sig)
+            m_in = self.shallow_input_blocks(L)
+        else:
+            self._last_full = None  # (until this call has run to its end)
+            entries: dict = {}
+            enters = {m + 1: k + 1 for k, m in enumerate(self._shallow_m)}  # output blocks left to run -> the depth that enters there
         self.gn_ws = self._buf("gn_ws", (n * ops.GN_WORKSPACE_SLABS * 32 * 2,), F32)
         self._stats = {}
 
@@ -927,14 +986,22 @@ class SevaEngine(_EngineBase):
                     cur, ch, cw = self._resample(spec, cur, n, ch, cw)
             return cur, ch, cw
 
-        for block in lay.input_blocks[1:]:
+        nout = len(lay.output_blocks)
+        for block in lay.input_blocks[1:1 + m_in] if L else lay.input_blocks[1:]:
             cur, ch, cw = run(block, cur, None, ch, cw)
             hs.append((cur, ch, cw))
-        cur, ch, cw = run(lay.middle, cur, None, ch, cw)
-        for block in lay.output_blocks:
+        if L:
+            cur, ch, cw, st_in = entry
+            self._produced(cur, st_in)  # (`_stats` was cleared above: the producer's statistics travel with the reused tensor)
+        else:
+            cur, ch, cw = run(lay.middle, cur, None, ch, cw)
+        for k in range(nout - (m_in + 1) if L else 0, nout):
+            if not L and nout - k in enters:
+                entries[enters[nout - k]] = (cur, ch, cw, self._stats.get(cur.data_ptr()))
             skip, sh, sw = hs.pop()
             assert (sh, sw) == (ch, cw)
-            cur, ch, cw = run(block, cur, skip, ch, cw)
+            cur, ch, cw = run(lay.output_blocks[k], cur, skip, ch, cw)
+        assert not hs
 
         # --- head: GroupNorm + SiLU + conv3x3 (model.py:170-174) ---
         audit_mark("out")
@@ -949,4 +1016,7 @@ class SevaEngine(_EngineBase):
         if out is None:
             out = torch.empty((n, p.out_channels, ch, cw), dtype=F32, device=self.device)
         ops.nhwc_to_nchw_f32(o_nhwc, out)
+        if not L:
+            self._shallow_entries[sig] = entries
+            self._last_full = sig
         return out

@@ -203,6 +203,29 @@ def network_eager_forced() -> bool:
     return _EAGER_DEPTH > 0
 
 
+# innermost request for a shallow network call (`SevaEngine.forward(shallow_levels=...)`): the sampler's denoiser is an opaque
+# callable, so the request reaches `SevaEngine.__call__` the way `eager_network` does.  A denoiser that is no SevaEngine ignores it.
+_SHALLOW_LEVELS: list = []
+
+
+class shallow_network:
+    def __init__(self, levels: int):
+        self.levels = int(levels)
+        if self.levels < 0:
+            raise ValueError(f"shallow_network: levels must be >= 0, got {levels!r}")
+
+    def __enter__(self):
+        _SHALLOW_LEVELS.append(self.levels)
+
+    def __exit__(self, *exc):
+        _SHALLOW_LEVELS.pop()
+        return False
+
+
+def network_shallow_levels() -> int:
+    return _SHALLOW_LEVELS[-1] if _SHALLOW_LEVELS else 0
+
+
 def load() -> C.CDLL:
     """Load libseva_hip.so and bind every symbol; raises SevaNativeError on any problem."""
     global _lib

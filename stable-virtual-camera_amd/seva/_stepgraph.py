@@ -64,21 +64,36 @@ class StepGraph:
         return self.static_out
 
 
+class _Entry:
+    """One key's place in the protocol: 0 = never seen, 1 = warmed; its graph once captured, and what that graph reads by address."""
+
+    __slots__ = ("key", "state", "graph", "keep")
+
+    def __init__(self):
+        self.key, self.state, self.graph, self.keep = None, 0, None, None
+
+
 class StepGraphCache:
-    """One live graph per sampler: keyed by the identity of everything the captured step closes over.
+    """One live graph per sampler and step kind: keyed by the identity of everything the captured step closes over.
 
     The key holds STRONG references (identity can then never be recycled by the allocator); a miss drops the old
     graph.  `state` per key: 0 = never seen -> run eagerly (warm-up: fills the engine arena, the guider's rule
     cache and every lazily packed weight; its result is the real step result), 1 = warmed -> capture + replay.
+
+    The step kind (`run(..., kind=)`: 0 = a full step, L = a step whose network call is shallow at depth L) is part of the
+    key, and each kind has an entry of its own: a sampler that alternates full and shallow steps keeps both graphs alive,
+    at most two per window shape.  `key` / `state` / `graph` / `keep` name the full step's entry.
     """
 
     def __init__(self):
-        self.key = None
-        self.state = 0
-        self.graph: StepGraph | None = None
-        self.keep = None  # tensors of the warm-up step that the captured graph reads by address
+        self.entries: dict = {0: _Entry()}
         self.disabled = False
         self.captures = 0
+
+    key = property(lambda self: self.entries[0].key)
+    state = property(lambda self: self.entries[0].state)
+    graph = property(lambda self: self.entries[0].graph)
+    keep = property(lambda self: self.entries[0].keep)  # tensors of the warm-up step that the captured graph reads by address
 
     @staticmethod
     def flat_key(obj) -> tuple:
@@ -108,35 +123,36 @@ class StepGraphCache:
                 return False
         return True
 
-    def lookup(self, key):
-        if self.key is None or not self._same(self.key, key):
-            self.key, self.state, self.graph, self.keep = key, 0, None, None
-        return self
+    def lookup(self, key, kind: int = 0) -> _Entry:
+        ent = self.entries.setdefault(kind, _Entry())
+        if ent.key is None or not self._same(ent.key, key):
+            ent.key, ent.state, ent.graph, ent.keep = key, 0, None, None
+        return ent
 
     def reset(self):
-        self.key, self.state, self.graph, self.keep = None, 0, None, None
+        self.entries = {0: _Entry()}
 
-    def run(self, key, fn, inputs, *, eligible, keep=None):
+    def run(self, key, fn, inputs, *, eligible, keep=None, kind: int = 0):
         """One step `fn(*inputs)` under the protocol: eager while not `eligible`; else the first step of `key` eagerly, the
         second captured and replayed, every later one replayed.  `fn` is the sync-free step math, `inputs` the tensors whose
         values are refreshed per replay; `keep()`, read after a capture succeeded, is what the graph reads by address and the
-        cache therefore holds for as long as the graph lives."""
+        cache therefore holds for as long as the graph lives.  `kind`: the step kind, whose entry `key` is looked up in."""
         if not eligible:
             return fn(*inputs)
-        self.lookup(key)
-        if self.state == 0:
+        ent = self.lookup(key, kind)
+        if ent.state == 0:
             # warm-up = the real first step, launched eagerly (also without the network-only graph: it would be
             # captured for this one call only)
             with _native.eager_network():
                 out = fn(*inputs)
-            self.state = 1
+            ent.state = 1
             return out
-        if self.graph is None:
+        if ent.graph is None:
             try:
                 # capture records the step without running it: what `fn` updates in place is updated by the replays alone
-                self.graph = StepGraph(fn, inputs)
+                ent.graph = StepGraph(fn, inputs)
                 self.captures += 1
-                self.keep = keep() if keep is not None else None
+                ent.keep = keep() if keep is not None else None
             except Exception as e:  # a step that cannot be captured (foreign denoiser with host syncs, ...) runs eagerly
                 self.disabled = True
                 self.reset()
@@ -148,4 +164,4 @@ class StepGraphCache:
                               "falling back to eager steps", RuntimeWarning)
                 return fn(*inputs)
         # the graph's output buffer is overwritten by the next replay: hand the caller its own copy (435 KB)
-        return self.graph(*inputs).clone()
+        return ent.graph(*inputs).clone()

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 from tqdm import tqdm
 
-from . import _stepgraph, audit, ops
+from . import _native, _stepgraph, audit, ops
 from ._native import SevaNativeError
 
 
@@ -342,17 +342,48 @@ class MultiviewTemporalCFG(MultiviewCFG):
 SOLVERS = ("euler", "dpmpp2m")
 
 
+def parse_cache(interval, levels) -> tuple:
+    """(interval, levels) of the deep-feature reuse from arguments or environment strings: interval None / "" / 0 / 1 = off
+    (returned as 0), N >= 2 = on; levels 1, 2 or 3 (None / "": 1).  Anything else is a ValueError."""
+    def as_int(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, str)):
+            raise ValueError(f"{what} must be an integer, got {v!r}")
+        try:
+            return int(v)
+        except ValueError:
+            raise ValueError(f"{what} must be an integer, got {v!r}") from None
+
+    n = 0 if interval is None or interval == "" else as_int(interval, "cache_interval")
+    lv = 1 if levels is None or levels == "" else as_int(levels, "cache_levels")
+    if n < 0:
+        raise ValueError(f"cache_interval must be 0 or 1 (off) or >= 2, got {interval!r}")
+    if lv not in (1, 2, 3):
+        raise ValueError(f"cache_levels must be 1, 2 or 3, got {levels!r}")
+    return (n if n >= 2 else 0), lv
+
+
 class EulerEDMSampler(object):
     """Reference sampling.py:301-405 (Euler discretisation of the EDM probability-flow ODE).
 
     `solver` (opt-in, not in the reference): "euler" = the reference's step; "dpmpp2m" = DPM-Solver++(2M), the
     deterministic second-order multistep solver (`DPMPP2MSampler` of sgm), same one network call per step.  None reads
     the environment variable SEVA_SOLVER (default "euler"), so code that constructs or subclasses this class by name can
-    opt in unchanged; an explicit argument wins over the variable."""
+    opt in unchanged; an explicit argument wins over the variable.
+
+    `cache_interval` = N >= 2 (opt-in, not in the reference): reuse of deep UNet features across steps.  Step i of a trajectory
+    runs the whole network iff i % N == 0 or it is the last step; every other step runs a shallow network call of depth
+    `cache_levels` (1, 2 or 3: `SevaEngine.forward(shallow_levels=...)`), which recomputes the top of the UNet and takes the rest
+    from the last full step.  0 or 1: off.  None reads SEVA_CACHE_INTERVAL and SEVA_CACHE_LEVELS (unset: off, depth 1).  The
+    schedule lives in `__call__`: a subclass that drives `sampler_step` itself gets full steps."""
 
     def __init__(self, discretization: DDPMDiscretization, guider, num_steps: int | None = None,
                  verbose: bool = False, device: str | torch.device = "cuda", s_churn=0.0, s_tmin=0.0,
-                 s_tmax=float("inf"), s_noise=1.0, solver: str | None = None, check_finite: bool | None = None):
+                 s_tmax=float("inf"), s_noise=1.0, solver: str | None = None, check_finite: bool | None = None,
+                 cache_interval: int | None = None, cache_levels: int | None = 1):
+        if cache_interval is None:  # both from the environment (the depth: the argument where the variable is unset)
+            cache_interval = os.environ.get("SEVA_CACHE_INTERVAL")
+            cache_levels = os.environ.get("SEVA_CACHE_LEVELS") or cache_levels
+        self.cache_interval, self.cache_levels = parse_cache(cache_interval, cache_levels)
         if solver is None:
             solver = os.environ.get("SEVA_SOLVER") or "euler"
         if solver not in SOLVERS:
@@ -418,14 +449,14 @@ class EulerEDMSampler(object):
             sigma_generator = tqdm(sigma_generator, total=num_sigmas - 1, desc="Sampling", leave=False)
         return sigma_generator
 
-    def _step_math(self, sigma, next_sigma, x, eps, denoiser, scale, cond, uc, gamma, guider_kwargs):
+    def _step_math(self, sigma, next_sigma, x, eps, denoiser, scale, cond, uc, gamma, guider_kwargs, shallow=0):
         """Reference sampling.py:357-368 on f32 contiguous device tensors; sync-free once the guider's rule is cached,
         which is what makes it capturable as one hipGraph (`_stepgraph.StepGraph`)."""
         sigma_hat = sigma * (gamma + 1.0) + 1e-6
         noise_scale = (sigma_hat**2 - sigma**2) ** 0.5 * self.s_noise
         x_noised = torch.empty_like(x)
         ops.add_noise(x, eps, _f32c(noise_scale), x_noised)
-        denoised2 = self._denoised_pair(denoiser, x_noised, sigma_hat, cond, uc)
+        denoised2 = self._denoised_pair(denoiser, x_noised, sigma_hat, cond, uc, shallow)
         dt = next_sigma - sigma_hat
         out = torch.empty_like(x)
         den, fs = self._guidance_operands(denoised2, sigma_hat, scale, x, guider_kwargs)
@@ -435,9 +466,13 @@ class EulerEDMSampler(object):
             ops.euler_step(x_noised, den, sigma_hat, dt, out)
         return out
 
-    def _denoised_pair(self, denoiser, x_in, sigma_in, cond, uc):
+    def _denoised_pair(self, denoiser, x_in, sigma_in, cond, uc, shallow=0):
         """The [uncond ; cond] denoised latents for (x_in, sigma_in): one CFG-batched network call, or under `cfg_split`
-        this rank's half of it and the other rank's."""
+        this rank's half of it and the other rank's.  `shallow` = L > 0: the network call runs inside
+        `_native.shallow_network(L)` (under `cfg_split` on either rank: each owns an engine, both follow one schedule)."""
+        if shallow:
+            with _native.shallow_network(shallow):
+                return self._denoised_pair(denoiser, x_in, sigma_in, cond, uc)
         if self.cfg_split is None:
             return denoiser(*self.guider.prepare_inputs(x_in, sigma_in, cond, uc))
         return self._denoise_cfg_split(denoiser, x_in, sigma_in, cond, uc)
@@ -490,12 +525,12 @@ class EulerEDMSampler(object):
         c = torch.where(second, -one_a * inv_2r, zero)
         return a, b, c
 
-    def _multistep_math(self, sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs):
+    def _multistep_math(self, sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs, shallow=0):
         """One DPM-Solver++(2M) step on f32 contiguous device tensors: no noise, no sigma_hat; guidance, update and the new
         history in ONE kernel (`ops.cfg_multistep`), which reads D- from `hist` and leaves D there.  Sync-free like
         `_step_math`, and the same code for the first, the second-order and the last step (they differ in a, b, c only), so
         one hipGraph serves them all."""
-        denoised2 = self._denoised_pair(denoiser, x, sigma, cond, uc)
+        denoised2 = self._denoised_pair(denoiser, x, sigma, cond, uc, shallow)
         a, b, c = self.multistep_coefficients(sigma, next_sigma, prev_sigma)
         out = torch.empty_like(x)
         den, fs = self._guidance_operands(denoised2, sigma, scale, x, guider_kwargs)
@@ -521,10 +556,12 @@ class EulerEDMSampler(object):
                 and ops._AUDIT is None and not torch.cuda.is_current_stream_capturing())
 
     def sampler_step(self, sigma: torch.Tensor, next_sigma: torch.Tensor, denoiser, x: torch.Tensor,
-                     scale, cond: dict, uc: dict, gamma: float = 0.0, **guider_kwargs) -> torch.Tensor:
+                     scale, cond: dict, uc: dict, gamma: float = 0.0, *, shallow: int = 0, **guider_kwargs) -> torch.Tensor:
         """One Euler-EDM step (reference sampling.py:347-368), or one DPM-Solver++(2M) step under solver="dpmpp2m".  From
         the second step of a trajectory on, the whole step is replayed from one hipGraph (see `_stepgraph`); the first step
-        runs eagerly and warms every cache.  Stays a callable unit for `GradioTrackedSampler` (reference eval.py:1037-1089)."""
+        runs eagerly and warms every cache.  Stays a callable unit for `GradioTrackedSampler` (reference eval.py:1037-1089).
+        `shallow` = L > 0 (`__call__`'s `cache_interval` schedule): the step's network call is a shallow one of depth L; such
+        steps have a whole-step graph of their own."""
         _need_gpu(x)
         x = _f32c(x)
         sigma = _f32c(sigma)
@@ -535,15 +572,15 @@ class EulerEDMSampler(object):
         if multistep:  # deterministic: no noise draw, no add_noise; `gamma` has nothing to act on
             hist, fourth = self._multistep_history(x, sigma)
             key = ("dpmpp2m", tuple(x.shape), hist, self.guider, denoiser) + flat
-            fn = lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, denoiser, scale, cond, uc, guider_kwargs)  # noqa: E731
+            fn = lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, denoiser, scale, cond, uc, guider_kwargs, shallow)  # noqa: E731
         else:
             fourth = _f32c(self.noise_fn(x))  # eps, drawn eagerly: the generator advances per step exactly as in the reference
             gamma = float(gamma)
             key = (tuple(x.shape), gamma, float(self.s_noise), self.guider, denoiser) + flat
-            fn = lambda s, n, xx, ee: self._step_math(s, n, xx, ee, denoiser, scale, cond, uc, gamma, guider_kwargs)  # noqa: E731
+            fn = lambda s, n, xx, ee: self._step_math(s, n, xx, ee, denoiser, scale, cond, uc, gamma, guider_kwargs, shallow)  # noqa: E731
         # keep: the graph reads the warm-up step's rule tensor, which must therefore outlive `reset_rule_cache`
         out = self._step_graphs.run(key, fn, (sigma, next_sigma, x, fourth), eligible=self._whole_step_graph_eligible(x),
-                                    keep=lambda: getattr(self.guider, "_rule_cache", None))
+                                    keep=lambda: getattr(self.guider, "_rule_cache", None), **({"kind": shallow} if shallow else {}))
         if multistep:
             self._ms_sigma, self._ms_have = sigma, True
         return out
@@ -552,14 +589,18 @@ class EulerEDMSampler(object):
                  num_steps: int | None = None, verbose: bool = True, **guider_kwargs) -> torch.Tensor:
         uc = cond if uc is None else uc
         x, s_in, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x, cond, uc, num_steps)
+        every, last = self.cache_interval, num_sigmas - 2
         for i in self.get_sigma_gen(num_sigmas, verbose=verbose):
             gamma = (
                 min(self.s_churn / (num_sigmas - 1), 2**0.5 - 1)
                 if self.s_tmin <= self._sigmas_host[i] <= self.s_tmax
                 else 0.0
             )
+            # deep-feature reuse: a full step at every `every`-th step and at the last one, shallow steps in between
+            # (the keyword is passed on shallow steps only: with the mode off the calls are the ones made before)
+            kind = {} if not every or i % every == 0 or i == last else {"shallow": self.cache_levels}
             x = self.sampler_step(s_in * sigmas[i], s_in * sigmas[i + 1], denoiser, x, scale, cond, uc,
-                                  gamma, **guider_kwargs)
+                                  gamma, **kind, **guider_kwargs)
         # once per trajectory, after the last step (never inside the loop): a split-K consumer that gave up waiting for its
         # producer (csrc/gemm.hip) left a wrong tile behind -- make that an error instead of a silently wrong sample
         if x.is_cuda:
