@@ -417,6 +417,21 @@ int seva_cfg_multistep_f32(const float* x, const float* den, const float* scale,
  *   out = u + scale[n]*(c - u), den2 = [2n][chw] with the uncond half first. */
 int seva_cfg_combine_f32(const float* den2, const float* scale, float* out, int32_t n, int64_t chw,
                          seva_stream_t stream);
+/* Rescaled guidance (Lin et al. 2024, `guidance_rescale` of diffusers; `EulerEDMSampler(guidance_rescale=phi)`): the guided
+ * prediction of each frame scaled towards the standard deviation of that frame's conditional prediction.
+ * `den2` = [2n][chw] with the uncond half first and `scale` = [n], as seva_cfg_combine_f32 takes them.  Per frame f, N = chw:
+ *   g_i  = u_i + scale[f]*(c_i - u_i)          the very device function of seva_cfg_combine_f32: phi == 0 gives its bits
+ *   S1c = sum c_i, S2c = sum c_i^2, S1g = sum g_i, S2g = sum g_i^2      in fp64, no atomics: thread t of the frame's one
+ *          256-thread workgroup adds elements t, t + 256, ... in that order, then the fixed tree of csrc/frame_common.h.
+ *          The order depends on chw alone -- not on n, on the frame's position in the batch, or on anything else in the launch
+ *   var_c = S2c - S1c^2/N,  var_g = S2g - S1g^2/N                        fp64 (a ratio of the two: no N vs N - 1 convention)
+ *   m    = phi > 0 && var_g > 0 && var_c >= 0 ? phi*sqrt(var_c/var_g) + (1 - phi) : 1      a select: N = 1, phi == 0, and a
+ *          constant frame whose sums are exact in fp64 (var == 0) give exactly 1; so does a NaN variance
+ *   m32  = (float)m, rounded once;  out_i = m32 * g_i, one fp32 multiply;  mult_out[f] = m32 where mult_out != NULL
+ * Non-finite inputs propagate through g.  `out` may not alias `den2`.  phi outside [0, 1] (NaN included), a NULL or
+ * misaligned pointer, n <= 0 or chw <= 0: SEVA_ERR_ARG. */
+int seva_cfg_rescale_f32(const float* den2, const float* scale, float phi, float* out, float* mult_out, int32_t n,
+                         int64_t chw, seva_stream_t stream);
 /* Euler step alone (to_d + update, sampling.py:24-25,366-368): out = x + dt[n]*(x - den)/sigma[n]. */
 int seva_euler_step_f32(const float* x, const float* den, const float* sigma_hat, const float* dt,
                         float* out, int32_t n, int64_t chw, seva_stream_t stream);

@@ -1,6 +1,7 @@
 // Layout changes and small elementwise kernels (HBM- or launch-bound; everything vectorised where
 // the layout allows).  See include/seva_hip.h for the reference lines each one replaces.
 #include "seva_common.h"
+#include "frame_common.h"  // block_tree: the fixed-order workgroup reduction (cfg_rescale_kernel)
 
 namespace {
 
@@ -225,14 +226,54 @@ __global__ void cfg_multistep_kernel(const float* x, const float* __restrict__ d
   }
 }
 
+// THE guided value of cfg_combine_kernel and cfg_rescale_kernel: u + s*(c - u) as one subtraction and one FMA (what
+// -ffp-contract=fast made of the expression before this helper existed), spelled out so that both kernels round alike
+__device__ __forceinline__ float cfg_guided(float u, float c, float s) { return __fmaf_rn(s, c - u, u); }
+
 __global__ void cfg_combine_kernel(const float* __restrict__ den2, const float* __restrict__ scale,
                                    float* __restrict__ out, int n, int64_t chw) {
   const int64_t total = (int64_t)n * chw;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
     const float u = den2[i], c = den2[total + i];
-    out[i] = u + scale[i / chw] * (c - u);
+    out[i] = cfg_guided(u, c, scale[i / chw]);
   }
+}
+
+// Rescaled guidance (include/seva_hip.h: seva_cfg_rescale_f32).  ONE workgroup of EW_THREADS per frame, so a frame's bits depend on
+// its own chw elements alone: thread t adds elements t, t + 256, ... in that order into four fp64 sums, the fixed tree of
+// frame_common.h folds the 256 partials, every thread derives the same multiplier from the tree's result, and a second pass (the
+// frame's 2 x chw floats come from L2) writes m32 * g.  No atomics, no workspace; g is computed by cfg_guided() in both passes.
+struct Sums4 { double s1c, s2c, s1g, s2g; };
+
+__global__ void __launch_bounds__(EW_THREADS)
+cfg_rescale_kernel(const float* __restrict__ den2, const float* __restrict__ scale, float phi,
+                   float* __restrict__ out, float* __restrict__ mult_out, int n, int64_t chw) {
+  __shared__ Sums4 red[EW_THREADS];
+  const int f = blockIdx.x;
+  const float* __restrict__ u = den2 + (int64_t)f * chw;
+  const float* __restrict__ c = u + (int64_t)n * chw;
+  float* __restrict__ o = out + (int64_t)f * chw;
+  const float s = scale[f];
+  Sums4 acc = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t i = threadIdx.x; i < chw; i += EW_THREADS) {
+    const float cv = c[i];
+    const double cd = (double)cv, gd = (double)cfg_guided(u[i], cv, s);
+    acc.s1c += cd;
+    acc.s2c += cd * cd;  // (exact products of two fp32 values: contraction cannot change these sums)
+    acc.s1g += gd;
+    acc.s2g += gd * gd;
+  }
+  const Sums4 t = block_tree<EW_THREADS>(acc, red, [](Sums4 a, Sums4 b) {
+    return Sums4{a.s1c + b.s1c, a.s2c + b.s2c, a.s1g + b.s1g, a.s2g + b.s2g};
+  });
+  const double N = (double)chw;
+  const double var_c = t.s2c - t.s1c * t.s1c / N, var_g = t.s2g - t.s1g * t.s1g / N;
+  double m = 1.0;  // a select: a NaN in either variance compares false and leaves 1
+  if (phi > 0.f && var_g > 0.0 && var_c >= 0.0) m = (double)phi * sqrt(var_c / var_g) + (1.0 - (double)phi);
+  const float m32 = (float)m;
+  if (mult_out && threadIdx.x == 0) mult_out[f] = m32;
+  for (int64_t i = threadIdx.x; i < chw; i += EW_THREADS) o[i] = m32 * cfg_guided(u[i], c[i], s);
 }
 
 __global__ void euler_step_kernel(const float* __restrict__ x, const float* __restrict__ den,
@@ -443,6 +484,17 @@ extern "C" int seva_cfg_combine_f32(const float* den2, const float* scale, float
   SEVA_REQUIRE(den2 && scale && out && n > 0 && chw > 0, "cfg_combine: bad args");
   SevaProfScope prof(4, (double)n * chw * 12.0, (hipStream_t)stream);
   EW_LAUNCH(cfg_combine_kernel, (int64_t)n * chw, den2, scale, out, n, chw);
+}
+
+extern "C" int seva_cfg_rescale_f32(const float* den2, const float* scale, float phi, float* out,
+                                    float* mult_out, int32_t n, int64_t chw, seva_stream_t stream) {
+  SEVA_REQUIRE(den2 && scale && out && n > 0 && chw > 0, "cfg_rescale: bad args");
+  SEVA_REQUIRE(phi >= 0.f && phi <= 1.f, "cfg_rescale: phi=%g outside [0, 1]", (double)phi);  // (a NaN fails both comparisons)
+  SEVA_REQUIRE((((uintptr_t)den2 | (uintptr_t)scale | (uintptr_t)out | (uintptr_t)mult_out) & 3) == 0, "cfg_rescale: unaligned");
+  hipStream_t s_ = (hipStream_t)stream;
+  SevaProfScope prof(4, (double)n * chw * 12.0, s_);  // HBM bytes: the second read of u and c comes from L2
+  hipLaunchKernelGGL(cfg_rescale_kernel, dim3((unsigned)n), dim3(EW_THREADS), 0, s_, den2, scale, phi, out, mult_out, (int)n, chw);
+  return seva_check_launch("cfg_rescale_kernel");
 }
 
 extern "C" int seva_euler_step_f32(const float* x, const float* den, const float* sigma_hat,

@@ -155,6 +155,7 @@ SYMBOLS = {
     "seva_cfg_multistep_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int32, c_int64, c_void_p]),
     "seva_cfg_combine_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
+    "seva_cfg_rescale_f32": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
     "seva_euler_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
     "seva_to_d_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
     "seva_scale_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),

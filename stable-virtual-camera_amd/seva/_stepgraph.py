@@ -80,9 +80,10 @@ class StepGraphCache:
     graph.  `state` per key: 0 = never seen -> run eagerly (warm-up: fills the engine arena, the guider's rule
     cache and every lazily packed weight; its result is the real step result), 1 = warmed -> capture + replay.
 
-    The step kind (`run(..., kind=)`: 0 = a full step, L = a step whose network call is shallow at depth L) is part of the
-    key, and each kind has an entry of its own: a sampler that alternates full and shallow steps keeps both graphs alive,
-    at most two per window shape.  `key` / `state` / `graph` / `keep` name the full step's entry.
+    The step kind (`run(..., kind=)`: 0 = a full step, L = a step whose network call is shallow at depth L, (0 or L, "unguided") =
+    the same without guidance; any hashable value) is part of the key, and each kind has an entry of its own: a sampler that
+    alternates full and shallow steps keeps both graphs alive, one that also leaves a guidance interval all four, at most four
+    per window shape.  `key` / `state` / `graph` / `keep` name the full guided step's entry.
     """
 
     def __init__(self):
@@ -123,7 +124,7 @@ class StepGraphCache:
                 return False
         return True
 
-    def lookup(self, key, kind: int = 0) -> _Entry:
+    def lookup(self, key, kind=0) -> _Entry:
         ent = self.entries.setdefault(kind, _Entry())
         if ent.key is None or not self._same(ent.key, key):
             ent.key, ent.state, ent.graph, ent.keep = key, 0, None, None
@@ -132,7 +133,7 @@ class StepGraphCache:
     def reset(self):
         self.entries = {0: _Entry()}
 
-    def run(self, key, fn, inputs, *, eligible, keep=None, kind: int = 0):
+    def run(self, key, fn, inputs, *, eligible, keep=None, kind=0):
         """One step `fn(*inputs)` under the protocol: eager while not `eligible`; else the first step of `key` eagerly, the
         second captured and replayed, every later one replayed.  `fn` is the sync-free step math, `inputs` the tensors whose
         values are refreshed per replay; `keep()`, read after a capture succeeded, is what the graph reads by address and the

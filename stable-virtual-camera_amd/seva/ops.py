@@ -972,6 +972,27 @@ def cfg_combine(den2: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> N
 
 
 @_audited("out")
+def cfg_rescale(den2: torch.Tensor, scale: torch.Tensor, phi: float, out: torch.Tensor,
+                mult_out: torch.Tensor | None = None) -> None:
+    """Rescaled guidance (seva_cfg_rescale_f32): out[f] = m[f] * g[f] with g = u + scale[f]*(c - u) exactly as `cfg_combine`
+    computes it from `den2` = [uncond ; cond], and m[f] = phi * std(c[f]) / std(g[f]) + (1 - phi) from fp64 sums in a fixed order
+    (1 where phi == 0 or std(g[f]) == 0).  `mult_out` (n,) receives m.  `out` may not alias `den2`."""
+    require_cuda(den2, scale, out, mult_out)
+    n = out.shape[0]
+    for name, t in (("den2", den2), ("scale", scale), ("out", out), ("mult_out", mult_out)):
+        if t is not None and (t.dtype != F32 or not t.is_contiguous()):
+            raise nv.SevaNativeError(f"cfg_rescale: {name} must be contiguous float32 (got {t.dtype}, strides {t.stride()})")
+    want = (2 * n,) + tuple(out.shape[1:])
+    if tuple(den2.shape) != want:
+        raise nv.SevaNativeError(f"cfg_rescale: den2 has shape {tuple(den2.shape)}, expected {want}")
+    for name, t in (("scale", scale), ("mult_out", mult_out)):
+        if t is not None and t.numel() != n:
+            raise nv.SevaNativeError(f"cfg_rescale: {name} has {t.numel()} entries for {n} images")
+    check(_lib().seva_cfg_rescale_f32(den2.data_ptr(), scale.data_ptr(), float(phi), out.data_ptr(), ptr(mult_out), n,
+                                      out.numel() // max(n, 1), stream_ptr(out.device)), "seva_cfg_rescale_f32")
+
+
+@_audited("out")
 def euler_step(x: torch.Tensor, den: torch.Tensor, sigma_hat: torch.Tensor, dt: torch.Tensor,
                out: torch.Tensor) -> None:
     require_cuda(x, den, out)

@@ -146,6 +146,14 @@ def _per_pass(v):
     return v, v
 
 
+def _per_pass_interval(v):
+    """`guidance_interval` of the drivers -> the (first pass, second pass) pair: a 2-tuple whose elements are themselves (lo, hi)
+    tuples (or "lo,hi" strings) or None is that pair; anything else -- None, a string, a 2-tuple of numbers -- is one value for both."""
+    if isinstance(v, (list, tuple)) and len(v) == 2 and all(e is None or isinstance(e, (list, tuple, str)) for e in v):
+        return v[0], v[1]
+    return v, v
+
+
 def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int | Sequence[int] = 21, chunk_strategy: str = "interp",
                     first_pass_strategy: str = "gt-nearest", options: dict | None = None,
                     task: str = "img2trajvid", refine_anchors: bool = True) -> TrajectoryPlan:
@@ -242,12 +250,15 @@ def second_pass_schedule(n_windows: int, world: int, cfg_split: bool) -> list[li
 def run_window(win: Window, latents_of: dict, denoise_net: Callable, c2ws, Ks, *, hw, num_steps, cfg, cfg_min, guider,
                camera_scale, noise: torch.Tensor, step_seed: int, clip_token: torch.Tensor, device,
                sampler_hook: Callable | None = None, cfg_split: tuple | None = None,
-               solver: str | None = None, cache_interval: int | None = None, cache_levels: int | None = 1) -> torch.Tensor:
+               solver: str | None = None, cache_interval: int | None = None, cache_levels: int | None = 1,
+               guidance_interval=None, guidance_rescale: float | None = None) -> torch.Tensor:
     """One window = the reference's get_value_dict + do_sample (eval.py:1152-1321) on this package's parts.
     `latents_of[frame_id]` -> (4,h,w) latent of every conditioning frame.  Returns the (T,4,h,w) sample.
     `solver`: `EulerEDMSampler(solver=...)` ("euler", "dpmpp2m"; None = SEVA_SOLVER, default "euler").
     `cache_interval`, `cache_levels`: `EulerEDMSampler(cache_interval=..., cache_levels=...)`, the opt-in reuse of deep UNet
-    features across steps (None = SEVA_CACHE_INTERVAL / SEVA_CACHE_LEVELS, default off)."""
+    features across steps (None = SEVA_CACHE_INTERVAL / SEVA_CACHE_LEVELS, default off).
+    `guidance_interval`, `guidance_rescale`: `EulerEDMSampler(guidance_interval=(sigma_lo, sigma_hi), guidance_rescale=phi)`, the
+    opt-in guidance controls (None = SEVA_GUIDANCE_INTERVAL / SEVA_GUIDANCE_RESCALE, default off)."""
     T = len(win.slot_frame)
     h, w = hw
     frames = win.slot_frame
@@ -261,7 +272,8 @@ def run_window(win: Window, latents_of: dict, denoise_net: Callable, c2ws, Ks, *
     den = S.DiscreteDenoiser(disc, num_idx=1000, device=device)
     g = [S.VanillaCFG(), S.MultiviewCFG(cfg_min), S.MultiviewTemporalCFG(T, cfg_min)][guider]
     sampler = S.EulerEDMSampler(disc, g, num_steps=num_steps, verbose=False, device=device, s_churn=0.0,
-                                solver=solver, cache_interval=cache_interval, cache_levels=cache_levels)
+                                solver=solver, cache_interval=cache_interval, cache_levels=cache_levels,
+                                guidance_interval=guidance_interval, guidance_rescale=guidance_rescale)
     gen = torch.Generator(device=device)
     gen.manual_seed(int(step_seed))
     sampler.noise_fn = lambda x: torch.randn(x.shape, generator=gen, device=x.device, dtype=x.dtype)
@@ -283,13 +295,15 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
                    plan: TrajectoryPlan | None = None, timers: dict | None = None,
                    sampler_hook: Callable | None = None, conditioner: Callable | None = None,
                    input_rgb: torch.Tensor | None = None, cfg_split: bool = False, solver: str | None = None,
-                   cache_interval=None, cache_levels=1) -> dict:
+                   cache_interval=None, cache_levels=1, guidance_interval=None, guidance_rescale=None) -> dict:
     """Generate every non-input frame of a trajectory.  `denoise_net(x, t, cond, num_frames=T)` is the network call
     (`SGMWrapper(model)`); `input_latents` (n_in,4,h,w) are the VAE-encoded input views (x 0.18215), frame ids
     `input_ids` index `c2ws` (n,4,4) / `Ks` (n,3,3).  Returns, on rank 0, {"latents": (n,4,h,w) in frame order,
     "frame_ids", "plan", "anchor_latents" (first-pass anchors as pass 2 saw them), ["rgb"]}; other ranks get {"plan"} only.
     `solver` goes to every window's sampler (`run_window`), and so do `cache_interval` / `cache_levels` (the opt-in reuse of deep
-    UNet features across steps), each one value or a (first pass, second pass) pair.
+    UNet features across steps), each one value or a (first pass, second pass) pair.  Likewise `guidance_interval` /
+    `guidance_rescale` (the opt-in guidance controls): one value or a pair; for the interval a pair is a 2-tuple whose elements are
+    themselves (lo, hi) tuples or None, and a 2-tuple of numbers is one interval for both passes.
     `T`, `cfg` and `guider` each take one value or a (first pass, second pass) pair, as the reference's `--T 96,21` /
     `cfg 3,2` do (eval.py:1785-1789, 1929-1933); `options` goes to the planner (`num_prior_frames_ratio`, ...).  A window
     is as long as its pass of the plan says (`plan.T1` / `plan.T2`): its noise draw, its guider and its network call."""
@@ -300,6 +314,7 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
                                    refine_anchors=refine_anchors)
     cfgs, guiders = _per_pass(cfg), _per_pass(guider)
     cache_ns, cache_ls = _per_pass(cache_interval), _per_pass(cache_levels)
+    guide_ivs, guide_phis = _per_pass_interval(guidance_interval), _per_pass(guidance_rescale)
     rgb_of: dict = {}
     if conditioner is not None:
         # the reference's rule (eval.py:1248): token of a window = mean CLIP embedding of its conditioning views' RGB
@@ -362,7 +377,8 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
         t_w = _now(device) if timers is not None else 0.0
         z = run_window(win, latents_of, denoise_net, c2ws, Ks, noise=noises[win.global_index], step_seed=step_seed(win),
                        clip_token=tok(win.source_ids), cfg_split=(pairs[0], rank) if split1 else None,
-                       cfg=cfgs[0], guider=guiders[0], cache_interval=cache_ns[0], cache_levels=cache_ls[0], **common)
+                       cfg=cfgs[0], guider=guiders[0], cache_interval=cache_ns[0], cache_levels=cache_ls[0],
+                       guidance_interval=guide_ivs[0], guidance_rescale=guide_phis[0], **common)
         if timers is not None:
             timers.setdefault("windows", []).append((1, i, _now(device) - t_w))
         zt = handoff_latent(z[win.target_slots], win.target_ids)
@@ -409,7 +425,8 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
             outs[i] = run_window(win, latents_of, denoise_net, c2ws, Ks, noise=noises[win.global_index],
                                  step_seed=step_seed(win), clip_token=tok(win.source_ids),
                                  cfg_split=(pairs[ranks[0] // 2], ranks.index(rank)) if len(ranks) == 2 else None,
-                                 cfg=cfgs[1], guider=guiders[1], cache_interval=cache_ns[1], cache_levels=cache_ls[1], **common)
+                                 cfg=cfgs[1], guider=guiders[1], cache_interval=cache_ns[1], cache_levels=cache_ls[1],
+                                 guidance_interval=guide_ivs[1], guidance_rescale=guide_phis[1], **common)
             if timers is not None:
                 timers.setdefault("windows", []).append((2, i, _now(device) - t_w))
     mark("pass2")
@@ -456,7 +473,7 @@ def run_views(denoise_net: Callable, input_latents: torch.Tensor, c2ws: torch.Te
               input_ids: Sequence[int], *, T: int = 21, chunk_strategy: str = "gt", options: dict | None = None,
               task: str = "img2img", **run_trajectory_kwargs) -> dict:
     """One-pass generation of every non-input frame: `run_trajectory` over `plan_views(...)`; every other argument (`solver`,
-    `cache_interval`, `cache_levels`, ...) and the result are `run_trajectory`'s ("anchor_latents": every generated frame as
+    `cache_interval`, `cache_levels`, `guidance_interval`, `guidance_rescale`, ...) and the result are `run_trajectory`'s ("anchor_latents": every generated frame as
     later windows saw it)."""
     plan = plan_views(c2ws, input_ids, T, chunk_strategy, options, task)
     return run_trajectory(denoise_net, input_latents, c2ws, Ks, input_ids, T=T, plan=plan, **run_trajectory_kwargs)
@@ -477,7 +494,9 @@ def run_scene(denoise_net: Callable, ae, images: Sequence, c2ws: torch.Tensor, K
     "metrics" = {"frame_ids", "sse", "psnr", "ssim"}; in either mode.  `lpips` (a `metrics.LPIPS` on the device; frames of at
     least 32 x 32) adds "lpips" to that table: the complete score table without the frames leaving the card.
     `cache_interval=` / `cache_levels=` (like every other sampler option) travel to `run_trajectory`; with `use_traj_prior=False`
-    and `targets=` this is the call that measures what the reuse of deep features costs in picture quality."""
+    and `targets=` this is the call that measures what the reuse of deep features costs in picture quality.  The same holds for
+    `guidance_interval=` / `guidance_rescale=`: `run_scene(..., use_traj_prior=False, targets=..., guidance_interval=...,
+    guidance_rescale=...)` is the call that measures what they do to picture quality."""
     from . import frames
     device = torch.device(run_trajectory_kwargs.pop("device", None) or "cuda")
     ids = [int(i) for i in input_ids]

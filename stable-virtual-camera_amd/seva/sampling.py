@@ -362,6 +362,41 @@ def parse_cache(interval, levels) -> tuple:
     return (n if n >= 2 else 0), lv
 
 
+def parse_guidance(interval, rescale) -> tuple:
+    """(interval, phi) of the guidance controls from arguments or environment strings.  interval: None / "" = off (returned as
+    None), else (sigma_lo, sigma_hi) -- a pair of numbers or a string "lo,hi" -- with 0 <= sigma_lo < sigma_hi, sigma_hi may be
+    inf; returned as a pair of floats.  rescale: None / "" = 0.0 (off), else a number or numeric string in [0, 1].  Anything else
+    is a ValueError."""
+    def as_float(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, float, str)):
+            raise ValueError(f"{what} must be a number, got {v!r}")
+        try:
+            f = float(v)
+        except ValueError:
+            raise ValueError(f"{what} must be a number, got {v!r}") from None
+        if f != f:
+            raise ValueError(f"{what} must not be NaN")
+        return f
+
+    if interval is None or (isinstance(interval, str) and interval.strip() == ""):
+        iv = None
+    else:
+        parts = interval.split(",") if isinstance(interval, str) else interval
+        if not isinstance(parts, (list, tuple)) or len(parts) != 2:
+            raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) or \"lo,hi\", got {interval!r}")
+        lo, hi = as_float(parts[0], "guidance_interval sigma_lo"), as_float(parts[1], "guidance_interval sigma_hi")
+        if not (0.0 <= lo < hi) or lo == float("inf"):
+            raise ValueError(f"guidance_interval needs 0 <= sigma_lo < sigma_hi, got {interval!r}")
+        iv = (lo, hi)
+    if rescale is None or (isinstance(rescale, str) and rescale.strip() == ""):
+        phi = 0.0
+    else:
+        phi = as_float(rescale, "guidance_rescale")
+        if not 0.0 <= phi <= 1.0:
+            raise ValueError(f"guidance_rescale must lie in [0, 1], got {rescale!r}")
+    return iv, phi
+
+
 class EulerEDMSampler(object):
     """Reference sampling.py:301-405 (Euler discretisation of the EDM probability-flow ODE).
 
@@ -374,12 +409,29 @@ class EulerEDMSampler(object):
     runs the whole network iff i % N == 0 or it is the last step; every other step runs a shallow network call of depth
     `cache_levels` (1, 2 or 3: `SevaEngine.forward(shallow_levels=...)`), which recomputes the top of the UNet and takes the rest
     from the last full step.  0 or 1: off.  None reads SEVA_CACHE_INTERVAL and SEVA_CACHE_LEVELS (unset: off, depth 1).  The
-    schedule lives in `__call__`: a subclass that drives `sampler_step` itself gets full steps."""
+    schedule lives in `__call__`: a subclass that drives `sampler_step` itself gets full steps.
+
+    `guidance_interval` = (sigma_lo, sigma_hi) (opt-in, not in the reference; Kynkaanniemi et al. 2024): step i is guided iff
+    sigma_lo < sigmas[i] <= sigma_hi -- the schedule's own sigma, so churn moves no step across a bound.  Every other step calls the
+    denoiser on the conditional inputs alone (n frames instead of 2n, no guider) and takes the plain update.  None reads
+    SEVA_GUIDANCE_INTERVAL="lo,hi" (unset: off = every step guided).  The schedule lives in `__call__` too: a subclass that drives
+    `sampler_step` itself gets guided steps.  With `cache_interval`, a step whose guided flag differs from the previous step's is a
+    full step as well (the network's batch changes there).
+    `guidance_rescale` = phi in [0, 1] (opt-in, not in the reference; Lin et al. 2024): on guided steps the guided prediction of
+    each frame is scaled to the standard deviation of that frame's conditional prediction, blended with weight phi
+    (`ops.cfg_rescale`), before the plain update.  None reads SEVA_GUIDANCE_RESCALE (unset or 0: off).  Needs a guider that states
+    its `frame_scale`."""
 
     def __init__(self, discretization: DDPMDiscretization, guider, num_steps: int | None = None,
                  verbose: bool = False, device: str | torch.device = "cuda", s_churn=0.0, s_tmin=0.0,
                  s_tmax=float("inf"), s_noise=1.0, solver: str | None = None, check_finite: bool | None = None,
-                 cache_interval: int | None = None, cache_levels: int | None = 1):
+                 cache_interval: int | None = None, cache_levels: int | None = 1,
+                 guidance_interval: tuple | str | None = None, guidance_rescale: float | None = None):
+        if guidance_interval is None:
+            guidance_interval = os.environ.get("SEVA_GUIDANCE_INTERVAL")
+        if guidance_rescale is None:
+            guidance_rescale = os.environ.get("SEVA_GUIDANCE_RESCALE")
+        self.guidance_interval, self.guidance_rescale = parse_guidance(guidance_interval, guidance_rescale)
         if cache_interval is None:  # both from the environment (the depth: the argument where the variable is unset)
             cache_interval = os.environ.get("SEVA_CACHE_INTERVAL")
             cache_levels = os.environ.get("SEVA_CACHE_LEVELS") or cache_levels
@@ -449,17 +501,17 @@ class EulerEDMSampler(object):
             sigma_generator = tqdm(sigma_generator, total=num_sigmas - 1, desc="Sampling", leave=False)
         return sigma_generator
 
-    def _step_math(self, sigma, next_sigma, x, eps, denoiser, scale, cond, uc, gamma, guider_kwargs, shallow=0):
+    def _step_math(self, sigma, next_sigma, x, eps, denoiser, scale, cond, uc, gamma, guider_kwargs, shallow=0, guided=True):
         """Reference sampling.py:357-368 on f32 contiguous device tensors; sync-free once the guider's rule is cached,
-        which is what makes it capturable as one hipGraph (`_stepgraph.StepGraph`)."""
+        which is what makes it capturable as one hipGraph (`_stepgraph.StepGraph`).  The step's kind (`guided`,
+        `guidance_rescale`) decides the operands alone (`_step_operands`)."""
         sigma_hat = sigma * (gamma + 1.0) + 1e-6
         noise_scale = (sigma_hat**2 - sigma**2) ** 0.5 * self.s_noise
         x_noised = torch.empty_like(x)
         ops.add_noise(x, eps, _f32c(noise_scale), x_noised)
-        denoised2 = self._denoised_pair(denoiser, x_noised, sigma_hat, cond, uc, shallow)
+        den, fs = self._step_operands(denoiser, x_noised, sigma_hat, scale, cond, uc, x, guider_kwargs, shallow, guided)
         dt = next_sigma - sigma_hat
         out = torch.empty_like(x)
-        den, fs = self._guidance_operands(denoised2, sigma_hat, scale, x, guider_kwargs)
         if fs is not None:
             ops.cfg_euler(x_noised, den, fs, sigma_hat, dt, out)  # CFG combine + to_d + Euler update in one pass
         else:
@@ -476,6 +528,32 @@ class EulerEDMSampler(object):
         if self.cfg_split is None:
             return denoiser(*self.guider.prepare_inputs(x_in, sigma_in, cond, uc))
         return self._denoise_cfg_split(denoiser, x_in, sigma_in, cond, uc)
+
+    def _step_operands(self, denoiser, x_in, sigma_in, scale, cond, uc, x, guider_kwargs, shallow=0, guided=True):
+        """(den, fs) for a step's update kernel, whatever the step's kind.
+        Guided, `guidance_rescale` 0: `_guidance_operands` of the CFG-batched call -- the fused kernels combine.
+        Guided, `guidance_rescale` = phi > 0: (D, None) with D from `ops.cfg_rescale` on the [uncond ; cond] pair, a latent-sized
+        round trip that the fused path does not make; needs a guider that states its `frame_scale`.
+        Unguided: (the denoiser on the conditional inputs alone, None), at batch n -- no `guider.prepare_inputs`, no scale rule,
+        and under `cfg_split` no collective: both ranks of the pair make this call themselves and go on holding identical state
+        (the half batch is bitwise the half of the full batch).  The denoiser gets a dictionary of its own (`DiscreteDenoiser`
+        pops "replace" from the one it is handed)."""
+        if not guided:
+            if shallow:
+                with _native.shallow_network(shallow):
+                    return _f32c(denoiser(x_in, sigma_in, dict(cond))), None
+            return _f32c(denoiser(x_in, sigma_in, dict(cond))), None
+        phi = self.guidance_rescale
+        if phi > 0 and not hasattr(self.guider, "frame_scale"):
+            raise ValueError("guidance_rescale > 0 needs a guider that states its per-frame scale (`frame_scale`): "
+                             f"{type(self.guider).__name__} has none")
+        denoised2 = self._denoised_pair(denoiser, x_in, sigma_in, cond, uc, shallow)
+        den, fs = self._guidance_operands(denoised2, sigma_in, scale, x, guider_kwargs)
+        if phi > 0:
+            D = torch.empty_like(x)
+            ops.cfg_rescale(den, fs, phi, D)
+            return D, None
+        return den, fs
 
     def _guidance_operands(self, denoised2, sigma_in, scale, x, guider_kwargs):
         """What the fused update kernels take: (the f32 [uncond ; cond] pair, the per-frame scale vector) for them to
@@ -525,15 +603,16 @@ class EulerEDMSampler(object):
         c = torch.where(second, -one_a * inv_2r, zero)
         return a, b, c
 
-    def _multistep_math(self, sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs, shallow=0):
+    def _multistep_math(self, sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs, shallow=0,
+                        guided=True):
         """One DPM-Solver++(2M) step on f32 contiguous device tensors: no noise, no sigma_hat; guidance, update and the new
         history in ONE kernel (`ops.cfg_multistep`), which reads D- from `hist` and leaves D there.  Sync-free like
         `_step_math`, and the same code for the first, the second-order and the last step (they differ in a, b, c only), so
-        one hipGraph serves them all."""
-        denoised2 = self._denoised_pair(denoiser, x, sigma, cond, uc, shallow)
+        one hipGraph serves them all.  An unguided or a rescaled step hands the kernel its D with scale=None
+        (`_step_operands`); the history is whatever D the step used."""
+        den, fs = self._step_operands(denoiser, x, sigma, scale, cond, uc, x, guider_kwargs, shallow, guided)
         a, b, c = self.multistep_coefficients(sigma, next_sigma, prev_sigma)
         out = torch.empty_like(x)
-        den, fs = self._guidance_operands(denoised2, sigma, scale, x, guider_kwargs)
         ops.cfg_multistep(x, den, fs, hist, a, b, c, out, hist)
         return out
 
@@ -556,31 +635,41 @@ class EulerEDMSampler(object):
                 and ops._AUDIT is None and not torch.cuda.is_current_stream_capturing())
 
     def sampler_step(self, sigma: torch.Tensor, next_sigma: torch.Tensor, denoiser, x: torch.Tensor,
-                     scale, cond: dict, uc: dict, gamma: float = 0.0, *, shallow: int = 0, **guider_kwargs) -> torch.Tensor:
+                     scale, cond: dict, uc: dict, gamma: float = 0.0, *, shallow: int = 0, guided: bool = True,
+                     **guider_kwargs) -> torch.Tensor:
         """One Euler-EDM step (reference sampling.py:347-368), or one DPM-Solver++(2M) step under solver="dpmpp2m".  From
         the second step of a trajectory on, the whole step is replayed from one hipGraph (see `_stepgraph`); the first step
         runs eagerly and warms every cache.  Stays a callable unit for `GradioTrackedSampler` (reference eval.py:1037-1089).
         `shallow` = L > 0 (`__call__`'s `cache_interval` schedule): the step's network call is a shallow one of depth L; such
-        steps have a whole-step graph of their own."""
+        steps have a whole-step graph of their own.  `guided` False (`__call__`'s `guidance_interval` schedule): the step calls the
+        denoiser on the conditional inputs alone and takes the plain update; such steps, full or shallow, have graphs of their
+        own too."""
         _need_gpu(x)
         x = _f32c(x)
         sigma = _f32c(sigma)
         next_sigma = _f32c(next_sigma)
         multistep = self.solver == "dpmpp2m"
         flat = _stepgraph.StepGraphCache.flat_key((scale, cond, uc, guider_kwargs))
+        # what the feature adds to the key, nothing while it is off: a rescaled step's phi is baked into its graph
+        if not guided:
+            flat += ("unguided",)
+        elif self.guidance_rescale > 0:
+            flat += ("rescale", float(self.guidance_rescale))
         # per solver: the cache key (everything the closure holds), the sync-free step as a closure, the fourth graph input
         if multistep:  # deterministic: no noise draw, no add_noise; `gamma` has nothing to act on
             hist, fourth = self._multistep_history(x, sigma)
             key = ("dpmpp2m", tuple(x.shape), hist, self.guider, denoiser) + flat
-            fn = lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, denoiser, scale, cond, uc, guider_kwargs, shallow)  # noqa: E731
+            fn = lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, denoiser, scale, cond, uc, guider_kwargs, shallow, guided)  # noqa: E731
         else:
             fourth = _f32c(self.noise_fn(x))  # eps, drawn eagerly: the generator advances per step exactly as in the reference
             gamma = float(gamma)
             key = (tuple(x.shape), gamma, float(self.s_noise), self.guider, denoiser) + flat
-            fn = lambda s, n, xx, ee: self._step_math(s, n, xx, ee, denoiser, scale, cond, uc, gamma, guider_kwargs, shallow)  # noqa: E731
+            fn = lambda s, n, xx, ee: self._step_math(s, n, xx, ee, denoiser, scale, cond, uc, gamma, guider_kwargs, shallow, guided)  # noqa: E731
+        # the step kind names the graph entry: 0 / L as ever for a guided step, (0 / L, "unguided") for an unguided one
+        kind = shallow if guided else (shallow, "unguided")
         # keep: the graph reads the warm-up step's rule tensor, which must therefore outlive `reset_rule_cache`
         out = self._step_graphs.run(key, fn, (sigma, next_sigma, x, fourth), eligible=self._whole_step_graph_eligible(x),
-                                    keep=lambda: getattr(self.guider, "_rule_cache", None), **({"kind": shallow} if shallow else {}))
+                                    keep=lambda: getattr(self.guider, "_rule_cache", None), **({"kind": kind} if kind else {}))
         if multistep:
             self._ms_sigma, self._ms_have = sigma, True
         return out
@@ -590,6 +679,7 @@ class EulerEDMSampler(object):
         uc = cond if uc is None else uc
         x, s_in, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x, cond, uc, num_steps)
         every, last = self.cache_interval, num_sigmas - 2
+        interval, was_guided = self.guidance_interval, True
         for i in self.get_sigma_gen(num_sigmas, verbose=verbose):
             gamma = (
                 min(self.s_churn / (num_sigmas - 1), 2**0.5 - 1)
@@ -598,7 +688,14 @@ class EulerEDMSampler(object):
             )
             # deep-feature reuse: a full step at every `every`-th step and at the last one, shallow steps in between
             # (the keyword is passed on shallow steps only: with the mode off the calls are the ones made before)
-            kind = {} if not every or i % every == 0 or i == last else {"shallow": self.cache_levels}
+            # guidance interval: decided on the schedule's own sigma (not sigma_hat: churn moves no step across a bound), in the
+            # sigmas' dtype like the test above; the keyword is passed on unguided steps only
+            guided = interval is None or bool(interval[0] < self._sigmas_host[i] <= interval[1])
+            # (a shallow call needs a full call of the same batch behind it: where the guided flag changes, the step is full)
+            kind = {} if not every or i % every == 0 or i == last or guided != was_guided else {"shallow": self.cache_levels}
+            if not guided:
+                kind["guided"] = False
+            was_guided = guided
             x = self.sampler_step(s_in * sigmas[i], s_in * sigmas[i + 1], denoiser, x, scale, cond, uc,
                                   gamma, **kind, **guider_kwargs)
         # once per trajectory, after the last step (never inside the loop): a split-K consumer that gave up waiting for its
