@@ -156,7 +156,8 @@ def _per_pass_interval(v):
 
 def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int | Sequence[int] = 21, chunk_strategy: str = "interp",
                     first_pass_strategy: str = "gt-nearest", options: dict | None = None,
-                    task: str = "img2trajvid", refine_anchors: bool = True) -> TrajectoryPlan:
+                    task: str = "img2trajvid", refine_anchors: bool = True,
+                    anchor_ids: Sequence[int] | None = None) -> TrajectoryPlan:
     """Anchors + windows of both passes for one trajectory; frame ids index `c2ws` (inputs first, like the reference's
     `input_indices` convention in run_one_scene).
 
@@ -170,7 +171,16 @@ def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int | Seque
     the lengths as the reference does (eval.py:344-421): the first pass becomes ONE window of all inputs + all anchors, and
     `interp-gt` widens the second pass by the input views it carries (golden: tests/golden/g15_semidense_plans.json).  The plan
     records both (`T1`, `T2`); `T` is the first-pass length.  `options` carries `num_prior_frames_ratio`, `num_prior_frames`
-    and `num_input_semi_dense`."""
+    and `num_input_semi_dense`.
+
+    `anchor_ids`: None (the default) lets `infer_prior_inds` choose the anchors; a list of frame ids takes that choice's place (the
+    reference's callers hand `run_one_scene` their own anchors: demo.py:231-256 spreads them over the targets with a rounding rule
+    of its own; `seva.scenes` is the caller here).  The ids must lie in the trajectory, and must not be input views; they are used in
+    ascending order, like `infer_prior_inds`' own, and an id given twice (the rounding rule repeats ids where it asks for more
+    anchors than there are targets) counts once.
+
+    Limit: a window length that leaves fewer than two free target slots (T < inputs + 2; under `interp-gt`, T < inputs + 4) makes the
+    chunkers loop without end ("Known limit").  The window lengths still follow `infer_prior_stats`."""
     n = c2ws.shape[0]
     ins = [int(i) for i in input_ids]
     opts = {"sampler_verbose": False, **(options or {}), "chunk_strategy": chunk_strategy}
@@ -178,7 +188,17 @@ def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int | Seque
     vd = {"T": T, "options": opts}
     n_prior = planner.infer_prior_stats(T, len(ins), n - len(ins), vd)
     T1, T2 = (int(t) for t in _per_pass(vd["T"]))
-    anchors = [int(v) for v in planner.infer_prior_inds(c2ws, n_prior, ins, opts)]
+    if anchor_ids is None:
+        anchors = [int(v) for v in planner.infer_prior_inds(c2ws, n_prior, ins, opts)]
+    else:
+        if any(int(v) != v for v in anchor_ids):
+            raise ValueError(f"anchor_ids: integer frame ids, not {list(anchor_ids)!r}")
+        anchors = sorted({int(v) for v in anchor_ids})
+        bad = [a for a in anchors if not 0 <= a < n]
+        if not anchors or bad:
+            raise ValueError(f"anchor_ids: {'an empty list' if not anchors else f'{bad} outside the {n} frames of the trajectory'}")
+        if set(anchors) & set(ins):
+            raise ValueError(f"anchor_ids: {sorted(set(anchors) & set(ins))} are input views")
     w1, serial = _input_conditioned_windows(c2ws, ins, anchors, T1, opts, task, first_pass_strategy)
     order = np.argsort(ins + anchors).tolist()
     pool2 = [(ins + anchors)[o] for o in order]
@@ -295,7 +315,8 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
                    plan: TrajectoryPlan | None = None, timers: dict | None = None,
                    sampler_hook: Callable | None = None, conditioner: Callable | None = None,
                    input_rgb: torch.Tensor | None = None, cfg_split: bool = False, solver: str | None = None,
-                   cache_interval=None, cache_levels=1, guidance_interval=None, guidance_rescale=None) -> dict:
+                   cache_interval=None, cache_levels=1, guidance_interval=None, guidance_rescale=None,
+                   anchor_ids: Sequence[int] | None = None) -> dict:
     """Generate every non-input frame of a trajectory.  `denoise_net(x, t, cond, num_frames=T)` is the network call
     (`SGMWrapper(model)`); `input_latents` (n_in,4,h,w) are the VAE-encoded input views (x 0.18215), frame ids
     `input_ids` index `c2ws` (n,4,4) / `Ks` (n,3,3).  Returns, on rank 0, {"latents": (n,4,h,w) in frame order,
@@ -306,12 +327,13 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
     themselves (lo, hi) tuples or None, and a 2-tuple of numbers is one interval for both passes.
     `T`, `cfg` and `guider` each take one value or a (first pass, second pass) pair, as the reference's `--T 96,21` /
     `cfg 3,2` do (eval.py:1785-1789, 1929-1933); `options` goes to the planner (`num_prior_frames_ratio`, ...).  A window
-    is as long as its pass of the plan says (`plan.T1` / `plan.T2`): its noise draw, its guider and its network call."""
+    is as long as its pass of the plan says (`plan.T1` / `plan.T2`): its noise draw, its guider and its network call.
+    `anchor_ids` goes to `plan_trajectory` (None: the planner's own anchors); with a ready `plan=` it is not read."""
     rank, world = _rank_world(group)
     device = torch.device(device) if device is not None else input_latents.device
     h, w = input_latents.shape[-2:]
     plan = plan or plan_trajectory(c2ws, input_ids, T, chunk_strategy, first_pass_strategy, options,
-                                   refine_anchors=refine_anchors)
+                                   refine_anchors=refine_anchors, anchor_ids=anchor_ids)
     cfgs, guiders = _per_pass(cfg), _per_pass(guider)
     cache_ns, cache_ls = _per_pass(cache_interval), _per_pass(cache_levels)
     guide_ivs, guide_phis = _per_pass_interval(guidance_interval), _per_pass(guidance_rescale)
