@@ -143,11 +143,30 @@ def env_int(name: str, default: int) -> int:
     return int(os.environ.get(name, default))
 
 
+class Act:
+    """A residual-stream tensor on its way from block to block: `t`, fp32 channels-last [n, h*w, c], the image size, and `stats`,
+    the GroupNorm statistics that its producer's epilogue emitted (seva_gemm_desc.ch_stats), or None where it emitted none."""
+
+    __slots__ = ("t", "n", "h", "w", "stats")
+
+    def __init__(self, t, n, h, w, stats=None):
+        self.t, self.n, self.h, self.w, self.stats = t, n, h, w, stats
+
+    hw = property(lambda self: self.h * self.w)
+    c = property(lambda self: self.t.shape[2])
+    rows = property(lambda self: self.n * self.h * self.w)
+    t2 = property(lambda self: self.t.view(self.rows, self.c))  # [rows, c]: what a GEMM reads or writes
+    # the output keywords of the call that produces it: a conv (3-D), a GEMM (2-D)
+    dst = property(lambda self: {"out_f32": self.t, "ch_stats": self.stats})
+    dst2 = property(lambda self: {"out_f32": self.t2, "ch_stats": self.stats})
+
+
 class _EngineBase:
     """What the UNet, VAE and CLIP engines share: the device of the module they pack, the arena, and (engines with GroupNorms) the
     hand-off of GroupNorm statistics from the producing kernel's epilogue."""
 
     NEEDS_GPU = ""  # the error of a module that is not on a cuda device
+    _ops = property(lambda self: ops)  # what `_groupnorm` launches through: an engine in another module binds its own `ops` (the tests' seam)
 
     @staticmethod
     def _resolve_device(module):
@@ -167,7 +186,6 @@ class _EngineBase:
             # GroupNorm statistics from the producers' epilogues: 0 off (separate statistics pass everywhere, A/B runs),
             # 1 where it pays (default), 2 wherever hw % 64 == 0, even on launches that would otherwise run 64-row tiles (tests)
             self.gn_fused_stats = env_int("SEVA_GN_FUSED_STATS", 1)
-            self._stats: dict = {}
 
     def _buf(self, name, shape, dtype, zero=False):
         return self.arena.get(name, shape, dtype, zero)
@@ -185,20 +203,17 @@ class _EngineBase:
             return None
         return self._buf("st:" + name, ops.channel_stats_shape(rows, c), F32)
 
-    def _produced(self, out, st):
-        """Record (or forget) the statistics buffer that travels with fp32 tensor `out`."""
-        if st is None:
-            self._stats.pop(out.data_ptr(), None)
-        else:
-            self._stats[out.data_ptr()] = st
+    def _out32(self, name, n, h, w, c) -> Act:
+        """The arena's stream tensor `name`, with the statistics buffer its producer is to fill (`_stats_buf`'s rule)."""
+        t = self._buf(name, (n, h * w, c), F32)
+        return Act(t, n, h, w, self._stats_buf(name, n * h * w, h * w, c))
 
-    def _gn_stats(self, x1, x2=None):
-        """(stats1, stats2) for a GroupNorm over x1 (|| x2): the producers' buffers, or (None, None) unless every source has one."""
-        s1 = self._stats.get(x1.data_ptr())
-        s2 = None if x2 is None else self._stats.get(x2.data_ptr())
+    def _groupnorm(self, x: Act, x2: Act | None, gamma, beta, out_f16, **kw):
+        """`ops.groupnorm` over x (|| x2) with the producers' statistics: both sources' buffers, or none unless every source has one."""
+        s1, s2 = x.stats, None if x2 is None else x2.stats
         if s1 is None or (x2 is not None and s2 is None):
-            return None, None
-        return s1, s2
+            s1 = s2 = None
+        self._ops.groupnorm(x.t, None if x2 is None else x2.t, gamma, beta, out_f16, self.gn_ws, stats1=s1, stats2=s2, **kw)
 
 
 class SevaEngine(_EngineBase):
@@ -261,7 +276,7 @@ class SevaEngine(_EngineBase):
         self.use_graph = env_flag("SEVA_HIPGRAPH", "not0", True)
         self._graphs: dict = {}
         # shallow calls (`forward(shallow_levels=L)`): the signature of the last full call, and per signature what a full call
-        # left behind for each entry point L -- (tensor entering the first output block a shallow call runs, h, w, its statistics)
+        # left behind for each entry point L -- the `Act` entering the first output block a shallow call runs (statistics included)
         self._last_full: tuple | None = None
         self._shallow_entries: dict = {}
         # per depth L = 1, 2, ...: the input blocks after the stem that precede the L-th Downsample of the layout
@@ -543,10 +558,11 @@ class SevaEngine(_EngineBase):
                      out_f16=None if out_f16 is None else out_f16[r0:r1])
 
     # ------------------------------------------------------------------ blocks
-    def _resblock(self, spec, x1, x2, n, h, w, dense, emb_all):
+    def _resblock(self, spec, x1: Act, x2: Act | None, dense, emb_all) -> Act:
         """ResBlock.forward, reference layers.py:120-139.  x1 (‖ x2) fp32 [n, hw, c]."""
         audit_mark(spec.prefix)
-        W, pfx, hw = self.W, spec.prefix, h * w
+        W, pfx = self.W, spec.prefix
+        n, h, w, hw = x1.n, x1.h, x1.w, x1.hw
         cin, cout = spec.cin, spec.cout
         f8_1, f8_2 = pfx + ".conv1.w8" in W, pfx + ".conv2.w8" in W  # fp8 mode: the conv consumes e4m3 activations
         sp_conv = "conv" in self.split  # both GroupNorms write [hi | lo] channels, the convs see 2 cin / 2 cout input channels
@@ -557,24 +573,22 @@ class SevaEngine(_EngineBase):
         # the 1x1 skip conv (cin != cout) consumes the raw input as f16: emitted by the same GroupNorm pass
         sp_skip = cin != cout and self._split_skip(cout)
         xs16 = self._buf("skip16", (n * hw, (2 if sp_skip else 1) * cin), F16) if cin != cout else None
-        s1, s2 = self._gn_stats(x1, x2)
-        ops.groupnorm(x1, x2, W[pfx + ".in_layers.0.g"], W[pfx + ".in_layers.0.b"], a16, self.gn_ws,
-                      eps=1e-5, silu=True, dense=dense, dense_w=W[pfx + ".dense.w"], dense_b=W[pfx + ".dense.b"],
-                      raw_f16=xs16, out_f8=a8, stats1=s1, stats2=s2, split_raw=sp_skip, split_out=sp_conv)
-        hmid = self._buf("res_mid", (n, hw, cout), F32)
-        st_mid = self._stats_buf("res_mid", n * hw, hw, cout)
+        self._groupnorm(x1, x2, W[pfx + ".in_layers.0.g"], W[pfx + ".in_layers.0.b"], a16,
+                        eps=1e-5, silu=True, dense=dense, dense_w=W[pfx + ".dense.w"], dense_b=W[pfx + ".dense.b"],
+                        raw_f16=xs16, out_f8=a8, split_raw=sp_skip, split_out=sp_conv)
+        mid = self._out32("res_mid", n, h, w, cout)
         off = self.emb_off[pfx]
         if f8_1:
             ops.conv3x3(a8.view(n, h, w, cin8), W[pfx + ".conv1.w8"], w_exp=W[pfx + ".conv1.w8e"], bias=W[pfx + ".conv1.b"],
-                        row_add=emb_all[:, off:], rows_per_group=hw, ld_row_add=self.emb_total, out_f32=hmid, ch_stats=st_mid)
+                        row_add=emb_all[:, off:], rows_per_group=hw, ld_row_add=self.emb_total, **mid.dst)
         else:
             ops.conv3x3(a16.view(n, h, w, k1), W[pfx + ".conv1.w"], bias=W[pfx + ".conv1.b"],
-                        row_add=emb_all[:, off:], rows_per_group=hw, ld_row_add=self.emb_total, out_f32=hmid, ch_stats=st_mid,
+                        row_add=emb_all[:, off:], rows_per_group=hw, ld_row_add=self.emb_total, **mid.dst,
                         splitk_ws=self._sk(n * hw, hw, cout), alg_k=9 * cin if sp_conv else 0)
         b16 = None if f8_2 else self._buf("gn16", (n, hw, k2), F16)
         b8 = self._buf("gn8", (n, hw, cout8), U8, zero=True) if f8_2 else None
-        ops.groupnorm(hmid, None, W[pfx + ".out_layers.0.g"], W[pfx + ".out_layers.0.b"], b16, self.gn_ws,
-                      eps=1e-5, silu=True, out_f8=b8, stats1=st_mid, split_out=sp_conv)
+        self._groupnorm(mid, None, W[pfx + ".out_layers.0.g"], W[pfx + ".out_layers.0.b"], b16,
+                        eps=1e-5, silu=True, out_f8=b8, split_out=sp_conv)
         fold = cin != cout and self.fold_skip and not f8_2 and (hw > 128 or not self.conv_splitk)
         if fold:
             res = None
@@ -583,20 +597,17 @@ class SevaEngine(_EngineBase):
             ops.gemm(xs16, W[pfx + ".skip.w"], bias=W[pfx + ".skip.b"], out_f32=res, alg_k=cin)  # ([hi | lo] doubles K, not the FLOP credit)
         else:
             assert x2 is None
-            res = x1
-        out = self._buf("out:" + pfx, (n, hw, cout), F32)
-        st_out = self._stats_buf("out:" + pfx, n * hw, hw, cout)
+            res = x1.t
+        out = self._out32("out:" + pfx, n, h, w, cout)
         if fold:
-            ops.conv3x3(b16.view(n, h, w, k2), W[pfx + ".conv2.wf"], bias=W[pfx + ".conv2.bf"], a2=xs16, out_f32=out,
-                        ch_stats=st_out)
+            ops.conv3x3(b16.view(n, h, w, k2), W[pfx + ".conv2.wf"], bias=W[pfx + ".conv2.bf"], a2=xs16, **out.dst)
         elif f8_2:
             ops.conv3x3(b8.view(n, h, w, cout8), W[pfx + ".conv2.w8"], w_exp=W[pfx + ".conv2.w8e"], bias=W[pfx + ".conv2.b"],
-                        residual=res, out_f32=out, ch_stats=st_out)
+                        residual=res, **out.dst)
         else:
             ops.conv3x3(b16.view(n, h, w, k2), W[pfx + ".conv2.w"], bias=W[pfx + ".conv2.b"],
-                        residual=res, out_f32=out, ch_stats=st_out, splitk_ws=self._sk(n * hw, hw, cout),
+                        residual=res, **out.dst, splitk_ws=self._sk(n * hw, hw, cout),
                         alg_k=9 * cout if sp_conv else 0)
-        self._produced(out, st_out)
         return out
 
     def _self_attention(self, x32, ln_pfx, at_pfx, rows, c, heads, *, regime, n, hw, T, residual,
@@ -681,16 +692,15 @@ class SevaEngine(_EngineBase):
                       o_strides=o_strides)
         ops.gemm(att, W[at_pfx + ".out.w"], bias=W[at_pfx + ".out.b"], residual=x32, out_f32=out_f32)
 
-    def _transformer(self, spec, x, n, h, w, T, ctxvec, ctx16, lc):
+    def _transformer(self, spec, x: Act, T, ctxvec, ctx16, lc) -> Act:
         """MultiviewTransformer.forward, reference transformer.py:215-247."""
         audit_mark(spec.prefix)
-        W, pfx, hw, c, heads = self.W, spec.prefix, h * w, spec.channels, spec.heads
-        rows = n * hw
+        W, pfx, c, heads = self.W, spec.prefix, spec.channels, spec.heads
+        n, hw, rows = x.n, x.hw, x.rows
         sp_in, sp_out = "proj_in" in self.split, "proj_out" in self.split
         cs = 2 * c if sp_in else c
         g16 = self._buf("gn16", (n, hw, cs), F16)
-        ops.groupnorm(x, None, W[pfx + ".norm.g"], W[pfx + ".norm.b"], g16, self.gn_ws, eps=1e-6, silu=False,
-                      stats1=self._gn_stats(x)[0], split_out=sp_in)
+        self._groupnorm(x, None, W[pfx + ".norm.g"], W[pfx + ".norm.b"], g16, eps=1e-6, silu=False, split_out=sp_in)
         cur = self._buf("t_h", (rows, c), F32)
         ops.gemm(g16.view(rows, cs), W[pfx + ".proj_in.w"], bias=W[pfx + ".proj_in.b"], out_f32=cur, alg_k=c if sp_in else 0)
         collapse = lc == 1
@@ -748,42 +758,36 @@ class SevaEngine(_EngineBase):
             self._ff(m2, m + ".norm3", m + ".ff", rows, c, residual=h2, out_f32=nxt, out_f16=last16, unit=hw)
             cur = nxt
         audit_mark(pfx)
-        out = self._buf("out:" + pfx, (n, hw, c), F32)
-        st_out = self._stats_buf("out:" + pfx, rows, hw, c)
-        ops.gemm(last16, W[pfx + ".proj_out.w"], bias=W[pfx + ".proj_out.b"], residual=x.view(rows, c),
-                 out_f32=out.view(rows, c), ch_stats=st_out, alg_k=c if sp_out else 0)
-        self._produced(out, st_out)
+        out = self._out32("out:" + pfx, n, x.h, x.w, c)
+        ops.gemm(last16, W[pfx + ".proj_out.w"], bias=W[pfx + ".proj_out.b"], residual=x.t2, **out.dst2, alg_k=c if sp_out else 0)
         return out
 
-    def _resample(self, spec, x, n, h, w):
+    def _resample(self, spec, x: Act) -> Act:
         """Downsample (layers.py:49-58) / Upsample (layers.py:35-46)."""
         audit_mark(spec.prefix)
         c = spec.channels
+        n, h, w = x.n, x.h, x.w
         sp_rs = "resample" in self.split
         x16 = self._buf("rs16", (n, h, w, 2 * c if sp_rs else c), F16)
-        (ops.cast_concat_f16_split if sp_rs else ops.cast_concat_f16)(x, None, x16)
+        (ops.cast_concat_f16_split if sp_rs else ops.cast_concat_f16)(x.t, None, x16)
         alg_k = 9 * c if sp_rs else 0
         if spec.kind == "down":
             oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-            out = self._buf("out:" + spec.prefix, (n, oh * ow, c), F32)
-            st_out = self._stats_buf("out:" + spec.prefix, n * oh * ow, oh * ow, c)
-            ops.conv3x3(x16, self.W[spec.prefix + ".w"], stride=2, bias=self.W[spec.prefix + ".b"], out_f32=out, ch_stats=st_out,
+            out = self._out32("out:" + spec.prefix, n, oh, ow, c)
+            ops.conv3x3(x16, self.W[spec.prefix + ".w"], stride=2, bias=self.W[spec.prefix + ".b"], **out.dst,
                         splitk_ws=self._sk(n * oh * ow, oh * ow, c), alg_k=alg_k)
+            return out
+        oh, ow = 2 * h, 2 * w
+        phases = getattr(ops, "conv3x3_up_phases", None)
+        if phases is not None and c % 160 == 0 and env_flag("SEVA_UPSAMPLE_PHASES", "not0", True):  # (read at every call)
+            # four 2x2 phase convs on the source image: 4/9 of the FLOPs.  The path emits no statistics (a 64-row block of one
+            # phase is not image-aligned), so the consuming GroupNorm runs its own pass over this tensor
+            out = Act(self._buf("out:" + spec.prefix, (n, oh * ow, c), F32), n, oh, ow)
+            phases(x16, self.W[spec.prefix + ".w4"], bias=self.W[spec.prefix + ".b"], **out.dst, alg_k=9 * c)
         else:
-            oh, ow = 2 * h, 2 * w
-            out = self._buf("out:" + spec.prefix, (n, oh * ow, c), F32)
-            phases = getattr(ops, "conv3x3_up_phases", None)
-            if phases is not None and c % 160 == 0 and env_flag("SEVA_UPSAMPLE_PHASES", "not0", True):  # (read at every call)
-                # four 2x2 phase convs on the source image: 4/9 of the FLOPs.  The path emits no statistics (a 64-row block of one
-                # phase is not image-aligned), so the consuming GroupNorm runs its own pass over this tensor
-                st_out = None
-                phases(x16, self.W[spec.prefix + ".w4"], bias=self.W[spec.prefix + ".b"], out_f32=out, ch_stats=None, alg_k=9 * c)
-            else:
-                st_out = self._stats_buf("out:" + spec.prefix, n * oh * ow, oh * ow, c)
-                ops.conv3x3(x16, self.W[spec.prefix + ".w"], upsample=True, bias=self.W[spec.prefix + ".b"], out_f32=out,
-                            ch_stats=st_out, alg_k=alg_k)
-        self._produced(out, st_out)
-        return out, oh, ow
+            out = self._out32("out:" + spec.prefix, n, oh, ow, c)
+            ops.conv3x3(x16, self.W[spec.prefix + ".w"], upsample=True, bias=self.W[spec.prefix + ".b"], **out.dst, alg_k=alg_k)
+        return out
 
     # ------------------------------------------------------------------ graph replay
     @torch.no_grad()
@@ -877,7 +881,7 @@ class SevaEngine(_EngineBase):
         return self._shallow_m[levels - 1]
 
     def _shallow_entry(self, levels: int, sig: tuple):
-        """The guard of a shallow call: (tensor, h, w, statistics) that the last full call left for depth `levels`, or
+        """The guard of a shallow call: the `Act` (tensor and statistics) that the last full call left for depth `levels`, or
         SevaNativeError when that call was not one of this signature -- never a buffer the engine cannot vouch for."""
         self.shallow_input_blocks(levels)
         last = self._last_full
@@ -926,7 +930,6 @@ class SevaEngine(_EngineBase):
             entries: dict = {}
             enters = {m + 1: k + 1 for k, m in enumerate(self._shallow_m)}  # output blocks left to run -> the depth that enters there
         self.gn_ws = self._buf("gn_ws", (n * ops.GN_WORKSPACE_SLABS * 32 * 2,), F32)
-        self._stats = {}
 
         # --- prologue: timestep embedding MLP, all ResBlock emb projections, folded cross-attn ---
         audit_mark("time_embed")
@@ -967,40 +970,33 @@ class SevaEngine(_EngineBase):
         cpad = CIN_PAD * (((2 if sp_stem else 1) * cin + CIN_PAD - 1) // CIN_PAD)
         x16 = self._buf("x16", (n, h, w, cpad), F16)
         ops.nchw_to_nhwc_f16(x, concat, x16, split=sp_stem)
-        cur = self._buf("out:" + stem.prefix, (n, h * w, stem.cout), F32)
-        st_stem = self._stats_buf("out:" + stem.prefix, n * h * w, h * w, stem.cout)
-        ops.conv3x3(x16, W[stem.prefix + ".w"], bias=W[stem.prefix + ".b"], out_f32=cur, ch_stats=st_stem,
+        cur = self._out32("out:" + stem.prefix, n, h, w, stem.cout)
+        ops.conv3x3(x16, W[stem.prefix + ".w"], bias=W[stem.prefix + ".b"], **cur.dst,
                     alg_k=9 * cin)  # (profiling counts the reference's 11 input channels, not the padded / split 64)
-        self._produced(cur, st_stem)
-        ch, cw = h, w
-        hs = [(cur, ch, cw)]
+        hs = [cur]
 
-        def run(block, cur, x2, ch, cw):
+        def run(block, cur, x2):
             for spec in block:
                 if spec.kind == "res":
-                    cur = self._resblock(spec, cur, x2, n, ch, cw, dense_at(ch, cw), emb_all)
+                    cur = self._resblock(spec, cur, x2, dense_at(cur.h, cur.w), emb_all)
                     x2 = None
                 elif spec.kind == "mvt":
-                    cur = self._transformer(spec, cur, n, ch, cw, T, ctxvec, ctx16, lc)
+                    cur = self._transformer(spec, cur, T, ctxvec, ctx16, lc)
                 else:
-                    cur, ch, cw = self._resample(spec, cur, n, ch, cw)
-            return cur, ch, cw
+                    cur = self._resample(spec, cur)
+            return cur
 
         nout = len(lay.output_blocks)
         for block in lay.input_blocks[1:1 + m_in] if L else lay.input_blocks[1:]:
-            cur, ch, cw = run(block, cur, None, ch, cw)
-            hs.append((cur, ch, cw))
-        if L:
-            cur, ch, cw, st_in = entry
-            self._produced(cur, st_in)  # (`_stats` was cleared above: the producer's statistics travel with the reused tensor)
-        else:
-            cur, ch, cw = run(lay.middle, cur, None, ch, cw)
+            cur = run(block, cur, None)
+            hs.append(cur)
+        cur = entry if L else run(lay.middle, cur, None)  # (a reused tensor arrives with its producer's statistics)
         for k in range(nout - (m_in + 1) if L else 0, nout):
             if not L and nout - k in enters:
-                entries[enters[nout - k]] = (cur, ch, cw, self._stats.get(cur.data_ptr()))
-            skip, sh, sw = hs.pop()
-            assert (sh, sw) == (ch, cw)
-            cur, ch, cw = run(lay.output_blocks[k], cur, skip, ch, cw)
+                entries[enters[nout - k]] = cur
+            skip = hs.pop()
+            assert (skip.h, skip.w) == (cur.h, cur.w)
+            cur = run(lay.output_blocks[k], cur, skip)
         assert not hs
 
         # --- head: GroupNorm + SiLU + conv3x3 (model.py:170-174) ---
@@ -1008,13 +1004,12 @@ class SevaEngine(_EngineBase):
         cfin = lay.final_channels
         sp_head = "head" in self.split
         cf2 = (2 if sp_head else 1) * cfin
-        g16 = self._buf("gn16", (n, ch * cw, cf2), F16)
-        ops.groupnorm(cur, None, W["out.0.g"], W["out.0.b"], g16, self.gn_ws, eps=1e-5, silu=True,
-                      stats1=self._gn_stats(cur)[0], split_out=sp_head)
-        o_nhwc = self._buf("head", (n, ch * cw, p.out_channels), F32)
-        ops.conv3x3(g16.view(n, ch, cw, cf2), W["out.2.w"], bias=W["out.2.b"], out_f32=o_nhwc, alg_k=9 * cfin)
+        g16 = self._buf("gn16", (n, cur.hw, cf2), F16)
+        self._groupnorm(cur, None, W["out.0.g"], W["out.0.b"], g16, eps=1e-5, silu=True, split_out=sp_head)
+        o_nhwc = self._buf("head", (n, cur.hw, p.out_channels), F32)
+        ops.conv3x3(g16.view(n, cur.h, cur.w, cf2), W["out.2.w"], bias=W["out.2.b"], out_f32=o_nhwc, alg_k=9 * cfin)
         if out is None:
-            out = torch.empty((n, p.out_channels, ch, cw), dtype=F32, device=self.device)
+            out = torch.empty((n, p.out_channels, cur.h, cur.w), dtype=F32, device=self.device)
         ops.nhwc_to_nchw_f32(o_nhwc, out)
         if not L:
             self._shallow_entries[sig] = entries

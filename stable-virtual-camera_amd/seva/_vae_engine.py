@@ -20,7 +20,7 @@ import os
 import torch
 
 from . import audit, ops
-from ._engine import CIN_PAD, _EngineBase, combine_up_phases, env_flag, pack_conv3x3
+from ._engine import CIN_PAD, Act, _EngineBase, combine_up_phases, env_flag, pack_conv3x3
 from ._native import require_cuda
 from .ops import audit_mark  # (bound here: the tests' seam swaps this module's `ops`)
 
@@ -171,6 +171,7 @@ class _VaeEngineBase(_EngineBase):
     PREFIXES: tuple = ()       # state_dict key prefixes this half owns
     CONV_IN = CONV_OUT = ""    # first conv (input channels padded to 64) / last conv (handled by the subclass)
 
+    _ops = property(lambda self: ops)  # (this module's `ops`)
     _w8: dict = {}  # e4m3 conv weights of the running decode / encode (fp8 precision), else empty
 
     def __init__(self, weights):
@@ -224,8 +225,9 @@ class _VaeEngineBase(_EngineBase):
         self.W = W
         self._pack_ends(sd, conv3)
 
-    def _resnet(self, p, x, n, h, w, cin, cout, f16_out=None, f8_out=None):
-        """diffusers ResnetBlock2D (no time embedding): GN-SiLU-conv-GN-SiLU-conv + shortcut.
+    def _resnet(self, p, x: Act, cout, f16_out=None, f8_out=None):
+        """diffusers ResnetBlock2D (no time embedding): GN-SiLU-conv-GN-SiLU-conv + shortcut; returns the `Act`, or with f16_out /
+        f8_out that buffer (a resampling conv's operand, no stream tensor).
         f16_out: the block's only consumer is a resampling conv (A operand = f16): the second conv's epilogue rounds
         `conv + shortcut` straight into that buffer -- the same rounding the separate cast pass made -- and the fp32 tensor
         (4 B written, 4 B read back per element at up to 576 x 576 x 256) is never formed.  The shortcut conv's f16 input comes
@@ -233,27 +235,25 @@ class _VaeEngineBase(_EngineBase):
         fp8 decode / encode: a conv with e4m3 weights in `self._w8` reads the e4m3 output of its GroupNorm; f8_out is f16_out's
         e4m3 twin (the upsample / downsample conv's A operand, written by the e4m3 conv2's epilogue, saturating)."""
         audit_mark(p)
-        W, W8, hw = self.W, self._w8, h * w
+        W, W8 = self.W, self._w8
+        n, h, w, hw, cin = x.n, x.h, x.w, x.hw, x.c
         f8_1, f8_2 = p + ".conv1.w8" in W8, p + ".conv2.w8" in W8
         assert f8_out is None or f8_2
         a16 = None if f8_1 else self._buf("gn16", (n, hw, cin), F16)
         a8 = self._buf("gn8", (n, hw, cin), U8) if f8_1 else None
         xs16 = self._buf("v_sk16", (n * hw, cin), F16) if cin != cout else None
-        ops.groupnorm(x, None, W[p + ".norm1.g"], W[p + ".norm1.b"], a16, self.gn_ws, eps=1e-6, silu=True,
-                      stats1=self._gn_stats(x)[0], raw_f16=None if xs16 is None else xs16.view(n, hw, cin), out_f8=a8)
-        mid = self._buf("v_mid", (n, hw, cout), F32)
-        st_mid = self._stats_buf("v_mid", n * hw, hw, cout)
+        self._groupnorm(x, None, W[p + ".norm1.g"], W[p + ".norm1.b"], a16, eps=1e-6, silu=True,
+                        raw_f16=None if xs16 is None else xs16.view(n, hw, cin), out_f8=a8)
+        mid = self._out32("v_mid", n, h, w, cout)
         if f8_1:
-            ops.conv3x3(a8.view(n, h, w, cin), W8[p + ".conv1.w8"], w_exp=W8[p + ".conv1.w8e"], bias=W[p + ".conv1.b"], out_f32=mid,
-                        ch_stats=st_mid)
+            ops.conv3x3(a8.view(n, h, w, cin), W8[p + ".conv1.w8"], w_exp=W8[p + ".conv1.w8e"], bias=W[p + ".conv1.b"], **mid.dst)
         else:
-            ops.conv3x3(a16.view(n, h, w, cin), W[p + ".conv1.w"], bias=W[p + ".conv1.b"], out_f32=mid, ch_stats=st_mid)
+            ops.conv3x3(a16.view(n, h, w, cin), W[p + ".conv1.w"], bias=W[p + ".conv1.b"], **mid.dst)
         b16 = None if f8_2 else self._buf("gn16", (n, hw, cout), F16)
         b8 = self._buf("gn8", (n, hw, cout), U8) if f8_2 else None
-        ops.groupnorm(mid, None, W[p + ".norm2.g"], W[p + ".norm2.b"], b16, self.gn_ws, eps=1e-6, silu=True, stats1=st_mid,
-                      out_f8=b8)
+        self._groupnorm(mid, None, W[p + ".norm2.g"], W[p + ".norm2.b"], b16, eps=1e-6, silu=True, out_f8=b8)
         # conv2 + shortcut, in e4m3 or f16, into the one tensor its consumer reads
-        xb, w2, e2, b2, res, a2 = b16, W[p + ".conv2.w"], None, W[p + ".conv2.b"], x, None
+        xb, w2, e2, b2, res, a2 = b16, W[p + ".conv2.w"], None, W[p + ".conv2.b"], x.t, None
         if f8_2:  # (never a channel-changing resnet: its folded shortcut is f16-only)
             assert cin == cout
             xb, w2, e2 = b8, W8[p + ".conv2.w8"], W8[p + ".conv2.w8e"]
@@ -268,23 +268,21 @@ class _VaeEngineBase(_EngineBase):
         elif f16_out is not None:
             out, dst = f16_out, {"out_f16": f16_out.view(n, hw, cout)}
         else:
-            out = self._buf("out:" + p, (n, hw, cout), F32)
-            st_out = self._stats_buf("out:" + p, n * hw, hw, cout)
-            dst = {"out_f32": out, "ch_stats": st_out}
-            self._produced(out, st_out)
+            out = self._out32("out:" + p, n, h, w, cout)
+            dst = out.dst
         ops.conv3x3(xb.view(n, h, w, cout), w2, w_exp=e2, bias=b2, residual=res, a2=a2, **dst)
         return out
 
-    def _attention(self, p, x, n, h, w, c):
+    def _attention(self, p, x: Act) -> Act:
         """Single-head self-attention over h*w tokens of dim c (diffusers Attention in the VAE mid block)."""
         audit_mark(p)
-        W, hw = self.W, h * w
+        W = self.W
+        n, h, w, hw, c = x.n, x.h, x.w, x.hw, x.c
         if hw % 4:
             raise ValueError(f"VAE attention needs h*w % 4 == 0 (got {h}x{w}); latents are multiples of 8 per side")
         hw_pad = 64 * ((hw + 63) // 64)
         g16 = self._buf("gn16", (n, hw, c), F16)
-        ops.groupnorm(x, None, W[p + ".group_norm.g"], W[p + ".group_norm.b"], g16, self.gn_ws, eps=1e-6, silu=False,
-                      stats1=self._gn_stats(x)[0])
+        self._groupnorm(x, None, W[p + ".group_norm.g"], W[p + ".group_norm.b"], g16, eps=1e-6, silu=False)
         q = self._buf("v_q", (n * hw, c), F16)
         k = self._buf("v_k", (n * hw, c), F16)
         ops.gemm(g16.view(n * hw, c), W[p + ".to_q.w"], bias=W[p + ".to_q.b"], out_f16=q)
@@ -299,11 +297,8 @@ class _VaeEngineBase(_EngineBase):
             ops.gemm(q[i * hw:(i + 1) * hw], k[i * hw:(i + 1) * hw], out_f32=sc)
             ops.softmax_rows(sc, pr, hw, 1.0 / (c**0.5))
             ops.gemm(pr, vT, bias=W[p + ".to_v.b"], out_f16=att[i * hw:(i + 1) * hw])
-        out = self._buf("out:" + p, (n, hw, c), F32)
-        st_out = self._stats_buf("out:" + p, n * hw, hw, c)
-        ops.gemm(att, W[p + ".to_out.0.w"], bias=W[p + ".to_out.0.b"], residual=x.view(n * hw, c),
-                 out_f32=out.view(n * hw, c), ch_stats=st_out)
-        self._produced(out, st_out)
+        out = self._out32("out:" + p, n, h, w, c)
+        ops.gemm(att, W[p + ".to_out.0.w"], bias=W[p + ".to_out.0.b"], residual=x.t2, **out.dst2)
         return out
 
 
@@ -359,7 +354,6 @@ class VaeDecoderEngine(_VaeEngineBase):
         if cz != self.latent:
             raise ValueError(f"expected {self.latent} latent channels, got {cz}")
         self.gn_ws = self._buf("gn_ws", (n * ops.GN_WORKSPACE_SLABS * 32 * 2,), F32)
-        self._stats = {}
         self._w8 = W8 = self.fp8_weights() if check_vae_precision(self.precision) == "fp8" else {}
         # the upsample convs as four 2x2 phase convs (4/9 of the FLOPs), where the operator exists: the f16 ones only
         phases = getattr(ops, "conv3x3_up_phases128", None) if check_vae_upsample(self.upsample) == "phases" else None
@@ -371,15 +365,12 @@ class VaeDecoderEngine(_VaeEngineBase):
         ops.gemm(z16.view(n * h * w, CIN_PAD), W["post_quant_conv.w"], bias=W["post_quant_conv.b"], out_f16=pq)
         top = self.block_out[-1]
         audit_mark("decoder.conv_in")
-        x = self._buf("out:conv_in", (n, h * w, top), F32)
-        st = self._stats_buf("out:conv_in", n * h * w, h * w, top)
-        ops.conv3x3(pq.view(n, h, w, CIN_PAD), W["decoder.conv_in.w"], bias=W["decoder.conv_in.b"], out_f32=x, ch_stats=st)
-        self._produced(x, st)
-        x = self._resnet("decoder.mid_block.resnets.0", x, n, h, w, top, top)
-        x = self._attention("decoder.mid_block.attentions.0", x, n, h, w, top)
-        x = self._resnet("decoder.mid_block.resnets.1", x, n, h, w, top, top)
+        x = self._out32("out:conv_in", n, h, w, top)
+        ops.conv3x3(pq.view(n, h, w, CIN_PAD), W["decoder.conv_in.w"], bias=W["decoder.conv_in.b"], **x.dst)
+        x = self._resnet("decoder.mid_block.resnets.0", x, top)
+        x = self._attention("decoder.mid_block.attentions.0", x)
+        x = self._resnet("decoder.mid_block.resnets.1", x, top)
         rev = list(reversed(self.block_out))
-        cin = rev[0]
         for i, cout in enumerate(rev):
             up = i != len(rev) - 1
             p = f"decoder.up_blocks.{i}.upsamplers.0.conv"
@@ -388,30 +379,26 @@ class VaeDecoderEngine(_VaeEngineBase):
             x16 = self._buf("v_up16", (n, h, w, cout), F16) if up and not up8 else None
             x8 = self._buf("v_up8", (n, h, w, cout), U8) if up8 else None
             for j in range(3):
-                x = self._resnet(f"decoder.up_blocks.{i}.resnets.{j}", x, n, h, w, cin if j == 0 else cout, cout,
+                x = self._resnet(f"decoder.up_blocks.{i}.resnets.{j}", x, cout,
                                  f16_out=x16 if j == 2 else None, f8_out=x8 if j == 2 else None)
-            cin = cout
             if up:
                 h, w = 2 * h, 2 * w
                 audit_mark(p)
-                x = self._buf("out:" + p, (n, h * w, cout), F32)
-                st = self._stats_buf("out:" + p, n * h * w, h * w, cout)
+                x = self._out32("out:" + p, n, h, w, cout)
                 if up8:
-                    ops.conv3x3(x8, W8[p + ".w8"], w_exp=W8[p + ".w8e"], upsample=True, bias=W[p + ".b"], out_f32=x, ch_stats=st)
+                    ops.conv3x3(x8, W8[p + ".w8"], w_exp=W8[p + ".w8e"], upsample=True, bias=W[p + ".b"], **x.dst)
                 elif p + ".w4" in W4 and up_phases128_applies(h // 2, w // 2):  # (a per-image rule; else the nine taps)
                     # statistics as for the nine taps, where a block of 64 source pixels of one phase stays inside an image (every latent
                     # whose sides are multiples of 8); else the consuming GroupNorm runs its own pass
                     if (h * w // 4) % ops.STATS_ROWS:
-                        st = None
-                    phases(x16, W4[p + ".w4"], bias=W[p + ".b"], out_f32=x, ch_stats=st, alg_k=9 * cout)
+                        x.stats = None
+                    phases(x16, W4[p + ".w4"], bias=W[p + ".b"], **x.dst, alg_k=9 * cout)
                 else:
-                    ops.conv3x3(x16, W[p + ".w"], upsample=True, bias=W[p + ".b"], out_f32=x, ch_stats=st)
-                self._produced(x, st)
+                    ops.conv3x3(x16, W[p + ".w"], upsample=True, bias=W[p + ".b"], **x.dst)
         c = rev[-1]
         audit_mark("decoder.conv_norm_out")
         g16 = self._buf("gn16", (n, h * w, c), F16)
-        ops.groupnorm(x, None, W["decoder.conv_norm_out.g"], W["decoder.conv_norm_out.b"], g16, self.gn_ws,
-                      eps=1e-6, silu=True, stats1=self._gn_stats(x)[0])
+        self._groupnorm(x, None, W["decoder.conv_norm_out.g"], W["decoder.conv_norm_out.b"], g16, eps=1e-6, silu=True)
         o4 = self._buf("v_o4", (n, h * w, 4), F32)
         ops.conv3x3(g16.view(n, h, w, c), W["decoder.conv_out.w"], bias=W["decoder.conv_out.b"], out_f32=o4)
         out = torch.empty((n, self.out_channels, h, w), dtype=F32, device=self.device)
@@ -460,17 +447,13 @@ class VaeEncoderEngine(_VaeEngineBase):
         if h % (1 << nd) or w % (1 << nd):
             raise ValueError(f"VAE encode needs H and W divisible by {1 << nd} (got {h}x{w})")
         self.gn_ws = self._buf("gn_ws", (n * ops.GN_WORKSPACE_SLABS * 32 * 2,), F32)
-        self._stats = {}
         self._w8 = W8 = self.fp8_weights() if check_vae_precision(self.precision) == "fp8" else {}
         one = torch.ones((n,), dtype=F32, device=self.device)
         x16 = self._buf("v_x16", (n, h * w, CIN_PAD), F16)
         ops.nchw_to_nhwc_f16(x, None, x16, scale=one)  # channels-last, 3 -> 64 zero-padded channels
         c0 = self.block_out[0]
-        cur = self._buf("out:enc_in", (n, h * w, c0), F32)
-        st = self._stats_buf("out:enc_in", n * h * w, h * w, c0)
-        ops.conv3x3(x16.view(n, h, w, CIN_PAD), W["encoder.conv_in.w"], bias=W["encoder.conv_in.b"], out_f32=cur, ch_stats=st)
-        self._produced(cur, st)
-        cin = c0
+        cur = self._out32("out:enc_in", n, h, w, c0)
+        ops.conv3x3(x16.view(n, h, w, CIN_PAD), W["encoder.conv_in.w"], bias=W["encoder.conv_in.b"], **cur.dst)
         for i, cout in enumerate(self.block_out):
             p = f"encoder.down_blocks.{i}.downsamplers.0.conv"
             # e4m3 downsample conv (SEVA_VAE_FP8_DOWNSAMPLE=1): its A operand is written by the e4m3 epilogue of the second resnet's conv2
@@ -478,28 +461,23 @@ class VaeEncoderEngine(_VaeEngineBase):
             d16 = self._buf("v_dn16", (n, h, w, cout), F16) if i != nd and not dn8 else None
             d8 = self._buf("v_dn8", (n, h, w, cout), U8) if dn8 else None
             for j in range(2):
-                cur = self._resnet(f"encoder.down_blocks.{i}.resnets.{j}", cur, n, h, w, cin if j == 0 else cout, cout,
+                cur = self._resnet(f"encoder.down_blocks.{i}.resnets.{j}", cur, cout,
                                    f16_out=d16 if j == 1 else None, f8_out=d8 if j == 1 else None)
-            cin = cout
             if i != nd:
                 h, w = h // 2, w // 2
                 audit_mark(p)
-                cur = self._buf("out:" + p, (n, h * w, cout), F32)
-                st = self._stats_buf("out:" + p, n * h * w, h * w, cout)
+                cur = self._out32("out:" + p, n, h, w, cout)
                 if dn8:
-                    ops.conv3x3(d8, W8[p + ".w8"], w_exp=W8[p + ".w8e"], stride=2, pad_br_only=True, bias=W[p + ".b"], out_f32=cur,
-                                ch_stats=st)
+                    ops.conv3x3(d8, W8[p + ".w8"], w_exp=W8[p + ".w8e"], stride=2, pad_br_only=True, bias=W[p + ".b"], **cur.dst)
                 else:
-                    ops.conv3x3(d16, W[p + ".w"], stride=2, pad_br_only=True, bias=W[p + ".b"], out_f32=cur, ch_stats=st)
-                self._produced(cur, st)
+                    ops.conv3x3(d16, W[p + ".w"], stride=2, pad_br_only=True, bias=W[p + ".b"], **cur.dst)
         top = self.block_out[-1]
-        cur = self._resnet("encoder.mid_block.resnets.0", cur, n, h, w, top, top)
-        cur = self._attention("encoder.mid_block.attentions.0", cur, n, h, w, top)
-        cur = self._resnet("encoder.mid_block.resnets.1", cur, n, h, w, top, top)
+        cur = self._resnet("encoder.mid_block.resnets.0", cur, top)
+        cur = self._attention("encoder.mid_block.attentions.0", cur)
+        cur = self._resnet("encoder.mid_block.resnets.1", cur, top)
         audit_mark("encoder.conv_norm_out")
         g16 = self._buf("gn16", (n, h * w, top), F16)
-        ops.groupnorm(cur, None, W["encoder.conv_norm_out.g"], W["encoder.conv_norm_out.b"], g16, self.gn_ws,
-                      eps=1e-6, silu=True, stats1=self._gn_stats(cur)[0])
+        self._groupnorm(cur, None, W["encoder.conv_norm_out.g"], W["encoder.conv_norm_out.b"], g16, eps=1e-6, silu=True)
         o4 = self._buf("v_m4", (n, h * w, self.latent), F32)
         ops.conv3x3(g16.view(n, h, w, top), W["enc_out.w"], bias=W["enc_out.b"], out_f32=o4)
         out = torch.empty((n, self.latent, h, w), dtype=F32, device=self.device)

@@ -114,12 +114,12 @@ def test_engine_packs_phase_weights_and_keeps_the_nine_tap_call_on_fake_ops(monk
 
     wt = torch.randn(320, 320, 3, 3, generator=g) * 0.03
     eng.W.update({"upx.w": _engine.pack_conv3x3(wt), "upx.w4": _engine.combine_up_phases(wt), "upx.b": torch.randn(320, generator=g)})
-    xs = torch.randn(2, 6 * 4, 320, generator=g)
+    xs = _engine.Act(torch.randn(2, 6 * 4, 320, generator=g), 2, 6, 4)
     del seen[:]
-    o4, oh, ow = eng._resample(Spec, xs, 2, 6, 4)
-    o4 = o4.clone()
-    assert calls == [9 * 320] and not seen and (oh, ow) == (12, 8) and o4.data_ptr() not in eng._stats
+    o = eng._resample(Spec, xs)
+    o4 = o.t.clone()
+    assert calls == [9 * 320] and not seen and (o.h, o.w) == (12, 8) and o.stats is None
     monkeypatch.setenv("SEVA_UPSAMPLE_PHASES", "0")
-    o9, _, _ = eng._resample(Spec, xs, 2, 6, 4)
+    o9 = eng._resample(Spec, xs).t
     assert calls == [9 * 320] and seen == [True]
     assert rel_l2(o4, o9) < 1e-3  # f16 weight rounding only

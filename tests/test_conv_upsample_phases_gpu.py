@@ -194,17 +194,17 @@ def test_engine_takes_the_phase_path_by_default(dev, monkeypatch):
     eng = _engine.SevaEngine.__new__(_engine.SevaEngine)
     w = _rand((320, 320, 3, 3), dev, 4, 0.03)
     eng.W = {"up0.w": _engine.pack_conv3x3(w), "up0.w4": _engine.combine_up_phases(w), "up0.b": _rand((320,), dev, 5)}
-    eng._stats, eng.gn_fused_stats = {}, 1
+    eng.gn_fused_stats = 1
     bufs = {}
     eng._buf = lambda name, shape, dtype, zero=False: bufs.setdefault((name, tuple(shape), dtype), torch.zeros(tuple(shape), dtype=dtype, device=dev))
-    x = _rand((2, 16 * 16, 320), dev, 6)
+    x = _engine.Act(_rand((2, 16 * 16, 320), dev, 6), 2, 16, 16)
     monkeypatch.delenv("SEVA_UPSAMPLE_PHASES", raising=False)
-    o4, oh, ow = eng._resample(Spec, x, 2, 16, 16)
-    o4 = o4.clone()
-    assert calls == [9 * 320] and (oh, ow) == (32, 32) and not eng._stats
+    o = eng._resample(Spec, x)
+    o4 = o.t.clone()
+    assert calls == [9 * 320] and (o.h, o.w) == (32, 32) and o.stats is None
     monkeypatch.setenv("SEVA_UPSAMPLE_PHASES", "0")
-    o9, _, _ = eng._resample(Spec, x, 2, 16, 16)
-    assert calls == [9 * 320] and len(eng._stats) == 1  # the nine-tap conv emits the statistics (hw = 1024)
-    err = rel_l2(o4, o9)
+    o9 = eng._resample(Spec, x)
+    assert calls == [9 * 320] and o9.stats is not None  # the nine-tap conv emits the statistics (hw = 1024)
+    err = rel_l2(o4, o9.t)
     print(f"engine _resample 16 -> 32, 320 ch: phases vs nine-tap rel-L2 {err:.3e}")
     assert 0 < err < 1e-3

@@ -89,8 +89,9 @@ def test_shallow_call_on_the_same_inputs_is_the_full_call(counting, case):
     for L in (1, 2, 3):
         name = _entry_name(eng, L)
         (buf,) = [t for k, t in eng.arena.bufs.items() if k[0] == name]
-        tensor, h, w, stats = eng._shallow_entries[eng._last_full][L]
-        assert tensor is buf
+        entry = eng._shallow_entries[eng._last_full][L]
+        stats = entry.stats
+        assert entry.t is buf
         travelled += stats is not None
         before, st_before = buf.clone(), None if stats is None else stats.clone()
         del counting.calls[:]

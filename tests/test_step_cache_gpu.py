@@ -29,7 +29,8 @@ def _same_inputs(eng, args):
     full = eng.forward(*args).clone()
     assert torch.isfinite(full).all()
     for L in (1, 2, 3):
-        buf, _, _, stats = eng._shallow_entries[eng._last_full][L]
+        entry = eng._shallow_entries[eng._last_full][L]
+        buf, stats = entry.t, entry.stats
         # (the arena is shared by every shape this engine has run: one buffer of that name per shape)
         assert sum(t is buf for k, t in eng.arena.bufs.items() if k[0] == _entry_name(eng, L)) == 1
         before, st_before = buf.clone(), None if stats is None else stats.clone()
@@ -55,7 +56,7 @@ def test_shallow_call_on_the_same_inputs_is_the_full_call(dev, tiny, case):
             eng.gn_fused_stats = 2
         _same_inputs(eng, _to(args, dev))
         if case == "T2_32x32_stats2":
-            assert any(e[3] is not None for e in eng._shallow_entries[eng._last_full].values())  # statistics did travel
+            assert any(e.stats is not None for e in eng._shallow_entries[eng._last_full].values())  # statistics did travel
     finally:
         eng.gn_fused_stats = keep
 

@@ -191,6 +191,7 @@ def unet(tag):
 
 
 UNET_INPUTS = {"T3_8x24_lc1": (3, 8, 24, 1), "T2_8x8_lc3": (2, 8, 8, 3), "T3_96x96_lc1": (3, 96, 96, 1)}
+UNET_INPUTS_SHALLOW = {**UNET_INPUTS, "T2_16x16_lc1": (2, 16, 16, 1)}  # (`unet_record`'s default is every key of UNET_INPUTS)
 
 
 def unet_inputs(T, h, w, lc):
@@ -214,6 +215,40 @@ def unet_record(env, net="tiny", inputs=tuple(UNET_INPUTS), forward=True, **opts
                 lines += traced(lambda: eng.forward(inp["x"], None, inp["t"], inp["y"], inp["dense"], T),
                                 lambda: [("in", inp), ("W", eng.W), ("arena", eng.arena.bufs)])
             lines += [f"arena {k}" for k in eng.arena.bufs]
+    record(name, lines)
+
+
+SHALLOW_WITH_STATS = []  # (record, L) of every shallow call whose entering tensor came with its producer's statistics
+
+
+def unet_shallow_record(env, key):
+    """One engine under `env`: a full eager forward of input `key`, then the shallow forwards L = 1, 2, 3 of the same signature."""
+    name = f"unet[tiny] {env_tag(env)} shallow {key}"
+    with environment(env):
+        eng = _engine.SevaEngine(unet("tiny"))
+        inp, T = unet_inputs(*UNET_INPUTS_SHALLOW[key])
+        lines = attribute_lines(eng)
+        nout = len(eng.layout.output_blocks)
+        for L in (0, 1, 2, 3):
+            lines.append(f"input {key} shallow_levels={L}")
+            calls = traced(lambda: eng.forward(inp["x"], None, inp["t"], inp["y"], inp["dense"], T, shallow_levels=L),
+                           lambda: [("in", inp), ("W", eng.W), ("arena", eng.arena.bufs)])
+            lines += calls
+            if L:
+                # the arena buffer that enters the first output block this call runs: the last operator of the block before it
+                first = nout - (eng.shallow_input_blocks(L) + 1)
+                entry = "('out:" + eng.layout.output_blocks[first - 1][-1].prefix + "'"
+                reads = 0
+                for ln in calls:
+                    if ln.startswith("call seva_groupnorm_f16 "):
+                        f = dict(json.loads(ln.split(" ", 2)[2]))
+                        for x, st in (("x1", "stats1"), ("x2", "stats2")):
+                            if isinstance(f[x], list) and f[x][0] == "arena" and f[x][1].startswith(entry) and f[x][2] == 0:
+                                reads += 1
+                                if f[st]:
+                                    SHALLOW_WITH_STATS.append((name, L))
+                assert reads == 1, (name, L, reads)  # exactly one GroupNorm reads the entering tensor
+        lines += [f"arena {k}" for k in eng.arena.bufs]
     record(name, lines)
 
 
@@ -241,6 +276,9 @@ def unet_configurations():
             unet_record({sw: v}, forward=False, precision="fp8" if "FP8" in sw else None)
     for v in ("", "1", "2", "yes"):  # read at every `_resample` call: needs the forward ("0": above)
         unet_record({"SEVA_UPSAMPLE_PHASES": v}, net="phase", inputs=("T2_8x8_lc3",))
+    # shallow calls: where the default rule gives the entry points statistics, and a small input under the rule of the tests
+    unet_shallow_record({}, "T3_96x96_lc1")
+    unet_shallow_record({"SEVA_GN_FUSED_STATS": 2}, "T2_16x16_lc1")
 
 
 # ------------------------------------------------------------------------------------------------------------------ VAE, CLIP
@@ -523,6 +561,7 @@ def coverage():
         table[s] = seen(s)
     for s in ("seva_cfg_euler_f32", "seva_euler_step_f32", "seva_replace_blend_f32"):
         table[s] = seen(s)
+    table["shallow call, entry with stats"] = len(SHALLOW_WITH_STATS)  # a shallow call whose entering tensor came with statistics
     table["seva_cfg_multistep_f32 scale"] = seen("seva_cfg_multistep_f32", lambda r: field(r, "arg2"))
     table["seva_cfg_multistep_f32 no scale"] = seen("seva_cfg_multistep_f32", lambda r: not field(r, "arg2"))
     print("\ncoverage (recorded calls over all configurations)")
