@@ -548,8 +548,17 @@ __global__ __launch_bounds__(256, 2) void attn2_kernel(AttnArgs p) {
 // matrix load, and lower for v_mfma_f32_32x32x16 than for 16x16x32 -- the same FLOP took 653 ns against 553 ns in bare loops on random
 // data (1.63 against 1.97 GHz; tools/micro/pingpong_probe.hip, profiles/r04_pingpong_probe.log; MI355X guide, DVFS item 7), and
 // in this kernel MFMA time and VALU time ADD (same probe: neither SIMD partners nor one wave's own stream overlap them).
-// Same counts as attn2_kernel per 64 x 64 tile and wave: 8 K fragments, 8 V^T fragment pairs, 64 exp2, 32 packs, 32 dot2; 64 MFMAs of
-// 16 cycles instead of 32 of 32; the -m_run C-operand block is 4 registers per query block instead of 16.
+// Per 64 x 64 tile and wave: 8 K fragments, 8 V^T fragment pairs, 64 exp2, 32 packs as attn2_kernel; 72 MFMAs of 16 cycles instead of 32
+// of 32; the -m_run C-operand block is 4 registers per query block instead of 16.
+// The softmax row sums are 8 of the 72 MFMAs, not VALU work (attn2_kernel: 32 dot2 in four chains per block, their adds, two shuffles
+// per block after the loop): P^T, rounded to f16, is the B operand of the P.V product already, and against an A fragment of ONES that
+// product is sum_keys P of query i16 in every output row -- the full 64-key sum, in all four lanes of the query.  The steady-state
+// tile is about 115 VALU instructions beside 72 MFMAs (before: 160 beside 64), and since matrix and vector time ADD on this chip (see
+// above) the 128 matrix cycles buy more vector cycles than they cost (profiles/attention_rowsum.log).
+// ONE rare branch per tile: exp2 / pack / sums of all four blocks, then one wave-uniform test of the four sums against the bound.  Inside
+// it the decision stays per query block but as a select (delta = 0 leaves a block bit for bit as it was), and the scores come from the
+// K tile again: kept in registers for the branch, the 64 score registers no longer die into P and the kernel spills.  Tile 0, which
+// always sets the exponent reference, is its own instantiation of the body (FIRST) in front of the loop.
 //   S^T block (16 keys x 16 queries) = K(16 x 32 d) Q^T: lane (i16 = lane & 15, g = lane >> 4) holds keys 4g .. 4g+3 of query i16
 //   P^T as B operand of O^T(16 d x 16 queries) += V^T(16 d x 32 keys) P^T: the 32 keys of a step are two 16-key blocks in the order
 //   kappa = 8g + r <-> key 4g + r of block 2j, kappa = 8g + 4 + r <-> key 4g + r of block 2j + 1: a lane's B fragment is its own
@@ -601,16 +610,22 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
 #pragma unroll
     for (int d = 0; d < 4; ++d) acc_o[c][d] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  constexpr float P_SUM_BOUND = 16384.0f;  // a lane's partial row sum at or above 2^14: look at the maximum, rescale (as attn2_kernel)
+  // a query's 64-key row sum of one tile at or above 2^14: look at the maximum, rescale.  Still 2^14, attn2_kernel's bound on a lane's
+  // 16-key partial sum: the bound keeps P inside f16 with margin, and the full row's sum crosses it no later than any of its parts did.
+  constexpr float P_SUM_BOUND = 16384.0f;
 
   const int nt = (lk + KT - 1) / KT;
   Ring ring(kbase, vbase, p.k_sl, lk, smem, lane, wave);
   const int q4 = i16 >> 2, p4 = i16 & 3;
   typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
-  const fp16x2_t ones2 = {(__fp16)1.0f, (__fp16)1.0f};
+  half8_t ones8;  // the A fragment of the row-sum MFMAs
+#pragma unroll
+  for (int r = 0; r < 8; ++r) ones8[r] = (half_t)1.0f;
 
-  auto tile = [&](int buf, auto masked_c, int kt) {
+  // FIRST: tile 0 of this workgroup's keys, which always sets the exponent reference; the steady-state tile has no such case
+  auto tile = [&](int buf, auto masked_c, auto first_c, int kt) {
     constexpr bool MASKED = decltype(masked_c)::value;
+    constexpr bool FIRST = decltype(first_c)::value;
     const char* const lds_k = smem + buf * BUF_BYTES;
     const char* const lds_v = lds_k + KT * 128;
     const bool more2 = attn_ring_prefetch(kt, nt, buf, true, ring);
@@ -629,64 +644,108 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
             sc[c][kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[c][ks], ks == 0 ? neg_m[c] : sc[c][kb], 0, 0, 0);
         }
       }
-      // ---- online softmax per query block (attn2_kernel's: exp2 / pack / row sums first, the maximum only on the rare path) ----
+      // ---- online softmax per query block: exp2 / pack / row sums first, the maximum only on the rare path ----
       half8_t pf[NQ][NJ];
+      const auto mask_tail = [&](f32x4 (&s)[NKB]) {
 #pragma unroll
-      for (int c = 0; c < NQ; ++c) {
-        if (MASKED) {
+        for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
-          for (int kb = 0; kb < NKB; ++kb)
+          for (int r = 0; r < 4; ++r)
+            if (kt * KT + 16 * kb + 4 * g + r >= lk) s[kb][r] = -1e30f;
+      };
+      // P of query block c, rounded to f16, and its row sums ON THE MATRIX PIPE: with an A fragment of ones, the product that adds
+      // V^T P^T gives sum_keys P of query i16 in every row of its output block, so every lane holds in element 0 the 64-key sum of
+      // ITS query, taken from the rounded P (the quotient O / l loses nothing to the rounding: tests/test_output_rounding_gpu.py)
+      const auto exp_pack = [&](int c, const f32x4 (&s)[NKB]) {
+        f32x4 tl = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (kt * KT + 16 * kb + 4 * g + r >= lk) sc[c][kb][r] = -1e30f;
+        for (int j = 0; j < NJ; ++j) {
+          fp16x2_t pk[4];
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              const float e0 = __builtin_amdgcn_exp2f(s[2 * j + h][2 * e]);
+              const float e1 = __builtin_amdgcn_exp2f(s[2 * j + h][2 * e + 1]);
+              pk[2 * h + e] = pack_p(e0, e1);
+            }
+          pf[c][j] = __builtin_bit_cast(half8_t, pk);
+          tl = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones8, pf[c][j], tl, 0, 0, 0);
         }
-        float ls[4];
-        const auto exp_pack = [&]() {
-          ls[0] = ls[1] = ls[2] = ls[3] = 0.f;  // four partial sums: short dependent dot2 chains
+        return tl[0];
+      };
+      // the rare path of one query block, on its (masked) scores s: move the exponent reference to the block maximum, P and sums again
+      const auto new_reference = [&](int c, f32x4 (&s)[NKB], bool need) {
+        float mx = s[0][0];
 #pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            fp16x2_t pk[4];
+        for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
+          for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kb][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));  // the four lanes of a query: lane groups g = 0 .. 3
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float delta = FIRST ? mx : need ? fmaxf(mx, 0.f) : 0.f;
+        m_run[c] += delta;
 #pragma unroll
-              for (int e = 0; e < 2; ++e) {
-                const float e0 = __builtin_amdgcn_exp2f(sc[c][2 * j + h][2 * e]);
-                const float e1 = __builtin_amdgcn_exp2f(sc[c][2 * j + h][2 * e + 1]);
-                pk[2 * h + e] = pack_p(e0, e1);
-                ls[2 * h + e] = __builtin_amdgcn_fdot2(pk[2 * h + e], ones2, ls[2 * h + e], false);
-              }
-            pf[c][j] = __builtin_bit_cast(half8_t, pk);
-          }
-          return (ls[0] + ls[1]) + (ls[2] + ls[3]);
-        };
-        float tot = exp_pack();
-        const bool first = kt == 0;
-        if (__builtin_expect(first || __any(!(tot < P_SUM_BOUND)), 0)) {  // wave-uniform, rare (NaN / inf sums land here too)
-          float mx = sc[c][0][0];
-#pragma unroll
-          for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[c][kb][r]);
-          mx = fmaxf(mx, __shfl_xor(mx, 16, 64));  // the four lanes of a query: lane groups g = 0 .. 3
-          mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-          const float delta = first ? mx : fmaxf(mx, 0.f);
-          const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);
-          m_run[c] += delta;
+        for (int r = 0; r < 4; ++r) neg_m[c][r] = -m_run[c];
+        if (!FIRST) {  // (tile 0: l_run and acc_o are zero)
+          const float alpha = __builtin_amdgcn_exp2f(-delta);
           l_run[c] *= alpha;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) neg_m[c][r] = -m_run[c];
 #pragma unroll
           for (int d = 0; d < 4; ++d)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc_o[c][d][r] *= alpha;
-#pragma unroll
-          for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sc[c][kb][r] -= delta;
-          tot = exp_pack();
         }
-        l_run[c] += tot;
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s[kb][r] -= delta;
+        return exp_pack(c, s);
+      };
+      float tot[NQ];
+      if (FIRST) {
+#pragma unroll
+        for (int c = 0; c < NQ; ++c) {
+          if (MASKED) mask_tail(sc[c]);
+          tot[c] = new_reference(c, sc[c], true);
+        }
+      } else {
+        // all four blocks first (block c's row-sum MFMAs finish under block c + 1's exponentials), then ONE wave-uniform test.  The
+        // scores die into P block by block, as they always did: kept for the rare path they would cost 64 registers more than the two
+        // workgroups per CU leave.
+        bool over = false;
+#pragma unroll
+        for (int c = 0; c < NQ; ++c) {
+          if (MASKED) mask_tail(sc[c]);
+          tot[c] = exp_pack(c, sc[c]);
+          if (c > 0) over |= !(tot[c - 1] < P_SUM_BOUND);  // (one block behind: its MFMAs have finished)
+          __builtin_amdgcn_sched_barrier(0);  // block by block: mixed freely, the four blocks' temporaries do not fit in 256 registers
+        }
+        over |= !(tot[NQ - 1] < P_SUM_BOUND);
+        if (__builtin_expect(__any(over), 0)) {  // wave-uniform, rare (NaN / inf sums land here too)
+          // The decision stays per query block and wave-uniform, but as a select, not a branch (four more branches with the accumulators
+          // live across them, and hipcc spills the accumulators in EVERY tile): a block whose own sums were below the bound gets
+          // delta = 0, alpha = 1, which leaves its reference, accumulators, P and sums bit for bit as they were.
+#pragma unroll
+          for (int c = 0; c < NQ; ++c) {
+            const bool need = __any(!(tot[c] < P_SUM_BOUND));
+            // the block's scores again, from the K tile (still in LDS) and the old reference: the same MFMAs, the same bits
+            f32x4 s1[NKB];
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb) {
+              const int krow = 16 * kb + i16;
+#pragma unroll
+              for (int ks = 0; ks < 2; ++ks) {
+                const half8_t kf = *(const half8_t*)(lds_k + krow * 128 + (k_chunk_swz(krow, 4 * ks + g) << 4));
+                s1[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[c][ks], ks == 0 ? neg_m[c] : s1[kb], 0, 0, 0);
+              }
+            }
+            if (MASKED) mask_tail(s1);
+            tot[c] = new_reference(c, s1, need);
+          }
+        }
       }
+#pragma unroll
+      for (int c = 0; c < NQ; ++c) l_run[c] += tot[c];
       // ---- O^T += V^T P^T for the four query blocks off ONE V^T fragment ----
       // all eight V^T fragments are ISSUED before the first MFMA (the scores' registers are free by now): read one pair ahead, as hipcc
       // orders them, every group of eight MFMAs waits for its LDS round trip.  Same-box A/B (profiles/r04_kattn16.log): per-frame
@@ -714,21 +773,20 @@ __global__ __launch_bounds__(256, 2) void attn16_kernel(AttnArgs p) {
   };
   attn_ring_start<Ring::G>(nt, ring, qf);
   const int nfull = lk / KT;
-  int buf = 0;
-  for (int kt = 0; kt < nfull; ++kt) {
-    tile(buf, std::false_type{}, kt);
+  // tile 0 (buffer 0) on its own: the only one that always sets the exponent reference.  nt == 1 with a ragged tile: masked AND first
+  if (nfull > 0) tile(0, std::false_type{}, std::true_type{}, 0);
+  else tile(0, std::true_type{}, std::true_type{}, 0);
+  int buf = 1;
+  for (int kt = 1; kt < nfull; ++kt) {
+    tile(buf, std::false_type{}, std::false_type{}, kt);
     buf = buf == 2 ? 0 : buf + 1;
   }
-  if (nfull < nt) tile(buf, std::true_type{}, nfull);
+  if (nfull > 0 && nfull < nt) tile(buf, std::true_type{}, std::false_type{}, nfull);
 
+  // every lane of a query holds the full sums: nothing to exchange
   float l_tot[NQ];
 #pragma unroll
-  for (int c = 0; c < NQ; ++c) {
-    float l = l_run[c];
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    l_tot[c] = l;
-  }
+  for (int c = 0; c < NQ; ++c) l_tot[c] = l_run[c];
   if constexpr (SPLIT) {
     attn_write_partial16(p, w, wq0, acc_o, m_run, l_tot, i16, g);
     return;
