@@ -3,7 +3,9 @@
 // vectors, a tensor is read twice (statistics, apply) and written once as f16.
 //
 // GroupNorm statistics are deterministic: per-slab partial sums (fixed thread->element map, fixed
-// reduction order) are written to a workspace and combined in double precision by the apply kernel.
+// reduction order) are written to a workspace and combined in double precision by the finalize kernel.
+// The sums are taken about a per-(sample, group) pivot (load_pivot), so they stay near-fp32 accurate
+// whatever the ratio of a group's mean to its standard deviation.
 // The input may be the channel concatenation of two tensors (UNet skip concat), read in place.
 #include "seva_common.h"
 
@@ -66,8 +68,15 @@ __device__ __forceinline__ f32x4 load_quad(const GnArgs& p, int n, int pix, int 
   return *(const f32x4*)(p.x2 + ((int64_t)n * p.hw + pix) * p.c2 + (c - p.c1));
 }
 
+// The pivot of (sample n, group g): the sample's own pixel 0, first channel of the group.  The statistics pass sums x - pivot and
+// (x - pivot)^2, so what fp32 adds up is of the size of the group's spread, not of its offset: E[x^2] - mean^2 on the raw values
+// loses (mean / std)^2 of relative precision.  The same for every slab, re-read by gn_finalize_kernel; a function of the sample alone.
+__device__ __forceinline__ float load_pivot(const GnArgs& p, int n, int c) {
+  return c < p.c1 ? p.x1[(int64_t)n * p.hw * p.c1 + c] : p.x2[(int64_t)n * p.hw * p.c2 + (c - p.c1)];
+}
+
 __global__ __launch_bounds__(GN_MAX_THREADS) void gn_stats_kernel(GnArgs p) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];  // [pl_count][C] sums, then sumsq
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [pl_count][C] sums, then sumsq (both of x - pivot)
   const int C = p.c1 + p.c2;
   const GnMap mp(C);
   const int n = blockIdx.y, slab = blockIdx.x, nslab = gridDim.x;
@@ -76,12 +85,30 @@ __global__ __launch_bounds__(GN_MAX_THREADS) void gn_stats_kernel(GnArgs p) {
   float* const lsum = lds;
   float* const lsq = lds + mp.pl_count * C;
   if (mp.active) {
+    const int cpg = C / p.groups;
     for (int q = mp.q0; q < mp.cq; q += mp.qstep) {
+      // a quad may straddle groups (cpg = 10, 2): one pivot per channel; one division, then the group's first channel steps along.
+      // The four pivot loads and the first pixel's load are issued before the first first_read() (each one waits for its load),
+      // and the next pixel is always in flight: the pivots' latency is not added to the slab's.
+      f32x4 pv;
+      int c_first = q * 4 / cpg * cpg;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (q * 4 + r >= c_first + cpg) c_first += cpg;
+        pv[r] = load_pivot(p, n, c_first);
+      }
+      int pix = p_begin + mp.pl;
+      f32x4 nxt = {0.f, 0.f, 0.f, 0.f};
+      if (pix < p_end) nxt = load_quad(p, n, pix, q * 4);
+      pv = first_read(pv);
       f32x4 s = {0.f, 0.f, 0.f, 0.f}, ss = {0.f, 0.f, 0.f, 0.f};
-      for (int pix = p_begin + mp.pl; pix < p_end; pix += mp.pl_count) {
-        const f32x4 v = first_read(load_quad(p, n, pix, q * 4));  // (summed with packed adds: the first-reader rule, seva_common.h)
-        s += v;
-        ss += v * v;
+      while (pix < p_end) {
+        const f32x4 v = first_read(nxt);  // (summed with packed adds: the first-reader rule, seva_common.h)
+        pix += mp.pl_count;
+        if (pix < p_end) nxt = load_quad(p, n, pix, q * 4);
+        const f32x4 d = v - pv;
+        s += d;
+        ss += d * d;
       }
       *(f32x4*)(lsum + mp.pl * C + q * 4) = s;
       *(f32x4*)(lsq + mp.pl * C + q * 4) = ss;
@@ -109,6 +136,7 @@ __global__ void gn_finalize_kernel(GnArgs p) {
   // one wave per (sample, group): lane l takes slabs l, l + 64, ... in order, then a fixed xor-shuffle tree in fp64
   const int n = blockIdx.x, g = blockIdx.y, l = threadIdx.x;
   const int C = p.c1 + p.c2, cpg = C / p.groups;
+  const float pivot_raw = load_pivot(p, n, g * cpg);  // issued first: in flight under the slab loop
   double s = 0.0, ss = 0.0;
   for (int sl = l; sl < p.nslab_stats; sl += 64) {
     const float* o = p.ws + (((int64_t)n * p.nslab_stats + sl) * p.groups + g) * 2;
@@ -121,12 +149,14 @@ __global__ void gn_finalize_kernel(GnArgs p) {
     ss += __shfl_xor(ss, off, 64);
   }
   if (l != 0) return;
+  // the slab sums are of x - pivot (gn_stats_kernel): mean = pivot + E[d], var = E[d^2] - E[d]^2
+  const double pivot = (double)first_read(pivot_raw);
   const double cnt = (double)cpg * (double)p.hw;
-  const double mean = s / cnt;
-  double var = ss / cnt - mean * mean;
+  const double md = s / cnt;
+  double var = ss / cnt - md * md;
   if (var < 0.0) var = 0.0;
   float* f = p.ws + p.final_off + ((int64_t)n * p.groups + g) * 2;
-  f[0] = (float)mean;
+  f[0] = (float)(pivot + md);
   f[1] = (float)(1.0 / sqrt(var + (double)p.eps));
 }
 
