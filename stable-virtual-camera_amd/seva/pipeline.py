@@ -47,6 +47,7 @@ with `lpips=`).
 
 from __future__ import annotations
 
+import time
 from dataclasses import dataclass, field
 from typing import Callable, Sequence
 
@@ -56,7 +57,6 @@ import torch.distributed as dist
 
 from . import conditioning, planner
 from . import sampling as S
-from .distributed import shard_windows
 
 DEPENDENT_FIRST_PASS = ("gt-nearest", "gt-ltr")  # windows consume earlier windows' outputs (eval.py:530-616)
 
@@ -138,22 +138,6 @@ def plan_views(c2ws: torch.Tensor, input_ids: Sequence[int], T: int = 21, chunk_
     return TrajectoryPlan(T, ins, targets, w1, [], serial)
 
 
-def _per_pass(v):
-    """A scalar or a (first pass, second pass) pair -> the pair (the reference's `--T N,21`, `cfg 3,2`; eval.py:1785-1789)."""
-    if isinstance(v, (list, tuple)):
-        assert len(v) == 2, f"one value or a (first pass, second pass) pair, not {v!r}"
-        return v[0], v[1]
-    return v, v
-
-
-def _per_pass_interval(v):
-    """`guidance_interval` of the drivers -> the (first pass, second pass) pair: a 2-tuple whose elements are themselves (lo, hi)
-    tuples (or "lo,hi" strings) or None is that pair; anything else -- None, a string, a 2-tuple of numbers -- is one value for both."""
-    if isinstance(v, (list, tuple)) and len(v) == 2 and all(e is None or isinstance(e, (list, tuple, str)) for e in v):
-        return v[0], v[1]
-    return v, v
-
-
 def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int | Sequence[int] = 21, chunk_strategy: str = "interp",
                     first_pass_strategy: str = "gt-nearest", options: dict | None = None,
                     task: str = "img2trajvid", refine_anchors: bool = True,
@@ -187,7 +171,7 @@ def plan_trajectory(c2ws: torch.Tensor, input_ids: Sequence[int], T: int | Seque
     T = [int(t) for t in T] if isinstance(T, (list, tuple)) else int(T)
     vd = {"T": T, "options": opts}
     n_prior = planner.infer_prior_stats(T, len(ins), n - len(ins), vd)
-    T1, T2 = (int(t) for t in _per_pass(vd["T"]))
+    T1, T2 = (int(t) for t in S.per_pass(vd["T"]))
     if anchor_ids is None:
         anchors = [int(v) for v in planner.infer_prior_inds(c2ws, n_prior, ins, opts)]
     else:
@@ -233,8 +217,7 @@ _pair_groups: dict = {}
 
 
 def _now(device) -> float:
-    """Wall clock after the device has drained (per-window times of `run_trajectory(timers=...)`)."""
-    import time
+    """The drivers' one clock (`run_trajectory(timers=...)`: stages and windows): wall time after the device has drained."""
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     return time.perf_counter()
@@ -274,11 +257,12 @@ def run_window(win: Window, latents_of: dict, denoise_net: Callable, c2ws, Ks, *
                guidance_interval=None, guidance_rescale: float | None = None) -> torch.Tensor:
     """One window = the reference's get_value_dict + do_sample (eval.py:1152-1321) on this package's parts.
     `latents_of[frame_id]` -> (4,h,w) latent of every conditioning frame.  Returns the (T,4,h,w) sample.
-    `solver`: `EulerEDMSampler(solver=...)` ("euler", "dpmpp2m"; None = SEVA_SOLVER, default "euler").
-    `cache_interval`, `cache_levels`: `EulerEDMSampler(cache_interval=..., cache_levels=...)`, the opt-in reuse of deep UNet
-    features across steps (None = SEVA_CACHE_INTERVAL / SEVA_CACHE_LEVELS, default off).
-    `guidance_interval`, `guidance_rescale`: `EulerEDMSampler(guidance_interval=(sigma_lo, sigma_hi), guidance_rescale=phi)`, the
-    opt-in guidance controls (None = SEVA_GUIDANCE_INTERVAL / SEVA_GUIDANCE_RESCALE, default off)."""
+    The sampler options go to the window's `EulerEDMSampler` as they are, and its docstring describes them: `solver` ("euler",
+    "dpmpp2m"), `cache_interval` / `cache_levels` (the opt-in reuse of deep UNet features across steps), `guidance_interval` =
+    (sigma_lo, sigma_hi) / `guidance_rescale` = phi (the opt-in guidance controls).  None reads the option's SEVA_* variable
+    (`sampling.resolve_options`); everything is off by default."""
+    options = dict(solver=solver, cache_interval=cache_interval, cache_levels=cache_levels, guidance_interval=guidance_interval,
+                   guidance_rescale=guidance_rescale)
     T = len(win.slot_frame)
     h, w = hw
     frames = win.slot_frame
@@ -291,9 +275,7 @@ def run_window(win: Window, latents_of: dict, denoise_net: Callable, c2ws, Ks, *
     disc = S.DDPMDiscretization()
     den = S.DiscreteDenoiser(disc, num_idx=1000, device=device)
     g = [S.VanillaCFG(), S.MultiviewCFG(cfg_min), S.MultiviewTemporalCFG(T, cfg_min)][guider]
-    sampler = S.EulerEDMSampler(disc, g, num_steps=num_steps, verbose=False, device=device, s_churn=0.0,
-                                solver=solver, cache_interval=cache_interval, cache_levels=cache_levels,
-                                guidance_interval=guidance_interval, guidance_rescale=guidance_rescale)
+    sampler = S.EulerEDMSampler(disc, g, num_steps=num_steps, verbose=False, device=device, s_churn=0.0, **options)
     gen = torch.Generator(device=device)
     gen.manual_seed(int(step_seed))
     sampler.noise_fn = lambda x: torch.randn(x.shape, generator=gen, device=x.device, dtype=x.dtype)
@@ -303,6 +285,198 @@ def run_window(win: Window, latents_of: dict, denoise_net: Callable, c2ws, Ks, *
     kw = {} if guider == 0 else dict(c2w=vd["c2w"].to(device), K=Ks[frames].to(device), input_frame_mask=mask.to(device))
     return sampler(lambda x, s, c: den(denoise_net, x, s, c, num_frames=T), noise.to(device).clone(), scale=cfg,
                    cond=cond, uc=uc, verbose=False, **kw)
+
+
+@dataclass
+class _Trajectory:
+    """What the stages of `run_trajectory` share: one record per call, alike on every rank but for `rank`."""
+    plan: TrajectoryPlan
+    net: Callable                 # `denoise_net`
+    c2ws: torch.Tensor
+    Ks: torch.Tensor
+    hw: tuple                     # latent (h, w)
+    seed: int
+    device: torch.device
+    group: object
+    rank: int
+    world: int
+    timers: dict | None
+    ae: object
+    rgb_handoff: bool             # the hand-off goes decode -> encode through `ae`
+    conditioner: Callable | None
+    token: Callable               # a window's source ids -> its CLIP token
+    rgb_of: dict                  # frame id -> RGB, kept under `conditioner=` for the windows' tokens
+    latents_of: dict              # frame id -> the (4,h,w) latent that later windows condition on
+    noises: list                  # initial noise per window, in draw order (`Window.global_index`)
+    passes: tuple                 # per pass: the `run_window` keywords of its windows (cfg, guider, sampler options)
+    common: dict                  # the `run_window` keywords of every window
+    pairs: list = field(default_factory=list)  # `cfg_pair_groups` under cfg_split
+
+    @property
+    def split1(self) -> bool:
+        """serial strategies (and, under cfg_split, every one-window first pass): pair 0 = ranks (0, 1) splits the CFG batch of each window"""
+        return bool(self.pairs) and (self.plan.pass1_serial or len(self.plan.pass1) == 1)
+
+    @property
+    def keep_own(self) -> bool:
+        """one pass + RGB hand-off: a frame's OUTPUT is its own sample (the reference decodes it directly, `decode_output`); only
+        later windows see the re-encoded latent.  (Two passes keep the handed-off latent for anchors the second pass does not
+        regenerate.)"""
+        return self.rgb_handoff and not self.plan.pass2
+
+    def mark(self, name):
+        if self.timers is not None:
+            self.timers[name] = _now(self.device)
+
+
+def _token_rule(plan, device, clip_token, clip_fn, conditioner, input_rgb, ae, handoff):
+    """-> (a window's source ids -> its CLIP token, the `rgb_of` the rule reads: empty without a `conditioner`)"""
+    if conditioner is None:
+        assert clip_fn is not None or clip_token is not None, "a CLIP token (clip_token / clip_fn / conditioner) is required"
+        return ((lambda ids: clip_token) if clip_fn is None else clip_fn), {}
+    # the reference's rule (eval.py:1248): token of a window = mean CLIP embedding of its conditioning views' RGB
+    assert input_rgb is not None and ae is not None and handoff == "rgb", \
+        "conditioner= needs input_rgb=, ae= and handoff='rgb' (anchor RGB comes from the VAE decode between the passes)"
+    rgb_of = {fid: input_rgb[i].to(device) for i, fid in enumerate(plan.input_ids)}
+    return (lambda ids: conditioner(torch.stack([rgb_of[f] for f in ids])).mean(0)), rgb_of
+
+
+def _draw_noises(plan, seed, hw):
+    """initial noise: ONE CPU stream, seeded once per scene, drawn in plan order for EVERY window (eval.py:1294-1295,1450)"""
+    g0 = torch.Generator(device="cpu")
+    g0.manual_seed(seed)
+    return [torch.randn((len(win.slot_frame), 4, *hw), generator=g0) for win in plan.pass1 + plan.pass2]
+
+
+def first_pass_owner(plan: TrajectoryPlan, i: int, world: int, split1: bool) -> int:
+    """The rank that owns first-pass window i, that is, publishes its targets in the anchor exchange.  Rank 0 where the pass runs in
+    one place -- one process, a serial strategy, or `split1` (rank 1 of pair 0 runs every window too and holds the same bits, but
+    does not publish) -- and round-robin otherwise, as `distributed.shard_windows` deals windows."""
+    return 0 if (world == 1 or plan.pass1_serial or split1) else i % world
+
+
+def _run_one(run: _Trajectory, win: Window, ranks: tuple) -> torch.Tensor:
+    """`run_window` of `win` on this rank, with the window's own noise, step seed, token and pass settings; `ranks` = (q,): the whole
+    window, (2j, 2j+1): this rank's half of every CFG batch in pair j.  Appends (pass, index, seconds) to `timers["windows"]`."""
+    t0 = _now(run.device) if run.timers is not None else 0.0
+    # step seed = the per-window device stream: independent of rank and of execution order
+    z = run_window(win, run.latents_of, run.net, run.c2ws, run.Ks, noise=run.noises[win.global_index],
+                   step_seed=(run.seed * 1000003 + 7919 * (win.global_index + 1)) & 0x7FFFFFFFFFFF,
+                   clip_token=run.token(win.source_ids),
+                   cfg_split=(run.pairs[ranks[0] // 2], ranks.index(run.rank)) if len(ranks) == 2 else None,
+                   **run.passes[win.pass_id - 1], **run.common)
+    if run.timers is not None:
+        run.timers.setdefault("windows", []).append((win.pass_id, win.index, _now(run.device) - t0))
+    return z
+
+
+def _hand_off(run: _Trajectory, z, fids):
+    """(k,4,h,w) generated latents -> what the next window conditions on"""
+    if not run.rgb_handoff:
+        return z
+    rgb = run.ae.decode(z)
+    if run.conditioner is not None:
+        run.rgb_of.update(zip(fids, rgb))
+    return run.ae.encode(rgb)
+
+
+def _first_pass(run: _Trajectory) -> tuple:
+    """This rank's first-pass windows -> (handed-off latents, own samples under `keep_own`) of the targets it publishes."""
+    plan, split1 = run.plan, run.split1
+    pub_lat, pub_own = [], []
+    for i, win in enumerate(plan.pass1):
+        owner = first_pass_owner(plan, i, run.world, split1)
+        ranks = (0, 1) if split1 else (owner,)
+        if run.rank not in ranks:
+            continue
+        own = _run_one(run, win, ranks)[win.target_slots]
+        handed = _hand_off(run, own, win.target_ids)
+        run.latents_of.update(zip(win.target_ids, handed))  # a dependent strategy's next window on this rank may read it
+        if run.rank == owner:
+            pub_lat.extend(handed)
+            if run.keep_own:
+                pub_own.extend(own)
+    return pub_lat, pub_own
+
+
+def _exchange_anchors(run: _Trajectory, pub_lat: list, pub_own: list) -> dict:
+    """ONE all-gather of the first-pass targets into `latents_of` on every rank; under `keep_own` a second one, of the own samples
+    -> {frame id: own sample} (else {})."""
+    plan, world = run.plan, run.world
+    owner_ids = [[] for _ in range(world)]
+    for i, win in enumerate(plan.pass1):
+        owner_ids[first_pass_owner(plan, i, world, run.split1)].extend(win.target_ids)
+    counts = [len(ids) for ids in owner_ids]
+
+    def gathered(rows):
+        local = torch.stack(rows) if rows else torch.zeros((0, 4, *run.hw), device=run.device)
+        parts = _all_gather_padded(local.to(device=run.device, dtype=torch.float32), counts[run.rank], max(max(counts), 1), run.group)
+        return {fid: parts[r][j] for r in range(world) for j, fid in enumerate(owner_ids[r])}
+
+    run.latents_of.update(gathered(pub_lat))
+    own_of = gathered(pub_own) if run.keep_own else {}
+    if run.conditioner is not None and plan.pass2:
+        # ranks that did not generate an anchor need its RGB for the CLIP token: decode locally (1.66 MB of latents travelled, not
+        # 40 MB of RGB)
+        for fid in plan.anchor_ids:
+            if fid not in run.rgb_of:
+                run.rgb_of[fid] = run.ae.decode(run.latents_of[fid][None])[0]
+    return own_of
+
+
+def _second_pass(run: _Trajectory) -> tuple:
+    """Independent windows, sharded by `second_pass_schedule` -> (the schedule, {window index: sample} of this rank's windows)."""
+    sched = second_pass_schedule(len(run.plan.pass2), run.world, bool(run.pairs))
+    outs = {}
+    for rnd in sched:
+        for i, ranks in rnd:
+            if run.rank in ranks:
+                outs[i] = _run_one(run, run.plan.pass2[i], ranks)
+    return sched, outs
+
+
+def _gather(run: _Trajectory, sched: list, outs: dict) -> dict:
+    """The second-pass samples to rank 0, one `dist.gather` per round -> {window index: sample} there."""
+    rank, world = run.rank, run.world
+    collected = {}
+    for rnd in sched:
+        sender = {ranks[0]: i for i, ranks in rnd}  # a pair's even rank sends (both hold the same bits)
+        mine = outs.get(sender[rank]) if rank in sender else None
+        if world == 1:
+            if mine is not None:
+                collected[sender[rank]] = mine
+            continue
+        send = mine if mine is not None else torch.zeros((run.plan.T2, 4, *run.hw), device=run.device)
+        bufs = [torch.empty_like(send) for _ in range(world)] if rank == 0 else None
+        dist.gather(send.contiguous(), bufs, dst=0, group=run.group)
+        if rank == 0:
+            for rr, i in sender.items():
+                collected[i] = bufs[rr]
+    return collected
+
+
+def _assemble(run: _Trajectory, collected: dict, own_of: dict) -> dict:
+    """Rank 0: the frames in target order, optionally VAE-decoded -> the result of `run_trajectory`."""
+    plan, latents_of = run.plan, run.latents_of
+    n = run.c2ws.shape[0]
+    final = torch.zeros((n, 4, *run.hw), device=run.device)
+    filled = torch.zeros(n, dtype=torch.bool)
+    for fid in plan.input_ids + plan.anchor_ids:  # (anchors: first-pass samples, overwritten below when pass 2 regenerates them)
+        final[fid] = own_of.get(fid, latents_of[fid])
+        filled[fid] = True
+    for i, win in enumerate(plan.pass2):
+        z = collected[i]
+        for fid, slot in zip(win.target_ids, win.target_slots):
+            final[fid] = z[slot]
+            filled[fid] = True
+    assert bool(filled.all()), f"frames never generated: {torch.nonzero(~filled).flatten().tolist()}"
+    # "anchor_latents": what pass 2 conditioned on (first-pass samples after the hand-off), whether or not pass 2 regenerated them
+    res = {"latents": final, "frame_ids": list(range(n)), "plan": plan,
+           "anchor_latents": {fid: latents_of[fid] for fid in plan.anchor_ids}}
+    if run.ae is not None:
+        res["rgb"] = run.ae.decode(final)
+        run.mark("decode")
+    return res
 
 
 def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: torch.Tensor, Ks: torch.Tensor,
@@ -321,182 +495,51 @@ def run_trajectory(denoise_net: Callable, input_latents: torch.Tensor, c2ws: tor
     (`SGMWrapper(model)`); `input_latents` (n_in,4,h,w) are the VAE-encoded input views (x 0.18215), frame ids
     `input_ids` index `c2ws` (n,4,4) / `Ks` (n,3,3).  Returns, on rank 0, {"latents": (n,4,h,w) in frame order,
     "frame_ids", "plan", "anchor_latents" (first-pass anchors as pass 2 saw them), ["rgb"]}; other ranks get {"plan"} only.
-    `solver` goes to every window's sampler (`run_window`), and so do `cache_interval` / `cache_levels` (the opt-in reuse of deep
-    UNet features across steps), each one value or a (first pass, second pass) pair.  Likewise `guidance_interval` /
-    `guidance_rescale` (the opt-in guidance controls): one value or a pair; for the interval a pair is a 2-tuple whose elements are
-    themselves (lo, hi) tuples or None, and a 2-tuple of numbers is one interval for both passes.
+    The sampler options (`run_window` lists them) go to every window's sampler.  `solver` is one value; each of the others is one
+    value or a (first pass, second pass) pair, by the rule of `sampling.per_pass_options` (for `guidance_interval` a pair is a
+    2-tuple whose elements are themselves (lo, hi) tuples or None, and a 2-tuple of numbers is one interval for both passes).
     `T`, `cfg` and `guider` each take one value or a (first pass, second pass) pair, as the reference's `--T 96,21` /
     `cfg 3,2` do (eval.py:1785-1789, 1929-1933); `options` goes to the planner (`num_prior_frames_ratio`, ...).  A window
     is as long as its pass of the plan says (`plan.T1` / `plan.T2`): its noise draw, its guider and its network call.
-    `anchor_ids` goes to `plan_trajectory` (None: the planner's own anchors); with a ready `plan=` it is not read."""
+    `anchor_ids` goes to `plan_trajectory` (None: the planner's own anchors); with a ready `plan=` it is not read.
+    `timers`: a dictionary that receives the wall clock at the end of each stage below ("start", "pass1", "exchange", "pass2",
+    "gather", "decode") and "windows" = [(pass, index, seconds)] of this rank's windows."""
+    sampler_options = dict(solver=solver, cache_interval=cache_interval, cache_levels=cache_levels,
+                           guidance_interval=guidance_interval, guidance_rescale=guidance_rescale)
     rank, world = _rank_world(group)
     device = torch.device(device) if device is not None else input_latents.device
-    h, w = input_latents.shape[-2:]
+    hw = tuple(input_latents.shape[-2:])
     plan = plan or plan_trajectory(c2ws, input_ids, T, chunk_strategy, first_pass_strategy, options,
                                    refine_anchors=refine_anchors, anchor_ids=anchor_ids)
-    cfgs, guiders = _per_pass(cfg), _per_pass(guider)
-    cache_ns, cache_ls = _per_pass(cache_interval), _per_pass(cache_levels)
-    guide_ivs, guide_phis = _per_pass_interval(guidance_interval), _per_pass(guidance_rescale)
-    rgb_of: dict = {}
-    if conditioner is not None:
-        # the reference's rule (eval.py:1248): token of a window = mean CLIP embedding of its conditioning views' RGB
-        assert input_rgb is not None and ae is not None and handoff == "rgb", \
-            "conditioner= needs input_rgb=, ae= and handoff='rgb' (anchor RGB comes from the VAE decode between the passes)"
-        for i, fid in enumerate(plan.input_ids):
-            rgb_of[fid] = input_rgb[i].to(device)
-
-        def tok(ids):
-            return conditioner(torch.stack([rgb_of[f] for f in ids])).mean(0)
-    else:
-        tok = (lambda ids: clip_token) if clip_fn is None else clip_fn
-        assert clip_fn is not None or clip_token is not None, "a CLIP token (clip_token / clip_fn / conditioner) is required"
-
-    # initial noise: ONE CPU stream, seeded once per scene, drawn in plan order for EVERY window (eval.py:1294-1295,1450)
-    g0 = torch.Generator(device="cpu")
-    g0.manual_seed(int(seed))
-    noises =[torch.randn((len(win.slot_frame), 4, h, w), generator=g0) for win in plan.pass1 + plan.pass2]
-
-    def step_seed(win):  # per-window device stream: independent of rank and of execution order
-        return (int(seed) * 1000003 + 7919 * (win.global_index + 1)) & 0x7FFFFFFFFFFF
-
-    latents_of = {fid: input_latents[i].to(device) for i, fid in enumerate(plan.input_ids)}
-    common = dict(hw=(h, w), num_steps=num_steps, cfg_min=cfg_min, camera_scale=camera_scale,
-                  device=device, sampler_hook=sampler_hook, solver=solver)
-
-    def mark(name):
-        if timers is not None:
-            if device.type == "cuda":
-                torch.cuda.synchronize(device)
-            import time
-            timers[name] = time.perf_counter()
-
-    def handoff_latent(z, fids=None):  # (k,4,h,w) generated latents -> what the next window conditions on
-        if handoff == "rgb" and ae is not None:
-            rgb = ae.decode(z)
-            if conditioner is not None and fids is not None:
-                for fid, img in zip(fids, rgb):
-                    rgb_of[fid] = img
-            return ae.encode(rgb)
-        return z
-
-    mark("start")
-    pairs = cfg_pair_groups(group) if (cfg_split and world >= 2) else []
-    # ------------------------------------------------------------------ pass 1
-    # serial strategies (and, under cfg_split, every first pass): pair 0 = ranks (0, 1) splits the CFG batch of each window
-    split1 = bool(pairs) and (plan.pass1_serial or len(plan.pass1) == 1)
-    if split1:
-        mine1 = list(range(len(plan.pass1))) if rank < 2 else []
-    else:
-        mine1 = list(range(len(plan.pass1))) if world == 1 else (
-            ([i for i in range(len(plan.pass1))] if rank == 0 else []) if plan.pass1_serial
-            else shard_windows(len(plan.pass1), rank, world))
-    # one pass + RGB hand-off: a frame's OUTPUT is its own sample (the reference decodes it directly, `decode_output`); only later
-    # windows see the re-encoded latent.  (Two passes keep the handed-off latent for anchors the second pass does not regenerate.)
-    keep_own = handoff == "rgb" and ae is not None and not plan.pass2
-    got_ids, got_lat, got_own = [], [], []
-    for i in mine1:
-        win = plan.pass1[i]
-        t_w = _now(device) if timers is not None else 0.0
-        z = run_window(win, latents_of, denoise_net, c2ws, Ks, noise=noises[win.global_index], step_seed=step_seed(win),
-                       clip_token=tok(win.source_ids), cfg_split=(pairs[0], rank) if split1 else None,
-                       cfg=cfgs[0], guider=guiders[0], cache_interval=cache_ns[0], cache_levels=cache_ls[0],
-                       guidance_interval=guide_ivs[0], guidance_rescale=guide_phis[0], **common)
-        if timers is not None:
-            timers.setdefault("windows", []).append((1, i, _now(device) - t_w))
-        zt = handoff_latent(z[win.target_slots], win.target_ids)
-        for fid, lat, own in zip(win.target_ids, zt, z[win.target_slots]):
-            latents_of[fid] = lat  # a dependent strategy's next window on this rank may read it
-            if not (split1 and rank == 1):  # (rank 1 of the pair holds the same bits; rank 0 is the owner that publishes them)
-                got_ids.append(fid)
-                got_lat.append(lat)
-                if keep_own:
-                    got_own.append(own)
-    mark("pass1")
-    # ------------------------------------------------------------------ exchange: one all-gather of the anchors
-    counts = [0] * world
-    for i, win in enumerate(plan.pass1):
-        owner = 0 if (world == 1 or plan.pass1_serial or split1) else i % world
-        counts[owner] += len(win.target_ids)
-    local = torch.stack(got_lat) if got_lat else torch.zeros((0, 4, h, w), device=device)
-    parts = _all_gather_padded(local.to(device=device, dtype=torch.float32), counts[rank], max(max(counts), 1), group)
-    owner_ids = [[] for _ in range(world)]
-    for i, win in enumerate(plan.pass1):
-        owner_ids[0 if (world == 1 or plan.pass1_serial or split1) else i % world].extend(win.target_ids)
-    for r in range(world):
-        for j, fid in enumerate(owner_ids[r]):
-            latents_of[fid] = parts[r][j]
-    own_of = {}
-    if keep_own:
-        local = torch.stack(got_own) if got_own else torch.zeros((0, 4, h, w), device=device)
-        parts = _all_gather_padded(local.to(device=device, dtype=torch.float32), counts[rank], max(max(counts), 1), group)
-        own_of = {fid: parts[r][j] for r in range(world) for j, fid in enumerate(owner_ids[r])}
-    if conditioner is not None and plan.pass2:  # ranks that did not generate an anchor need its RGB for the CLIP token: decode locally (1.66 MB of
-        for fid in plan.anchor_ids:  # latents travelled, not 40 MB of RGB)
-            if fid not in rgb_of:
-                rgb_of[fid] = ae.decode(latents_of[fid][None])[0]
-    mark("exchange")
-    # ------------------------------------------------------------------ pass 2: independent windows, sharded
-    sched = second_pass_schedule(len(plan.pass2), world, bool(pairs))
-    outs = {}
-    for rnd in sched:
-        for i, ranks in rnd:
-            if rank not in ranks:
-                continue
-            win = plan.pass2[i]
-            t_w = _now(device) if timers is not None else 0.0
-            outs[i] = run_window(win, latents_of, denoise_net, c2ws, Ks, noise=noises[win.global_index],
-                                 step_seed=step_seed(win), clip_token=tok(win.source_ids),
-                                 cfg_split=(pairs[ranks[0] // 2], ranks.index(rank)) if len(ranks) == 2 else None,
-                                 cfg=cfgs[1], guider=guiders[1], cache_interval=cache_ns[1], cache_levels=cache_ls[1],
-                                 guidance_interval=guide_ivs[1], guidance_rescale=guide_phis[1], **common)
-            if timers is not None:
-                timers.setdefault("windows", []).append((2, i, _now(device) - t_w))
-    mark("pass2")
-    # ------------------------------------------------------------------ gather to rank 0, round by round
-    collected = {}
-    for rnd in sched:
-        sender = {ranks[0]: i for i, ranks in rnd}  # a pair's even rank sends (both hold the same bits)
-        mine = outs.get(sender[rank]) if rank in sender else None
-        if world == 1:
-            if mine is not None:
-                collected[sender[rank]] = mine
-            continue
-        send = mine if mine is not None else torch.zeros((plan.T2, 4, h, w), device=device)
-        bufs = [torch.empty_like(send) for _ in range(world)] if rank == 0 else None
-        dist.gather(send.contiguous(), bufs, dst=0, group=group)
-        if rank == 0:
-            for rr, i in sender.items():
-                collected[i] = bufs[rr]
-    mark("gather")
-    if rank != 0:
-        return {"plan": plan}
-    n = c2ws.shape[0]
-    final = torch.zeros((n, 4, h, w), device=device)
-    filled = torch.zeros(n, dtype=torch.bool)
-    for fid in plan.input_ids + plan.anchor_ids:  # (anchors: first-pass samples, overwritten below when pass 2 regenerates them)
-        final[fid] = own_of.get(fid, latents_of[fid])
-        filled[fid] = True
-    for i, win in enumerate(plan.pass2):
-        z = collected[i]
-        for fid, slot in zip(win.target_ids, win.target_slots):
-            final[fid] = z[slot]
-            filled[fid] = True
-    assert bool(filled.all()), f"frames never generated: {torch.nonzero(~filled).flatten().tolist()}"
-    # "anchor_latents": what pass 2 conditioned on (first-pass samples after the hand-off), whether or not pass 2 regenerated them
-    res = {"latents": final, "frame_ids": list(range(n)), "plan": plan,
-           "anchor_latents": {fid: latents_of[fid] for fid in plan.anchor_ids}}
-    if ae is not None:
-        res["rgb"] = ae.decode(final)
-        mark("decode")
-    return res
+    passes = tuple({"cfg": c, "guider": g, **o}
+                   for c, g, o in zip(S.per_pass(cfg), S.per_pass(guider), S.per_pass_options(**sampler_options)))
+    token, rgb_of = _token_rule(plan, device, clip_token, clip_fn, conditioner, input_rgb, ae, handoff)
+    run = _Trajectory(plan=plan, net=denoise_net, c2ws=c2ws, Ks=Ks, hw=hw, seed=int(seed), device=device, group=group, rank=rank,
+                      world=world, timers=timers, ae=ae, rgb_handoff=handoff == "rgb" and ae is not None, conditioner=conditioner,
+                      token=token, rgb_of=rgb_of, noises=_draw_noises(plan, int(seed), hw), passes=passes,
+                      latents_of={fid: input_latents[i].to(device) for i, fid in enumerate(plan.input_ids)},
+                      common=dict(hw=hw, num_steps=num_steps, cfg_min=cfg_min, camera_scale=camera_scale, device=device,
+                                  sampler_hook=sampler_hook))
+    run.mark("start")
+    if cfg_split and world >= 2:
+        run.pairs = cfg_pair_groups(group)
+    published = _first_pass(run)
+    run.mark("pass1")
+    own_of = _exchange_anchors(run, *published)
+    run.mark("exchange")
+    sched, outs = _second_pass(run)
+    run.mark("pass2")
+    collected = _gather(run, sched, outs)
+    run.mark("gather")
+    return _assemble(run, collected, own_of) if rank == 0 else {"plan": plan}
 
 
 def run_views(denoise_net: Callable, input_latents: torch.Tensor, c2ws: torch.Tensor, Ks: torch.Tensor,
               input_ids: Sequence[int], *, T: int = 21, chunk_strategy: str = "gt", options: dict | None = None,
               task: str = "img2img", **run_trajectory_kwargs) -> dict:
-    """One-pass generation of every non-input frame: `run_trajectory` over `plan_views(...)`; every other argument (`solver`,
-    `cache_interval`, `cache_levels`, `guidance_interval`, `guidance_rescale`, ...) and the result are `run_trajectory`'s ("anchor_latents": every generated frame as
-    later windows saw it)."""
+    """One-pass generation of every non-input frame: `run_trajectory` over `plan_views(...)`; every other argument (the sampler
+    options, `solver` to `guidance_rescale`, among them) and the result are `run_trajectory`'s ("anchor_latents": every generated
+    frame as later windows saw it)."""
     plan = plan_views(c2ws, input_ids, T, chunk_strategy, options, task)
     return run_trajectory(denoise_net, input_latents, c2ws, Ks, input_ids, T=T, plan=plan, **run_trajectory_kwargs)
 
@@ -515,10 +558,8 @@ def run_scene(denoise_net: Callable, ae, images: Sequence, c2ws: torch.Tensor, K
     and scored against the generated frames of those ids (`metrics.compare` on the uint8 frames) -> on rank 0
     "metrics" = {"frame_ids", "sse", "psnr", "ssim"}; in either mode.  `lpips` (a `metrics.LPIPS` on the device; frames of at
     least 32 x 32) adds "lpips" to that table: the complete score table without the frames leaving the card.
-    `cache_interval=` / `cache_levels=` (like every other sampler option) travel to `run_trajectory`; with `use_traj_prior=False`
-    and `targets=` this is the call that measures what the reuse of deep features costs in picture quality.  The same holds for
-    `guidance_interval=` / `guidance_rescale=`: `run_scene(..., use_traj_prior=False, targets=..., guidance_interval=...,
-    guidance_rescale=...)` is the call that measures what they do to picture quality."""
+    The sampler options (`run_window` lists them, `solver=` to `guidance_rescale=`) travel to `run_trajectory`; with
+    `use_traj_prior=False` and `targets=` this is the call that measures what one of them does to picture quality."""
     from . import frames
     device = torch.device(run_trajectory_kwargs.pop("device", None) or "cuda")
     ids = [int(i) for i in input_ids]

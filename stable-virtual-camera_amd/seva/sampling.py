@@ -19,6 +19,7 @@ Division of labour
 
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -397,6 +398,76 @@ def parse_guidance(interval, rescale) -> tuple:
     return iv, phi
 
 
+def resolve_options(solver=None, cache_interval=None, cache_levels=1, guidance_interval=None, guidance_rescale=None) -> dict:
+    """The opt-in options of `EulerEDMSampler` (its docstring says what each does), from arguments and environment, as the attributes
+    the sampler holds.  The only place that names the SEVA_* variables of the sampler: an argument that is None reads its variable,
+    any other argument wins over it.  SEVA_CACHE_LEVELS is read together with SEVA_CACHE_INTERVAL, that is only where
+    `cache_interval` is None, and where it is unset or empty the depth is the argument; an empty SEVA_SOLVER is unset too."""
+    env = os.environ.get
+    if guidance_interval is None:
+        guidance_interval = env("SEVA_GUIDANCE_INTERVAL")
+    if guidance_rescale is None:
+        guidance_rescale = env("SEVA_GUIDANCE_RESCALE")
+    guidance_interval, guidance_rescale = parse_guidance(guidance_interval, guidance_rescale)
+    if cache_interval is None:
+        cache_interval, cache_levels = env("SEVA_CACHE_INTERVAL"), env("SEVA_CACHE_LEVELS") or cache_levels
+    cache_interval, cache_levels = parse_cache(cache_interval, cache_levels)
+    if solver is None:
+        solver = env("SEVA_SOLVER") or "euler"
+    if solver not in SOLVERS:
+        raise ValueError(f"unknown solver {solver!r}: expected one of {SOLVERS}")
+    return dict(solver=solver, cache_interval=cache_interval, cache_levels=cache_levels, guidance_interval=guidance_interval,
+                guidance_rescale=guidance_rescale)
+
+
+def per_pass(v) -> tuple:
+    """One value or a (first pass, second pass) pair -> the pair (the reference's `--T N,21`, `cfg 3,2`; eval.py:1785-1789)."""
+    if isinstance(v, (list, tuple)):
+        assert len(v) == 2, f"one value or a (first pass, second pass) pair, not {v!r}"
+        return v[0], v[1]
+    return v, v
+
+
+def per_pass_options(solver=None, cache_interval=None, cache_levels=1, guidance_interval=None, guidance_rescale=None) -> tuple:
+    """The two-pass drivers' sampler options -> (first pass, second pass): the `EulerEDMSampler` keywords of each pass's windows.
+    Every option but `solver` takes one value or a pair (`per_pass`).  One value of `guidance_interval` is itself a 2-tuple
+    (`parse_guidance`), so there a pair is a 2-tuple whose elements are each None, a (lo, hi) tuple or a "lo,hi" string; anything
+    else -- None, a string, a 2-tuple of numbers -- is one interval for both passes.  `solver` is one value for the trajectory."""
+    iv = guidance_interval
+    if not (isinstance(iv, (list, tuple)) and len(iv) == 2 and all(e is None or isinstance(e, (list, tuple, str)) for e in iv)):
+        iv = (iv, iv)
+    pairs = dict(cache_interval=per_pass(cache_interval), cache_levels=per_pass(cache_levels), guidance_interval=iv,
+                 guidance_rescale=per_pass(guidance_rescale))
+    return tuple({"solver": solver, **{k: v[p] for k, v in pairs.items()}} for p in (0, 1))
+
+
+def step_kinds(sigmas_host, cache_interval: int, cache_levels: int, guidance_interval: tuple | None) -> list:
+    """The step schedule of a trajectory: per step, the keywords `EulerEDMSampler.__call__` adds to `sampler_step` -- {} for a full
+    guided step, {"shallow": L} for a shallow one, {"guided": False} for an unguided one, both where both hold.  `sigmas_host`: the
+    schedule's sigmas with the final 0, on the host; the other arguments as `resolve_options` returns them.
+    Deep-feature reuse: a full step at every `cache_interval`-th step and at the last one, shallow steps in between; and a shallow
+    call needs a full call of the same batch behind it, so a step whose guided flag differs from the previous step's is full too.
+    Guidance interval: decided on the schedule's own sigma (not sigma_hat: churn moves no step across a bound), in the sigmas' dtype
+    like the s_tmin / s_tmax test (`prepare_sampling_loop`).
+    A keyword is absent while its feature is off: the calls are then the ones made before, and a subclass's `sampler_step` never
+    sees the keyword."""
+    kinds, last, was_guided = [], len(sigmas_host) - 2, True
+    for i in range(len(sigmas_host) - 1):
+        guided = guidance_interval is None or bool(guidance_interval[0] < sigmas_host[i] <= guidance_interval[1])
+        full = not cache_interval or i % cache_interval == 0 or i == last or guided != was_guided
+        kind = {} if full else {"shallow": cache_levels}
+        if not guided:
+            kind["guided"] = False
+        kinds.append(kind)
+        was_guided = guided
+    return kinds
+
+
+def _network_depth(levels: int):
+    """Context of one network call at depth `levels`: L > 0 is `_native.shallow_network(L)`, 0 (the whole network) changes nothing."""
+    return _native.shallow_network(levels) if levels else contextlib.nullcontext()
+
+
 class EulerEDMSampler(object):
     """Reference sampling.py:301-405 (Euler discretisation of the EDM probability-flow ODE).
 
@@ -409,12 +480,12 @@ class EulerEDMSampler(object):
     runs the whole network iff i % N == 0 or it is the last step; every other step runs a shallow network call of depth
     `cache_levels` (1, 2 or 3: `SevaEngine.forward(shallow_levels=...)`), which recomputes the top of the UNet and takes the rest
     from the last full step.  0 or 1: off.  None reads SEVA_CACHE_INTERVAL and SEVA_CACHE_LEVELS (unset: off, depth 1).  The
-    schedule lives in `__call__`: a subclass that drives `sampler_step` itself gets full steps.
+    schedule (`step_kinds`) is followed by `__call__`: a subclass that drives `sampler_step` itself gets full steps.
 
     `guidance_interval` = (sigma_lo, sigma_hi) (opt-in, not in the reference; Kynkaanniemi et al. 2024): step i is guided iff
     sigma_lo < sigmas[i] <= sigma_hi -- the schedule's own sigma, so churn moves no step across a bound.  Every other step calls the
     denoiser on the conditional inputs alone (n frames instead of 2n, no guider) and takes the plain update.  None reads
-    SEVA_GUIDANCE_INTERVAL="lo,hi" (unset: off = every step guided).  The schedule lives in `__call__` too: a subclass that drives
+    SEVA_GUIDANCE_INTERVAL="lo,hi" (unset: off = every step guided).  This is part of `step_kinds` too: a subclass that drives
     `sampler_step` itself gets guided steps.  With `cache_interval`, a step whose guided flag differs from the previous step's is a
     full step as well (the network's batch changes there).
     `guidance_rescale` = phi in [0, 1] (opt-in, not in the reference; Lin et al. 2024): on guided steps the guided prediction of
@@ -427,22 +498,10 @@ class EulerEDMSampler(object):
                  s_tmax=float("inf"), s_noise=1.0, solver: str | None = None, check_finite: bool | None = None,
                  cache_interval: int | None = None, cache_levels: int | None = 1,
                  guidance_interval: tuple | str | None = None, guidance_rescale: float | None = None):
-        if guidance_interval is None:
-            guidance_interval = os.environ.get("SEVA_GUIDANCE_INTERVAL")
-        if guidance_rescale is None:
-            guidance_rescale = os.environ.get("SEVA_GUIDANCE_RESCALE")
-        self.guidance_interval, self.guidance_rescale = parse_guidance(guidance_interval, guidance_rescale)
-        if cache_interval is None:  # both from the environment (the depth: the argument where the variable is unset)
-            cache_interval = os.environ.get("SEVA_CACHE_INTERVAL")
-            cache_levels = os.environ.get("SEVA_CACHE_LEVELS") or cache_levels
-        self.cache_interval, self.cache_levels = parse_cache(cache_interval, cache_levels)
-        if solver is None:
-            solver = os.environ.get("SEVA_SOLVER") or "euler"
-        if solver not in SOLVERS:
-            raise ValueError(f"unknown solver {solver!r}: expected one of {SOLVERS}")
-        if solver == "dpmpp2m" and s_churn > 0:
+        # plain attributes (assignable afterwards): solver, cache_interval, cache_levels, guidance_interval, guidance_rescale
+        vars(self).update(resolve_options(solver, cache_interval, cache_levels, guidance_interval, guidance_rescale))
+        if self.solver == "dpmpp2m" and s_churn > 0:
             raise ValueError("solver 'dpmpp2m' is deterministic: it has no stochastic form here, s_churn must be 0")
-        self.solver = solver
         # True: one ops.tensor_range over the final latent after the last step; an inf / NaN raises.  None: SEVA_CHECK_FINITE=1.  Off by default
         self.check_finite = audit.check_finite_from_env() if check_finite is None else bool(check_finite)
         # multistep history (dpmpp2m only): the previous step's guided denoised latent D-, its sigma, and whether they are valid.
@@ -501,15 +560,15 @@ class EulerEDMSampler(object):
             sigma_generator = tqdm(sigma_generator, total=num_sigmas - 1, desc="Sampling", leave=False)
         return sigma_generator
 
-    def _step_math(self, sigma, next_sigma, x, eps, denoiser, scale, cond, uc, gamma, guider_kwargs, shallow=0, guided=True):
+    def _step_math(self, sigma, next_sigma, x, eps, gamma, operands):
         """Reference sampling.py:357-368 on f32 contiguous device tensors; sync-free once the guider's rule is cached,
-        which is what makes it capturable as one hipGraph (`_stepgraph.StepGraph`).  The step's kind (`guided`,
-        `guidance_rescale`) decides the operands alone (`_step_operands`)."""
+        which is what makes it capturable as one hipGraph (`_stepgraph.StepGraph`).  The step's kind (shallow, guided,
+        `guidance_rescale`) decides the operands alone: `operands(x_in, sigma_in)` is `sampler_step`'s `_step_operands`."""
         sigma_hat = sigma * (gamma + 1.0) + 1e-6
         noise_scale = (sigma_hat**2 - sigma**2) ** 0.5 * self.s_noise
         x_noised = torch.empty_like(x)
         ops.add_noise(x, eps, _f32c(noise_scale), x_noised)
-        den, fs = self._step_operands(denoiser, x_noised, sigma_hat, scale, cond, uc, x, guider_kwargs, shallow, guided)
+        den, fs = operands(x_noised, sigma_hat)
         dt = next_sigma - sigma_hat
         out = torch.empty_like(x)
         if fs is not None:
@@ -518,19 +577,16 @@ class EulerEDMSampler(object):
             ops.euler_step(x_noised, den, sigma_hat, dt, out)
         return out
 
-    def _denoised_pair(self, denoiser, x_in, sigma_in, cond, uc, shallow=0):
+    def _denoised_pair(self, denoiser, x_in, sigma_in, cond, uc):
         """The [uncond ; cond] denoised latents for (x_in, sigma_in): one CFG-batched network call, or under `cfg_split`
-        this rank's half of it and the other rank's.  `shallow` = L > 0: the network call runs inside
-        `_native.shallow_network(L)` (under `cfg_split` on either rank: each owns an engine, both follow one schedule)."""
-        if shallow:
-            with _native.shallow_network(shallow):
-                return self._denoised_pair(denoiser, x_in, sigma_in, cond, uc)
+        this rank's half of it and the other rank's."""
         if self.cfg_split is None:
             return denoiser(*self.guider.prepare_inputs(x_in, sigma_in, cond, uc))
         return self._denoise_cfg_split(denoiser, x_in, sigma_in, cond, uc)
 
-    def _step_operands(self, denoiser, x_in, sigma_in, scale, cond, uc, x, guider_kwargs, shallow=0, guided=True):
-        """(den, fs) for a step's update kernel, whatever the step's kind.
+    def _step_operands(self, denoiser, x_in, sigma_in, scale, cond, uc, guider_kwargs, shallow=0, guided=True):
+        """(den, fs) for a step's update kernel, whatever the step's kind.  `shallow` = L > 0: the step's one network call, guided
+        or not, runs at depth L (`_network_depth`; under `cfg_split` on either rank: each owns an engine, both follow one schedule).
         Guided, `guidance_rescale` 0: `_guidance_operands` of the CFG-batched call -- the fused kernels combine.
         Guided, `guidance_rescale` = phi > 0: (D, None) with D from `ops.cfg_rescale` on the [uncond ; cond] pair, a latent-sized
         round trip that the fused path does not make; needs a guider that states its `frame_scale`.
@@ -538,19 +594,17 @@ class EulerEDMSampler(object):
         and under `cfg_split` no collective: both ranks of the pair make this call themselves and go on holding identical state
         (the half batch is bitwise the half of the full batch).  The denoiser gets a dictionary of its own (`DiscreteDenoiser`
         pops "replace" from the one it is handed)."""
-        if not guided:
-            if shallow:
-                with _native.shallow_network(shallow):
-                    return _f32c(denoiser(x_in, sigma_in, dict(cond))), None
-            return _f32c(denoiser(x_in, sigma_in, dict(cond))), None
         phi = self.guidance_rescale
-        if phi > 0 and not hasattr(self.guider, "frame_scale"):
+        if guided and phi > 0 and not hasattr(self.guider, "frame_scale"):
             raise ValueError("guidance_rescale > 0 needs a guider that states its per-frame scale (`frame_scale`): "
                              f"{type(self.guider).__name__} has none")
-        denoised2 = self._denoised_pair(denoiser, x_in, sigma_in, cond, uc, shallow)
-        den, fs = self._guidance_operands(denoised2, sigma_in, scale, x, guider_kwargs)
+        with _network_depth(shallow):
+            if not guided:
+                return _f32c(denoiser(x_in, sigma_in, dict(cond))), None
+            denoised2 = self._denoised_pair(denoiser, x_in, sigma_in, cond, uc)
+        den, fs = self._guidance_operands(denoised2, sigma_in, scale, x_in, guider_kwargs)
         if phi > 0:
-            D = torch.empty_like(x)
+            D = torch.empty_like(x_in)
             ops.cfg_rescale(den, fs, phi, D)
             return D, None
         return den, fs
@@ -603,14 +657,13 @@ class EulerEDMSampler(object):
         c = torch.where(second, -one_a * inv_2r, zero)
         return a, b, c
 
-    def _multistep_math(self, sigma, next_sigma, x, prev_sigma, hist, denoiser, scale, cond, uc, guider_kwargs, shallow=0,
-                        guided=True):
+    def _multistep_math(self, sigma, next_sigma, x, prev_sigma, hist, operands):
         """One DPM-Solver++(2M) step on f32 contiguous device tensors: no noise, no sigma_hat; guidance, update and the new
         history in ONE kernel (`ops.cfg_multistep`), which reads D- from `hist` and leaves D there.  Sync-free like
         `_step_math`, and the same code for the first, the second-order and the last step (they differ in a, b, c only), so
         one hipGraph serves them all.  An unguided or a rescaled step hands the kernel its D with scale=None
         (`_step_operands`); the history is whatever D the step used."""
-        den, fs = self._step_operands(denoiser, x, sigma, scale, cond, uc, x, guider_kwargs, shallow, guided)
+        den, fs = operands(x, sigma)
         a, b, c = self.multistep_coefficients(sigma, next_sigma, prev_sigma)
         out = torch.empty_like(x)
         ops.cfg_multistep(x, den, fs, hist, a, b, c, out, hist)
@@ -655,16 +708,17 @@ class EulerEDMSampler(object):
             flat += ("unguided",)
         elif self.guidance_rescale > 0:
             flat += ("rescale", float(self.guidance_rescale))
+        operands = lambda x_in, sigma_in: self._step_operands(denoiser, x_in, sigma_in, scale, cond, uc, guider_kwargs, shallow, guided)  # noqa: E731
         # per solver: the cache key (everything the closure holds), the sync-free step as a closure, the fourth graph input
         if multistep:  # deterministic: no noise draw, no add_noise; `gamma` has nothing to act on
             hist, fourth = self._multistep_history(x, sigma)
             key = ("dpmpp2m", tuple(x.shape), hist, self.guider, denoiser) + flat
-            fn = lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, denoiser, scale, cond, uc, guider_kwargs, shallow, guided)  # noqa: E731
+            fn = lambda s, n, xx, ps: self._multistep_math(s, n, xx, ps, hist, operands)  # noqa: E731
         else:
             fourth = _f32c(self.noise_fn(x))  # eps, drawn eagerly: the generator advances per step exactly as in the reference
             gamma = float(gamma)
             key = (tuple(x.shape), gamma, float(self.s_noise), self.guider, denoiser) + flat
-            fn = lambda s, n, xx, ee: self._step_math(s, n, xx, ee, denoiser, scale, cond, uc, gamma, guider_kwargs, shallow, guided)  # noqa: E731
+            fn = lambda s, n, xx, ee: self._step_math(s, n, xx, ee, gamma, operands)  # noqa: E731
         # the step kind names the graph entry: 0 / L as ever for a guided step, (0 / L, "unguided") for an unguided one
         kind = shallow if guided else (shallow, "unguided")
         # keep: the graph reads the warm-up step's rule tensor, which must therefore outlive `reset_rule_cache`
@@ -678,26 +732,15 @@ class EulerEDMSampler(object):
                  num_steps: int | None = None, verbose: bool = True, **guider_kwargs) -> torch.Tensor:
         uc = cond if uc is None else uc
         x, s_in, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x, cond, uc, num_steps)
-        every, last = self.cache_interval, num_sigmas - 2
-        interval, was_guided = self.guidance_interval, True
+        kinds = step_kinds(self._sigmas_host, self.cache_interval, self.cache_levels, self.guidance_interval)
         for i in self.get_sigma_gen(num_sigmas, verbose=verbose):
             gamma = (
                 min(self.s_churn / (num_sigmas - 1), 2**0.5 - 1)
                 if self.s_tmin <= self._sigmas_host[i] <= self.s_tmax
                 else 0.0
             )
-            # deep-feature reuse: a full step at every `every`-th step and at the last one, shallow steps in between
-            # (the keyword is passed on shallow steps only: with the mode off the calls are the ones made before)
-            # guidance interval: decided on the schedule's own sigma (not sigma_hat: churn moves no step across a bound), in the
-            # sigmas' dtype like the test above; the keyword is passed on unguided steps only
-            guided = interval is None or bool(interval[0] < self._sigmas_host[i] <= interval[1])
-            # (a shallow call needs a full call of the same batch behind it: where the guided flag changes, the step is full)
-            kind = {} if not every or i % every == 0 or i == last or guided != was_guided else {"shallow": self.cache_levels}
-            if not guided:
-                kind["guided"] = False
-            was_guided = guided
             x = self.sampler_step(s_in * sigmas[i], s_in * sigmas[i + 1], denoiser, x, scale, cond, uc,
-                                  gamma, **kind, **guider_kwargs)
+                                  gamma, **kinds[i], **guider_kwargs)
         # once per trajectory, after the last step (never inside the loop): a split-K consumer that gave up waiting for its
         # producer (csrc/gemm.hip) left a wrong tile behind -- make that an error instead of a silently wrong sample
         if x.is_cuda:

@@ -11,7 +11,13 @@ the engine's scalar attributes, a SHA-256 per packed weight, the arena's keys, t
 record byte-identical: run the tool on a worktree of the parent commit and on the new tree, and hand the first run's digest file
 to the second through --against (exit status 1 on any difference; --out keeps the records for a diff).
 
-The tool fails if its configurations together never reach one of the features listed in `COVERAGE`.
+The sampler's opt-in modes (`cache_interval`, `guidance_interval`, `guidance_rescale`; as arguments and through their SEVA_* variables)
+run ten steps behind a network that writes its batch and the depth asked of it into the record, and the record states the options the
+sampler resolved.  The drivers (`seva.pipeline.run_trajectory` / `run_views`, one process) do compute, on the torch emulation of the
+operators that tests/ keeps: their record is the plan, what every window's sampler was built with, the timers' keys and a SHA-256 of
+each result.
+
+The tool fails if its configurations together never reach one of the features in the table that `coverage()` prints.
 """
 import argparse
 import bisect
@@ -430,8 +436,13 @@ def operator_records():
 
 
 # ------------------------------------------------------------------------------------------------------------------ sampler
-SAMPLER_OPS = ("scale_rows", "add_noise", "replace_blend", "denoiser_combine", "cfg_combine", "cfg_euler", "euler_step", "cfg_multistep")
+SAMPLER_OPS = ("scale_rows", "add_noise", "replace_blend", "denoiser_combine", "cfg_combine", "cfg_euler", "euler_step", "cfg_multistep",
+               "cfg_rescale")
 SAMPLER_T, SAMPLER_STEPS = 4, 3
+# the opt-in modes: the 10-step case of tests/test_guidance_cpu.py -- cache_interval 3 at depth 2 and an interval that guides steps 3..7
+# give F S S F S S F S F F over unguided, guided, unguided: every step kind occurs
+MODE_STEPS, MODE_CACHE, MODE_INTERVAL, MODE_RESCALE = 10, dict(cache_interval=3, cache_levels=2), (3.0, 25.0), 0.7
+NETWORK_CALLS = []  # (rows, rows of a guided call, shallow depth) of every network call of the opt-in sampler records, for the coverage table
 
 
 @contextlib.contextmanager
@@ -466,6 +477,17 @@ def analytic_denoiser(xx, ss, cc):
     return mu * (1 - k) + xx * k
 
 
+def depth_recording_denoiser(host):
+    """A network of any batch that writes its rows and the depth the sampler asked for (`_native.shallow_network`) into the record:
+    a shallow step differs from a full one, an unguided step (n rows) from a guided one (2n)."""
+    def denoiser(xx, ss, cc):
+        L = nv.network_shallow_levels()
+        host.append(f"host network rows={xx.shape[0]} shallow_levels={L}")
+        NETWORK_CALLS.append((xx.shape[0], 2 * SAMPLER_T, L))
+        return torch.zeros_like(xx)
+    return denoiser
+
+
 def sampler_guider(S, kind):
     """(guider, guider_kwargs)"""
     T = SAMPLER_T
@@ -489,22 +511,33 @@ def sampler_guider(S, kind):
     return PlainGuider(), {}
 
 
-def sampler_record(solver, kind, s_churn=0.0):
+SAMPLER_ATTRS = ("solver", "cache_interval", "cache_levels", "guidance_interval", "guidance_rescale")
+
+
+def sampler_record(solver, kind, s_churn=0.0, env=None, **opts):
+    """Default options: three steps.  With `env` or sampler options: `MODE_STEPS` steps behind the depth-recording network, and the
+    record states the options the sampler resolved."""
     from seva import sampling as S
     guider, guider_kwargs = sampler_guider(S, kind)
-    with environment({}):
-        sm = S.EulerEDMSampler(S.DDPMDiscretization(), guider, num_steps=SAMPLER_STEPS, verbose=False, device="cpu", s_churn=s_churn,
-                               solver=solver)
+    modes = env is not None or bool(opts)
+    with environment(env or {}):
+        sm = S.EulerEDMSampler(S.DDPMDiscretization(), guider, num_steps=MODE_STEPS if modes else SAMPLER_STEPS, verbose=False,
+                               device="cpu", s_churn=s_churn, solver=solver, **opts)
         sm.noise_fn = torch.zeros_like
         inp = {"x": torch.zeros(SAMPLER_T, 4, 8, 8)}
         kept, host = [], []
+        net = depth_recording_denoiser(host) if modes else analytic_denoiser
 
         def run():
             with keeping_arguments(kept, host):
-                return sm(analytic_denoiser, inp["x"], 2.0, {}, {}, **guider_kwargs), kept
+                return sm(net, inp["x"], 2.0, {}, {}, **guider_kwargs), kept
 
         lines = traced(run, lambda: [("in", inp), ("ms", {"den": sm._ms_den})])
-    record(f"sampler {solver} {kind} s_churn={s_churn}", lines + host)
+    name = f"sampler {solver} {kind} s_churn={s_churn}"
+    if modes:
+        name += f" {env_tag(env or {}, **opts)} steps={MODE_STEPS}"
+        lines = ["attr " + json.dumps({k: getattr(sm, k) for k in SAMPLER_ATTRS})] + lines
+    record(name, lines + host)
 
 
 def denoiser_record():
@@ -530,6 +563,132 @@ def sampler_configurations():
         sampler_record("euler", kind, s_churn=0.5)
         sampler_record("dpmpp2m", kind)
     denoiser_record()
+    iv_env = "%g,%g" % MODE_INTERVAL
+    for solver in S.SOLVERS:
+        # each mode alone and all three together, as arguments
+        sampler_record(solver, "multiview", cache_interval=3)
+        sampler_record(solver, "multiview", guidance_interval=MODE_INTERVAL)
+        sampler_record(solver, "multiview", guidance_rescale=MODE_RESCALE)
+        sampler_record(solver, "multiview", **MODE_CACHE, guidance_interval=MODE_INTERVAL, guidance_rescale=MODE_RESCALE)
+        # each through its variable; the depth's variable with and without the interval's (without: the mode stays off)
+        sampler_record(solver, "multiview", env={"SEVA_CACHE_INTERVAL": 3})
+        sampler_record(solver, "multiview", env={"SEVA_GUIDANCE_INTERVAL": iv_env})
+        sampler_record(solver, "multiview", env={"SEVA_GUIDANCE_RESCALE": MODE_RESCALE})
+        sampler_record(solver, "multiview", env={"SEVA_CACHE_INTERVAL": 3, "SEVA_CACHE_LEVELS": 2})
+        sampler_record(solver, "multiview", env={"SEVA_CACHE_LEVELS": 2})
+        # the depth's variable is not read where the interval is an argument; an explicit argument wins over every variable
+        sampler_record(solver, "multiview", env={"SEVA_CACHE_LEVELS": 2}, cache_interval=3)
+        sampler_record(solver, "multiview", env={"SEVA_CACHE_INTERVAL": 2, "SEVA_GUIDANCE_INTERVAL": "1,2", "SEVA_GUIDANCE_RESCALE": 1,
+                                                 "SEVA_SOLVER": "euler" if solver == "dpmpp2m" else "dpmpp2m"},
+                       **MODE_CACHE, guidance_interval=MODE_INTERVAL, guidance_rescale=MODE_RESCALE)
+        # SEVA_SOLVER instead of the argument
+        sampler_record(None, "multiview", env={"SEVA_SOLVER": solver}, **MODE_CACHE)
+        # a guider without `frame_scale` under the interval (full and shallow)
+        sampler_record(solver, "plain", guidance_interval=MODE_INTERVAL)
+        sampler_record(solver, "plain", guidance_interval=MODE_INTERVAL, **MODE_CACHE)
+    sampler_record(None, "multiview", env={"SEVA_SOLVER": ""}, guidance_interval=MODE_INTERVAL)  # empty: unset
+    sampler_record("euler", "multiview", s_churn=0.5, guidance_interval=MODE_INTERVAL)
+    sampler_record("euler", "multiview", s_churn=4.0, guidance_interval=MODE_INTERVAL, guidance_rescale=MODE_RESCALE, **MODE_CACHE)
+
+
+# ------------------------------------------------------------------------------------------------------------------ drivers
+DRIVER_VIEWS, DRIVER_T, DRIVER_STEPS = 43, 21, 3  # tests/test_pipeline_cpu.py, test_step_cache_cpu.py, test_guidance_cpu.py: their sizes
+DRIVER_SEEN = {"per-pass pair": 0, "keep_own": 0}
+
+
+class StandInAE:
+    """cheap deterministic maps in place of the VAE: (k,4,h,w) -> (k,3,h,w) and back"""
+
+    def decode(self, z):
+        return torch.tanh(z[:, :3] * 0.5 + 0.1 * z[:, 3:4])
+
+    def encode(self, x):
+        return torch.cat([x * 1.5, x.mean(1, keepdim=True)], 1)
+
+
+@contextlib.contextmanager
+def emulated_operators():
+    """The drivers compute: `seva.ops` becomes the torch emulation of tests/ (fake_ops.py, and the two newer sampler operators)."""
+    import fake_guidance_ops
+    import fake_ops
+    from seva import geometry
+    from test_solver_dpmpp2m_cpu import _fake_cfg_multistep
+    new = {name: getattr(fake_ops, name) for name in dir(fake_ops)
+           if not name.startswith("_") and callable(getattr(fake_ops, name)) and hasattr(ops, name)}
+    new.update(cfg_multistep=_fake_cfg_multistep, cfg_rescale=fake_guidance_ops.cfg_rescale)
+    saved = {name: getattr(ops, name) for name in new}
+    saved_device = geometry._compute_device
+    for name, fn in new.items():
+        setattr(ops, name, fn)
+    geometry._compute_device = lambda *a: CPU
+    try:
+        yield
+    finally:
+        for name, fn in saved.items():
+            setattr(ops, name, fn)
+        geometry._compute_device = saved_device
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().contiguous().view(-1).view(U8).numpy().tobytes()).hexdigest()
+
+
+def driver_record(name, views=False, env=None, **kw):
+    """One run of `run_trajectory` (`views`: `run_views`) on one process: the plan, what every window's sampler was built with, the
+    timers' keys, and the results by SHA-256."""
+    from seva import pipeline
+    from test_pipeline_cpu import _fake_net, _scene
+    c2ws, Ks, lat, tok = _scene(DRIVER_VIEWS)
+    built, timers = [], {}
+
+    def hook(sm):
+        built.append([type(sm.guider).__name__, getattr(sm.guider, "num_frames", None)] + [getattr(sm, k) for k in SAMPLER_ATTRS])
+
+    with environment(env or {}):
+        res = (pipeline.run_views if views else pipeline.run_trajectory)(
+            _fake_net, lat, c2ws, Ks, [0], clip_token=tok, T=DRIVER_T, num_steps=DRIVER_STEPS, seed=23, device="cpu",
+            sampler_hook=hook, timers=timers, **kw)
+    plan = res["plan"]
+    wins = plan.pass1 + plan.pass2
+    assert len(built) == len(wins), (name, len(built), len(wins))  # one process: every window, in plan order
+    lines = [f"plan pass1={len(plan.pass1)} pass2={len(plan.pass2)} serial={plan.pass1_serial} T1={plan.T1} T2={plan.T2}",
+             "plan global_index " + json.dumps([w.global_index for w in wins]), "plan anchors " + json.dumps(plan.anchor_ids)]
+    lines += [f"window pass={w.pass_id} index={w.index} slots={len(w.slot_frame)} " + json.dumps(b) for w, b in zip(wins, built)]
+    lines.append("timers " + json.dumps(sorted(timers)))
+    lines.append("windows " + json.dumps([t[:2] for t in timers["windows"]]))
+    lines.append("result " + json.dumps(sorted(res)) + " frame_ids " + sha(torch.tensor(res["frame_ids"])))
+    lines.append(f"latents {list(res['latents'].shape)} {sha(res['latents'])}")
+    lines += [f"anchor_latent {fid} {sha(z)}" for fid, z in res["anchor_latents"].items()]
+    if "rgb" in res:
+        lines.append(f"rgb {list(res['rgb'].shape)} {sha(res['rgb'])}")
+    opts1, opts2 = ({json.dumps(b[2:]) for w, b in zip(wins, built) if w.pass_id == p} for p in (1, 2))
+    DRIVER_SEEN["per-pass pair"] += bool(opts1 and opts2 and opts1 != opts2)
+    # `keep_own`: a frame's output is its own sample, while later windows saw the latent that came back from the hand-off
+    DRIVER_SEEN["keep_own"] += any(not torch.equal(res["latents"][fid], z) for fid, z in res["anchor_latents"].items()
+                                   if not plan.pass2)
+    record(f"driver {name}", lines)
+
+
+def driver_configurations():
+    with emulated_operators():
+        driver_record("default")
+        driver_record("refine_anchors=False", refine_anchors=False)
+        driver_record("first_pass_strategy=gt", first_pass_strategy="gt")
+        driver_record("cfg=(3.0, 2.0) guider=(1, 2)", cfg=(3.0, 2.0), guider=(1, 2))
+        driver_record("solver=dpmpp2m", solver="dpmpp2m")
+        driver_record("cache_interval=(3, 2) cache_levels=(1, 2)", cache_interval=(3, 2), cache_levels=(1, 2))
+        driver_record("guidance_interval=((0.5, 3), None) guidance_rescale=(0.0, 0.5)",
+                      guidance_interval=((0.5, 3), None), guidance_rescale=(0.0, 0.5))
+        driver_record("guidance_interval=(0.3, 5)", guidance_interval=(0.3, 5))
+        driver_record("guidance_interval=('0.3,5', (0.5, 3))", guidance_interval=("0.3,5", (0.5, 3)))
+        driver_record("guidance_interval=((0.3, 5), None) guidance_rescale=(None, 0) GUIDANCE_INTERVAL=0.5,3 GUIDANCE_RESCALE=0.7",
+                      env={"SEVA_GUIDANCE_INTERVAL": "0.5,3", "SEVA_GUIDANCE_RESCALE": "0.7"},
+                      guidance_interval=((0.3, 5), None), guidance_rescale=(None, 0))
+        driver_record("handoff=rgb", handoff="rgb", ae=StandInAE())
+        driver_record("handoff=rgb run_views", views=True, handoff="rgb", ae=StandInAE())
+        driver_record("anchor_ids=[7, 14, 21, 28, 35, 42]", anchor_ids=[7, 14, 21, 28, 35, 42])
+        driver_record("run_views", views=True)
+        driver_record("run_views chunk_strategy=gt-nearest", views=True, chunk_strategy="gt-nearest")
 
 
 # ------------------------------------------------------------------------------------------------------------------ coverage
@@ -564,6 +723,12 @@ def coverage():
     table["shallow call, entry with stats"] = len(SHALLOW_WITH_STATS)  # a shallow call whose entering tensor came with statistics
     table["seva_cfg_multistep_f32 scale"] = seen("seva_cfg_multistep_f32", lambda r: field(r, "arg2"))
     table["seva_cfg_multistep_f32 no scale"] = seen("seva_cfg_multistep_f32", lambda r: not field(r, "arg2"))
+    table["seva_cfg_rescale_f32"] = seen("seva_cfg_rescale_f32")
+    table["sampler: shallow step"] = sum(1 for rows, guided_rows, L in NETWORK_CALLS if L)
+    table["sampler: unguided step"] = sum(1 for rows, guided_rows, L in NETWORK_CALLS if rows != guided_rows)
+    table["sampler: unguided shallow step"] = sum(1 for rows, guided_rows, L in NETWORK_CALLS if L and rows != guided_rows)
+    table["driver: per-pass pair"] = DRIVER_SEEN["per-pass pair"]
+    table["driver: keep_own branch"] = DRIVER_SEEN["keep_own"]
     print("\ncoverage (recorded calls over all configurations)")
     for k, v in table.items():
         print(f"  {k:32s} {v:7d}")
@@ -583,6 +748,7 @@ vae_configurations()
 clip_record()
 operator_records()
 sampler_configurations()
+driver_configurations()
 missing = coverage()
 split_ok = kv_split_check()
 digests = {name: hashlib.sha256(text.encode()).hexdigest() for name, text in RECORDS.items()}
